@@ -24,12 +24,21 @@ bracketed by barrier + synchronize, and `value` is the MEDIAN sub-region's rate 
 The passes go through smhv_pipeline_submit: the library owns the streams and the schedule (--pipeline-depth batches in
 flight, default 4); `value_depth1` is the same workload with ONE batch in flight, timed right after.
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  Extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run (`--gpus N --steps K --warmup W`) does only
+what that line's headline needs: set-up, warm-up, the K timed steps, the outputs of the last step (--dump-outputs DIR) and
+the line (metric, value, unit, higher_is_better, dtype, ms_per_step, the configuration and the timed region's own figures).
+`--full` adds every other leg after the timed region, with these extra objects among others:
   roofline     -- the dominant HBM streaming kernel: algorithmic bytes / hipEvent launch duration on the run's stream
-  stages_ms    -- average per-stage device time over the timed passes
+  stages_ms    -- average per-stage device time over the timed passes (stage timing is on only in a --full run)
   lsd          -- workload statistics of the (non-HBM-bound) ray-cast stage
   cpu_baseline -- the C oracle (a port of the reference's vision-cpu; the Rust original cannot be built here) timed on this
                   box's host cores on a bounded sample of the same frames, plus its single-thread per-stage split
+and value_depth1, slots_identical, all_map_open, device_during_timed_region, ingest, trait_path, co_residency, real_samples.
+
+--dump-outputs DIR writes what the last timed pass handed its caller as DIR/<name>.npy (float32 / float64): every field of
+the per-frame result records (lines, n_lines, mpx, ... -- entries past n_lines zeroed, an absent mpx / minimap 0 beside has_mpx / has_minimap = 0) and the
+output images of a fixed, seeded sample of frames (image_frames.npy), at most 64 MB in all.  Inputs are generated from
+fixed seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -111,7 +120,15 @@ def parse_args():
     ap.add_argument("--ingest-affinity", default="on", choices=("on", "off"), help="A/B: the ingest queue's hashing threads and the producer on the CPUs next to the GPU (on) or left to the scheduler")
     ap.add_argument("--ingest-frames", type=int, default=8192,
                     help="frames streamed through the ingest queue for the PCIe-inclusive figure (0 = skip; rank 0, N=1, config 2 only)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline after the timed region (stage timing, roofline and traffic probe, depth-1 region, "
+                         "slot / record checks, ingest, trait path, co-residency, real samples, CPU baseline); the options above tune those legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed pass as DIR/<name>.npy (records of every frame, images of a seeded sample of frames; <= 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def self_launch(args):
@@ -891,6 +908,57 @@ def traffic_probe(args, n, W, H, stages, kname, timeout=150):
                      "reads = 2 x FETCH_SIZE (gfx950 correction) = %.1f MB, writes = %.1f MB per launch" % (rd / 1e6, wr / 1e6))
 
 
+DUMP_BYTES = 64 * 10 ** 6                                  # --dump-outputs: all files together
+DUMP_SEED = 20240611                                       # the sample of frames (and, for very large frames, of rows) whose images are written
+
+
+def dump_outputs(smh, np, out_dir, recs, fb, stages, scales_start_y):
+    """--dump-outputs: what the last timed pass handed its caller.  recs: ctypes FrameResult array (every frame of the pass; N > 1:
+    the records gathered to rank 0); fb: the slot that ran the pass (this rank's frames); scales_start_y[i]: frame i's first
+    defined row of the find_scales_preprocess image (rows above it are not an output: written as 0)."""
+    L = smh._lib
+    a = np.ctypeslib.as_array(recs)
+    n_lines = a["n_lines"].astype(np.int64)
+    live = np.arange(L.MAX_LINES)[None, :] < n_lines[:, None]        # entries past n_lines are not results
+    out = {"lines": np.stack([a["lines"][c] for c in ("x0", "y0", "x1", "y1")], axis=-1).astype(np.float32) * live[..., None],
+           "length_px": np.where(live, a["length_px"], 0.0), "meters": np.where(live, a["meters"], 0.0),
+           "angle": np.where(live, a["angle"], 0.0).astype(np.float32),
+           "mpx": np.where(a["has_mpx"] != 0, a["mpx"], 0.0),
+           "minimap": np.where(a["has_minimap"][:, None] != 0, a["minimap"].astype(np.float64), 0.0)}
+    for k in ("map_open", "n_lines", "has_mpx", "has_minimap", "n_mask_px", "red_pixels", "rounds", "ray_steps", "status"):
+        out[k] = a[k].astype(np.float64)
+    x, y, w, h = fb.roi
+    kinds = [(name, which, shape) for bit, name, which, shape in (
+        (0x2, "ui_map", L.IMAGE_UI_MAP, (h, w, 4)), (0x1, "marker_mask", L.VIEW_LSD_INPUT, (h, w)),
+        (0x4, "ocr", L.VIEW_OCR_INPUT, (h // 2, w // 2)), (0x8, "scales", L.VIEW_FIND_SCALES_INPUT, (h // 2, w // 2))) if stages & bit]
+    rng = np.random.default_rng(DUMP_SEED)
+    per_frame = sum(4 * int(np.prod(s)) for _, _, s in kinds)
+    room = DUMP_BYTES - sum(v.nbytes for v in out.values()) - 8 * 4096
+    n = len(scales_start_y)
+    if per_frame:
+        k = int(max(1, min(4, n, room // per_frame)))
+        frames = np.sort(rng.choice(n, k, replace=False))
+        frac = min(1.0, room / float(k * per_frame))       # < 1 only when one frame's images alone exceed the budget: a seeded sample of rows
+        out["image_frames"] = frames.astype(np.float64)
+        for name, which, shape in kinds:
+            rows = np.arange(shape[0]) if frac >= 1.0 else np.sort(rng.choice(shape[0], max(1, int(shape[0] * frac)), replace=False))
+            imgs = []
+            for f in frames:
+                img = fb.read_image(which, int(f)).astype(np.float32)
+                if name == "scales":
+                    img[:scales_start_y[f]] = 0.0
+                imgs.append(img[rows])
+            out[name] = np.stack(imgs)
+            if frac < 1.0:
+                out[name + "_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        if not np.isfinite(v).all():                       # every file holds numbers a comparison can use
+            raise SystemExit("bench.py: --dump-outputs: %s holds a value that is not finite" % k)
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return sum(v.nbytes for v in out.values())
+
+
 def main():
     args = parse_args()
     if args.config is None:
@@ -933,10 +1001,15 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
+    if args.dump_outputs and (args.config == 0 or args.node):
+        raise SystemExit("bench.py: --dump-outputs writes the outputs of the pipeline path (not of --config 0 or --node)")
     if args.config == 0:
         return config0(args)
     if args.node:
         return node_main(args, cfg, n, W, H, stages, rounds, custom)
+    # a plain run times the headline and nothing else; --full adds the legs after the timed region
+    stage_timing = args.full and not args.no_stage_timing
+    depth1 = args.full and not args.no_depth1
 
     import numpy as np
     import torch
@@ -958,7 +1031,7 @@ def main():
     from squad_mortar_helper_amd import synth
 
     first = rank * n                                   # block shard of the global batch
-    keep = max(args.cpu_sample, 8) if (rank == 0 and world == 1) else 8
+    keep = (max(args.cpu_sample, 8) if (rank == 0 and world == 1) else 8) if args.full else 0    # host copies: only the --full legs read them
     frames, infos, frames_host, h2d_s = upload_synthetic(torch, synth, W, H, n, first, args.lines, args.distinct, torch.device("cuda", local_rank), keep)
 
     vision = smh.HipVision.init(local_rank)
@@ -988,6 +1061,7 @@ def main():
     pending = [False] * depth
     gather_stream = torch.cuda.Stream() if gather is not None else None
     submitted = [0]
+    latest_slot = [None]                               # the slot of the pipeline's most recent pass (--dump-outputs)
 
     def flush_gather(slot):
         pipe.wait(slot)
@@ -1005,6 +1079,8 @@ def main():
         if gather is not None and p is pipe:
             submitted[0] += 1
             pending[slot] = True
+        if p is pipe:
+            latest_slot[0] = slot
         return slot
 
     def step(p=pipe):
@@ -1051,21 +1127,28 @@ def main():
         if extra_warmup and rank == 0:
             print("bench.py: %d extra warm-up step(s): the pipeline measures both line searches on the workload before it settles" % extra_warmup, file=sys.stderr)
     barrier()
-    if not args.no_stage_timing:
+    if stage_timing:
         for b in pipe.slots:
             b.enable_timing(True)
-    try:
-        pr = torch.cuda.get_device_properties(local_rank)
-        watch = DeviceWatch("%04x:%02x:%02x" % (pr.pci_domain_id, pr.pci_bus_id, pr.pci_device_id) if hasattr(pr, "pci_bus_id") else None)
-    except Exception:  # noqa: BLE001  (diagnostic only)
-        watch = None
+    watch = None
+    if args.full:
+        try:
+            pr = torch.cuda.get_device_properties(local_rank)
+            watch = DeviceWatch("%04x:%02x:%02x" % (pr.pci_domain_id, pr.pci_bus_id, pr.pci_device_id) if hasattr(pr, "pci_bus_id") else None)
+        except Exception:  # noqa: BLE001  (diagnostic only)
+            watch = None
     if watch is not None and watch.files:
         with watch:
             regions = timed(pipe, args.steps)
     else:
         regions = timed(pipe, args.steps)
+    dump_slot = latest_slot[0]
+    if args.dump_outputs and rank == 0:                # before any later leg submits to the pipeline again
+        dump_recs = gather.records(dump_slot) if gather is not None else pipe.slots[dump_slot].read_results(0, n)
+        nb = dump_outputs(smh, np, args.dump_outputs, dump_recs, pipe.slots[dump_slot], stages, [i["scales_start_y"] for i in infos])
+        print("bench.py: outputs of the last timed pass (slot %d) written to %s (%.1f MB)" % (dump_slot, args.dump_outputs, nb / 1e6), file=sys.stderr)
     stages_ms = None
-    if not args.no_stage_timing:
+    if stage_timing:
         first = (args.warmup + extra_warmup) * rounds            # submissions before the timed region: slot = submission % depth
         per = [pipe.slots[(first + i) % depth].stage_ms() for i in range(min(depth, args.steps * rounds))]
         stages_ms = {k: float(np.mean([p[k] for p in per])) for k in per[0]}
@@ -1079,18 +1162,19 @@ def main():
     svc_stats = pipe.search_stats()                     # the frame-granular line search's own counters (None: batch-granular search)
     svc_geo = pipe.peek() if svc_stats else None
     # ---- every slot of the pipeline must hold the same records (same frames, same stages): byte for byte ----
-    used = min(depth, args.steps * rounds + args.warmup * rounds)
-    slot_bytes = [bytes(pipe.slots[s].read_results(0, n)) for s in range(used)]
-    slots_identical = all(sb == slot_bytes[0] for sb in slot_bytes)
-    if not slots_identical:
-        bad = [s for s in range(used) if slot_bytes[s] != slot_bytes[0]]
-        raise SystemExit("bench.py: pipeline slots %s hold records that differ from slot 0's (same frames, same stages)" % bad)
+    if args.full:
+        used = min(depth, args.steps * rounds + args.warmup * rounds)
+        slot_bytes = [bytes(pipe.slots[s].read_results(0, n)) for s in range(used)]
+        slots_identical = all(sb == slot_bytes[0] for sb in slot_bytes)
+        if not slots_identical:
+            bad = [s for s in range(used) if slot_bytes[s] != slot_bytes[0]]
+            raise SystemExit("bench.py: pipeline slots %s hold records that differ from slot 0's (same frames, same stages)" % bad)
 
     # ---- the same workload with ONE batch in flight, and one pass alone for the per-stage durations in isolation ----
     value_d1 = ms_d1 = iso_ms = d1_minmax = b2b_ms = None
-    if not args.no_depth1 or not args.no_stage_timing:
+    if depth1 or stage_timing:
         pipe1 = smh.Pipeline(vision, W, H, n, 1)
-        if not args.no_depth1:
+        if depth1:
             k1 = max(2, args.steps // 2)
             for _ in range(2):
                 step(pipe1)
@@ -1100,7 +1184,7 @@ def main():
             d1_minmax = [min(rates1), max(rates1)]
             ms_d1 = frames_per_step / value_d1 * 1e3
             assert bytes(pipe1.slots[0].read_results(0, n)) == slot_bytes[0], "the depth-1 pipeline's records differ from the depth-%d pipeline's" % depth
-        if not args.no_stage_timing:
+        if stage_timing:
             # one pass that runs ALONE and whole (a plain smhv_batch_run: the depth-1 pipeline cuts its submissions into
             # chunks, whose launches overlap) for the per-stage durations in isolation
             fb_iso = smh.FrameBatch(vision, W, H, n)
@@ -1142,19 +1226,20 @@ def main():
 
     # ---- result sanity + workload statistics (outside the timed region) ----
     fb = pipe.slots[0]
-    recs = smh.results_to_dicts(fb.read_results(0, n))
-    rounds_pf = float(np.mean([r["rounds"] for r in recs]))
-    ray_steps = float(np.mean([r["ray_steps"] for r in recs]))
-    n_lines = float(np.mean([r["n_lines"] for r in recs]))
-    all_open = all(r["map_open"] for r in recs)
     gather_ok = None
-    if gather is not None and rank == 0:
-        last_slot = (args.warmup * rounds + args.steps * rounds - 1) % depth
-        got = gather.records(last_slot)
-        assert len(got) == n * world, "gather returned %d records, expected %d" % (len(got), n * world)
-        sz = sdist.RECORD_BYTES
-        gather_ok = bytes(got)[:n * sz] == slot_bytes[0]
-        assert gather_ok, "rank 0's own block of the gather differs from its records"
+    if args.full:
+        recs = smh.results_to_dicts(fb.read_results(0, n))
+        rounds_pf = float(np.mean([r["rounds"] for r in recs]))
+        ray_steps = float(np.mean([r["ray_steps"] for r in recs]))
+        n_lines = float(np.mean([r["n_lines"] for r in recs]))
+        all_open = all(r["map_open"] for r in recs)
+        if gather is not None and rank == 0:
+            last_slot = (args.warmup * rounds + args.steps * rounds - 1) % depth
+            got = gather.records(last_slot)
+            assert len(got) == n * world, "gather returned %d records, expected %d" % (len(got), n * world)
+            sz = sdist.RECORD_BYTES
+            gather_ok = bytes(got)[:n * sz] == slot_bytes[0]
+            assert gather_ok, "rank 0's own block of the gather differs from its records"
 
     if world > 1:
         # every rank empties its C stdio buffer (RCCL's banner) NOW, so that nothing of the other ranks can land behind
@@ -1197,13 +1282,16 @@ def main():
         "timed_seconds": dt_total,
         "ms_per_pass": frames_per_step / value * 1e3 / rounds,
         "per_gpu_frames_per_s": value / world,
-        "value_depth1": value_d1, "value_depth1_min_max": d1_minmax, "ms_per_pass_depth1": (ms_d1 / rounds if ms_d1 is not None else None),
         "h2d_seconds_for_batch": h2d_s,
         "search_service": svc_stats,
-        "device_during_timed_region": (watch.summary() if watch is not None else None),
-        "all_map_open": bool(all_open),
-        "slots_identical": bool(slots_identical), "slots_compared": used,
     }
+    if args.full:
+        out.update({
+            "value_depth1": value_d1, "value_depth1_min_max": d1_minmax, "ms_per_pass_depth1": (ms_d1 / rounds if ms_d1 is not None else None),
+            "device_during_timed_region": (watch.summary() if watch is not None else None),
+            "all_map_open": bool(all_open),
+            "slots_identical": bool(slots_identical), "slots_compared": used,
+        })
     if gather_ok is not None:
         out["gather_matches_rank0_records"] = bool(gather_ok)
     if stages_ms is not None:
@@ -1339,17 +1427,17 @@ def main():
                       "ray_steps_per_s": (n * ray_steps / t_lsd) if t_lsd > 0 else None,
                       "time_share": stages_ms["lsd"] / max(sum(stages_ms.values()), 1e-9)}
 
-    if args.ingest_frames > 0 and world == 1 and args.config == 2 and not custom:
+    if args.full and args.ingest_frames > 0 and world == 1 and args.config == 2 and not custom:
         out["ingest"] = ingest_leg(smh, torch, vision, pipe, frames_host, anchors, stages, args.ingest_frames, W, H, n, affinity=args.ingest_affinity == "on")
     pipe.close()                                           # (its streams hold hardware queues the next leg's pipelines should get)
-    if world == 1 and args.config == 2 and not custom and len(frames_host):
+    if args.full and world == 1 and args.config == 2 and not custom and len(frames_host):
         out["trait_path"] = trait_path_leg(smh, vision, frames_host[0], infos[0]["anchors"])
-    if args.side_probe > 0 and world == 1 and args.config == 2 and not custom and depth >= 3:
+    if args.full and args.side_probe > 0 and world == 1 and args.config == 2 and not custom and depth >= 3:
         out["co_residency"] = co_residency_leg(smh, torch, vision, W, H, n, depth, fptr, anchors, stages, args.side_probe, rccl_probe=args.gather_probe)
-    if not args.no_real_samples and world == 1 and args.config == 2 and not custom:
+    if args.full and not args.no_real_samples and world == 1 and args.config == 2 and not custom:
         out["real_samples"] = real_samples_leg(smh, torch, vision, depth)
 
-    if args.cpu_sample > 0 and world == 1:
+    if args.full and args.cpu_sample > 0 and world == 1:
         from oracle import oracle as orc   # CPU baseline leg only (checker, never the product path)
         k = min(args.cpu_sample, n, len(frames_host)) if n > 1 else min(args.cpu_sample, 16)
         if n == 1:                                         # config 1: more frames of the same kind for a stable figure

@@ -1039,7 +1039,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo(vision):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--frames-per-gpu", "16", "--rounds-per-step", "2",
-           "--dist-backend", "gloo", "--force-device", "0", "--cpu-sample", "0", "--ingest-frames", "0"]
+           "--dist-backend", "gloo", "--force-device", "0", "--cpu-sample", "0", "--ingest-frames", "0", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
@@ -1067,6 +1067,54 @@ def test_bench_node_leg_and_config0(vision):
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["cases"][0]["size"] == [2560, 1440] and out["cases"][0]["gpu_lines_equal_cpu"] and out["cases"][1]["gpu_lines_equal_cpu"]
     assert set(out["cases"][0]["cpu_single_thread_stage_ms"]) == {"crop_to_map", "threshold_dilate", "lsd", "ocr_preprocess", "find_scales_preprocess"}
+
+
+def test_bench_plain_run_dumps_what_the_pipeline_computes(vision, tmp_path):
+    """A plain `bench.py --steps K --warmup W` times the headline only (no leg of --full in its line) and --dump-outputs writes
+    the last timed pass's outputs: the records of every frame and the images of the sampled frames equal a plain smhv_batch_run
+    of the same synthetic frames."""
+    import json
+    import subprocess
+    import sys
+    import torch
+    import squad_mortar_helper_amd as smh
+    from squad_mortar_helper_amd import synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    W, H, N = 1920, 1080, 16
+    d_out = str(tmp_path / "out")
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--frames-per-gpu", str(N),
+                        "--rounds-per-step", "2", "--dump-outputs", d_out], env=env, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["value"] > 0 and out["higher_is_better"] is True and out["unit"] == "frames/s"
+    assert out["ms_per_step"] > 0 and abs(out["ms_per_step"] - out["timed_seconds"] * 1e3 / 3) <= 1e-6 * out["ms_per_step"] + 1e-9
+    assert not {"roofline", "stages_ms", "cpu_baseline", "value_depth1", "slots_identical", "real_samples"} & set(out)
+    got = {f[:-4]: np.load(os.path.join(d_out, f)) for f in os.listdir(d_out)}
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in got.values()) and sum(v.nbytes for v in got.values()) <= 64 * 10 ** 6
+    frames, infos = synth.make_batch(W, H, N, first_idx=0)                 # the bench's frames: rank 0, every frame distinct
+    anchors = smh.make_anchors([(i["scales_start_y"], i["anchors"]) for i in infos])
+    d = torch.from_numpy(frames).cuda()
+    fb = smh.FrameBatch(vision, W, H, N)
+    fb.run(d.data_ptr(), N, anchors=anchors, stream=torch.cuda.current_stream().cuda_stream)
+    recs = smh.results_to_dicts(fb.read_results(0, N))
+    assert got["lines"].shape == (N, 32, 4) and got["n_lines"].shape == (N,)
+    for i, r in enumerate(recs):
+        k = r["n_lines"]
+        assert got["n_lines"][i] == k and np.array_equal(got["lines"][i, :k], r["lines"]) and not got["lines"][i, k:].any(), i
+        assert (got["map_open"][i], got["rounds"][i], got["n_mask_px"][i]) == (r["map_open"], r["rounds"], r["n_mask_px"]), i
+        assert got["has_mpx"][i] == (r["mpx"] is not None) and got["mpx"][i] == (0.0 if r["mpx"] is None else r["mpx"]), i
+        assert got["has_minimap"][i] == (r["minimap"] is not None) and list(got["minimap"][i]) == list(r["minimap"] or (0, 0, 0, 0)), i
+    L = smh._lib
+    sample = got["image_frames"].astype(int)
+    assert len(sample) >= 1 and len(set(sample)) == len(sample) and sample.max() < N
+    for j, f in enumerate(sample):
+        assert np.array_equal(got["ui_map"][j], fb.read_image(L.IMAGE_UI_MAP, f).astype(np.float32)), f
+        assert np.array_equal(got["marker_mask"][j], fb.read_image(L.VIEW_LSD_INPUT, f).astype(np.float32)), f
+        assert np.array_equal(got["ocr"][j], fb.read_image(L.VIEW_OCR_INPUT, f).astype(np.float32)), f
+        y0 = infos[f]["scales_start_y"]
+        assert np.array_equal(got["scales"][j][y0:], fb.read_image(L.VIEW_FIND_SCALES_INPUT, f)[y0:].astype(np.float32)) and not got["scales"][j][:y0].any(), f
+    fb.close()
 
 
 def test_node_entry_points_on_one_gpu(vision):

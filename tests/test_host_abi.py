@@ -86,7 +86,7 @@ def test_record_layout_matches_header(built):
     assert "#define SMHV_FRAME_OK 0u" in hdr and "#define SMHV_FRAME_LSD_STUCK 1u" in hdr and "uint32_t status;" in hdr
 
 
-def test_pipeline_options_and_flags_match_the_header(built):
+def test_pipeline_options_and_flags_match_the_header(built, tmp_path):
     """smhv_pipeline_options as the binding declares it == the struct in the header, field for field (all uint32_t, in order),
     and the SMHV_SEARCH_* / SMHV_PIPE_* / SMHV_INGEST_* values the binding uses are the header's.  A C program compiled against
     the header agrees on the size."""
@@ -106,7 +106,7 @@ def test_pipeline_options_and_flags_match_the_header(built):
         ["SMHV_PIPE_HELP_FIRST", "SMHV_PIPE_NO_PROLOGUE", "SMHV_PIPE_NO_REMOTE_HELP", "SMHV_PIPE_NO_STREAM_PRIORITY", "SMHV_PIPE_NO_TEAM_HELP", "SMHV_PIPE_THREE_LOAD_SETS",
          "SMHV_PIPE_WALK_BIT_ROWS"]
     assert (int(defs["SMHV_PIPE_WALK_BIT_ROWS"]), int(defs["SMHV_PIPE_THREE_LOAD_SETS"])) == (_lib.PIPE_WALK_BIT_ROWS, _lib.PIPE_THREE_LOAD_SETS)
-    src = os.path.join(os.environ.get("TMPDIR", "/tmp"), "smhv_opt_size.c")
+    src = str(tmp_path / "smhv_opt_size.c")
     exe = src[:-2]
     with open(src, "w") as f:
         f.write('#include <stdio.h>\n#include "smh_vision_hip.h"\nint main(void) { printf("%zu\\n", sizeof(smhv_pipeline_options)); return 0; }\n')
@@ -239,6 +239,61 @@ def test_bench_launches_its_own_ranks(built):
     # under a launcher whose world does not match --gpus: refuse
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--rendezvous-only"], env=dict(env, WORLD_SIZE="1", RANK="0"), capture_output=True, text=True, timeout=300)
     assert p.returncode == 2
+
+
+def test_bench_dump_outputs_layout_and_budget(built, tmp_path):
+    """bench.py --dump-outputs (dump_outputs, fed here with hand-made records and a stand-in for the slot's images): float32 /
+    float64 files only, every value finite, entries past n_lines zeroed, an absent mpx / minimap 0 with its has_ flag 0, the scales image's undefined rows zeroed, the
+    same files from the same inputs, and never more than 64 MB -- for frames too large for one image sample, a seeded sample of rows."""
+    import bench
+    import squad_mortar_helper_amd as smh
+    L = smh._lib
+
+    class Slot:
+        def __init__(self, w, h):
+            self.roi = (0, 0, w, h)
+
+        def read_image(self, which, frame):
+            w, h = self.roi[2], self.roi[3]
+            shape = {L.IMAGE_UI_MAP: (h, w, 4), L.VIEW_LSD_INPUT: (h, w)}.get(which, (h // 2, w // 2))
+            return ((np.arange(int(np.prod(shape)), dtype=np.uint64) * (which + 3) + frame) % 251).astype(np.uint8).reshape(shape)
+
+    n = 6
+    recs = (L.FrameResult * n)()
+    for i in range(n):
+        recs[i].n_lines, recs[i].map_open, recs[i].rounds = i % 3, 1, 10 + i
+        for j in range(L.MAX_LINES):                               # garbage past n_lines must not reach the files
+            recs[i].lines[j].x0, recs[i].length_px[j], recs[i].angle[j] = 1.0 + j, 2.0 + j, 3.0 + j
+    recs[1].has_mpx, recs[1].mpx = 1, 0.75
+    recs[2].has_minimap = 1
+    recs[2].minimap[:] = [1, 2, 3, 4]
+    start = [5 + i for i in range(n)]
+
+    def run(d, w, h):
+        nb = bench.dump_outputs(smh, np, str(d), recs, Slot(w, h), 0xF, start)
+        got = {f[:-4]: np.load(os.path.join(str(d), f)) for f in os.listdir(str(d))}
+        assert nb == sum(v.nbytes for v in got.values()) <= bench.DUMP_BYTES
+        assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in got.values())
+        return got
+
+    a = run(tmp_path / "a", 986, 822)                            # a 1080p frame's map ROI: whole images of a few frames
+    b = run(tmp_path / "b", 986, 822)
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert a["lines"].shape == (n, L.MAX_LINES, 4) and a["lines"].dtype == np.float32
+    for i in range(n):
+        k = i % 3
+        assert a["n_lines"][i] == k and np.all(a["lines"][i, :k, 0] == 1.0 + np.arange(k)) and not a["lines"][i, k:].any()
+        assert not a["length_px"][i, k:].any() and not a["angle"][i, k:].any()
+    assert a["mpx"][1] == 0.75 and a["has_mpx"][1] == 1 and a["mpx"][0] == 0 and a["has_mpx"][0] == 0
+    assert list(a["minimap"][2]) == [1, 2, 3, 4] and a["has_minimap"][2] == 1 and not a["minimap"][0].any() and a["has_minimap"][0] == 0
+    frames = a["image_frames"].astype(int)
+    assert 1 <= len(frames) <= 4 and len(set(frames)) == len(frames) and "ui_map_rows" not in a
+    for j, f in enumerate(frames):
+        assert a["ui_map"].shape[1:] == (822, 986, 4) and np.array_equal(a["ui_map"][j], Slot(986, 822).read_image(L.IMAGE_UI_MAP, f))
+        sc = Slot(986, 822).read_image(L.VIEW_FIND_SCALES_INPUT, f)
+        assert not a["scales"][j][:start[f]].any() and np.array_equal(a["scales"][j][start[f]:], sc[start[f]:])
+    c = run(tmp_path / "c", 3000, 2600)                          # one frame's images alone exceed the budget
+    assert len(c["image_frames"]) == 1 and 0 < len(c["ui_map_rows"]) < 2600 and c["ui_map"].shape[1:] == (len(c["ui_map_rows"]), 3000, 4)
 
 
 def test_parse_ocr_labels_follows_the_reference_filter(built):

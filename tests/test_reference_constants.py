@@ -1,23 +1,27 @@
 """The only numbers the reference itself holds for this path are its constants: the tunables of
 vision-common/src/consts/consts.toml:1-63, the two screen-relative rectangles of vision-common/src/consts/mod.rs:7-19, the luma
-weights its CUDA side hard-codes (vision-gpu/cuda/cuda.cu:23-25), and a handful of literals in lsd.rs / mpx_ratio.rs.  This test
-parses those files where they lie (build container only: /root/reference is not on the GPU box, and nothing of it is copied
-into the repo) and checks that csrc/smh_consts.h (what the HIP kernels and the host runtime are built from) and
-oracle/smh_oracle.c (the checker) carry exactly those values.  It does not lift parity above "unpinned by the reference" --
-the reference has no golden vectors -- but it makes the reference-held numbers machine-checked instead of eyeballed."""
+weights its CUDA side hard-codes (vision-gpu/cuda/cuda.cu:23-25), and a handful of literals in lsd.rs / mpx_ratio.rs.  Those
+values, as they are written in the reference's files, are recorded in tests/golden/reference_constants.json (data only: names,
+numbers and the literal text of each number; nothing of the reference's code is copied into the repo).  This test checks that
+csrc/smh_consts.h (what the HIP kernels and the host runtime are built from) and oracle/smh_oracle.c (the checker) carry exactly
+those values.  It does not lift parity above "unpinned by the reference" -- the reference has no golden vectors -- but it makes
+the reference-held numbers machine-checked instead of eyeballed.
+
+Regenerate the fixture from a checkout of the reference:  python tests/test_reference_constants.py <reference dir>"""
+import json
 import os
 import re
-
-import pytest
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "vision-common")), reason="the reference tree is only present in the build container")
+FIXTURE = os.path.join(ROOT, "tests", "golden", "reference_constants.json")
 
 
-def _toml_consts():
+# ---- extraction from the reference's own files (fixture generation only) ----
+
+def _toml_consts(ref):
     """[NAME] / type = ".." / value = <scalar | [a, b, c]> blocks (the whole grammar toml-consts accepts here)."""
-    text = open(os.path.join(REF, "vision-common", "src", "consts", "consts.toml")).read()
+    text = open(os.path.join(ref, "vision-common", "src", "consts", "consts.toml")).read()
     out = {}
     for name, body in re.findall(r"^\[([A-Z0-9_]+)\]\s*\n((?:[^\[\n].*\n?)*)", text, re.M):
         ty = re.search(r'type\s*=\s*"(\w+)"', body).group(1)
@@ -25,6 +29,47 @@ def _toml_consts():
         conv = float if ty.startswith("f") else int
         out[name] = [conv(v) for v in raw.strip("[]").split(",")] if raw.startswith("[") else conv(raw)
     return out
+
+
+def _rust_bounds(ref):
+    text = open(os.path.join(ref, "vision-common", "src", "consts", "mod.rs")).read()
+    out = {}
+    for name, body in re.findall(r"pub const (\w+): RelativeBounds2D = RelativeBounds2D \{(.*?)\};", text, re.S):
+        fields = {}
+        for f, corner, frac in re.findall(r"(\w):\s*(?:(Left|Right|Top|Bottom)\()?ScreenH\(([0-9.]+)\)\)?", body):
+            fields[f] = [corner, frac]
+        out[name] = fields
+    return out
+
+
+def _literals(ref):
+    """Literal text of the numbers the line search and the scale scan hard-code."""
+    cu = open(os.path.join(ref, "vision-gpu", "cuda", "cuda.cu")).read()
+    lsd = open(os.path.join(ref, "vision-common", "src", "lsd.rs")).read()
+    cpu = open(os.path.join(ref, "vision-cpu", "src", "lib.rs")).read()
+    mpx = open(os.path.join(ref, "src", "vision", "mpx_ratio.rs")).read()
+    lib = open(os.path.join(ref, "vision-common", "src", "lib.rs")).read()
+    return {
+        "luma": dict(re.findall(r"#define LUMA_([RGB]) ([0-9.]+)f", cu)),                                  # vision-gpu/cuda/cuda.cu:23-25
+        "lsd_accept_len_sq": re.search(r"if max_length > ([0-9.]+)", lsd).group(1),                        # lsd.rs:94
+        "lsd_proximity_sq": re.search(r"\.powi\(2\) < ([0-9.]+)", lsd).group(1),                            # lsd.rs:86
+        "lsd_centre_reach": re.search(r"const MAX_DIST: f32 = ([0-9.]+);", lsd).group(1),                  # lsd.rs:9
+        "lsd_rays": re.search(r"\(0\.\.(\d+)_u32\)", cpu[cpu.index("fn find_longest_line"):]).group(1),     # vision-cpu/src/lib.rs:434
+        "lsd_max_lines": re.search(r"SmallVec<Line<f32>, (\d+)>", lib).group(1),                           # vision-common/src/lib.rs
+        "min_scale_width": re.search(r"MIN_SCALE_WIDTH: u32 = (\d+)", mpx).group(1),                       # src/vision/mpx_ratio.rs
+        "min_scale_vertical_bar_height": re.search(r"MIN_SCALE_VERTICAL_BAR_HEIGHT: u32 = (\d+)", mpx).group(1),
+    }
+
+
+def extract(ref):
+    return {"consts_toml": _toml_consts(ref), "bounds": _rust_bounds(ref), "literals": _literals(ref)}
+
+
+# ---- the checks, against the recorded values ----
+
+def _fixture():
+    with open(FIXTURE) as f:
+        return json.load(f)
 
 
 def _defines(path):
@@ -39,19 +84,8 @@ def _num(text):
     return float(text) if "." in text else int(text)
 
 
-def _rust_bounds():
-    text = open(os.path.join(REF, "vision-common", "src", "consts", "mod.rs")).read()
-    out = {}
-    for name, body in re.findall(r"pub const (\w+): RelativeBounds2D = RelativeBounds2D \{(.*?)\};", text, re.S):
-        fields = {}
-        for f, corner, frac in re.findall(r"(\w):\s*(?:(Left|Right|Top|Bottom)\()?ScreenH\(([0-9.]+)\)\)?", body):
-            fields[f] = (corner, frac)
-        out[name] = fields
-    return out
-
-
 def test_consts_toml_equals_the_header_and_the_oracle():
-    toml = _toml_consts()
+    toml = _fixture()["consts_toml"]
     hdr = _defines(os.path.join(ROOT, "squad-mortar-helper_amd", "csrc", "smh_consts.h"))
     orc_text = open(os.path.join(ROOT, "oracle", "smh_oracle.c")).read()
     orc = _defines(os.path.join(ROOT, "oracle", "smh_oracle.c"))
@@ -86,7 +120,7 @@ def test_consts_toml_equals_the_header_and_the_oracle():
 
 
 def test_screen_relative_bounds_equal_consts_mod_rs():
-    rb = _rust_bounds()
+    rb = _fixture()["bounds"]
     hdr = _defines(os.path.join(ROOT, "squad-mortar-helper_amd", "csrc", "smh_consts.h"))
     orc_text = open(os.path.join(ROOT, "oracle", "smh_oracle.c")).read()
     mb, bb = rb["MAP_BOUNDS"], rb["CLOSE_DEPLOYMENT_BUTTON_BOUNDS"]
@@ -100,28 +134,29 @@ def test_screen_relative_bounds_equal_consts_mod_rs():
 
 
 def test_luma_weights_and_lsd_literals():
+    lit = _fixture()["literals"]
     hdr = _defines(os.path.join(ROOT, "squad-mortar-helper_amd", "csrc", "smh_consts.h"))
     orc_text = open(os.path.join(ROOT, "oracle", "smh_oracle.c")).read()
-    cu = open(os.path.join(REF, "vision-gpu", "cuda", "cuda.cu")).read()
-    luma = dict(re.findall(r"#define LUMA_([RGB]) ([0-9.]+)f", cu))
+    luma = lit["luma"]
     assert sorted(luma) == ["B", "G", "R"]
     for c in "RGB":
         assert hdr["SMH_LUMA_" + c] == luma[c]
     assert re.search(r"%sf \* \(float\)r \+ %sf \* \(float\)g \+ %sf \* \(float\)b" % (luma["R"], luma["G"], luma["B"]), orc_text)
 
-    lsd = open(os.path.join(REF, "vision-common", "src", "lsd.rs")).read()
-    cpu = open(os.path.join(REF, "vision-cpu", "src", "lib.rs")).read()
-    mpx = open(os.path.join(REF, "src", "vision", "mpx_ratio.rs")).read()
-    lib = open(os.path.join(REF, "vision-common", "src", "lib.rs")).read()
-    accept = re.search(r"if max_length > ([0-9.]+)", lsd).group(1)               # lsd.rs:94
-    prox = re.search(r"\.powi\(2\) < ([0-9.]+)", lsd).group(1)                     # lsd.rs:86
-    reach = re.search(r"const MAX_DIST: f32 = ([0-9.]+);", lsd).group(1)          # lsd.rs:9
-    rays = re.search(r"\(0\.\.(\d+)_u32\)", cpu[cpu.index("fn find_longest_line"):]).group(1)   # vision-cpu/src/lib.rs:434
-    nmax = re.search(r"SmallVec<Line<f32>, (\d+)>", lib).group(1)
+    accept, prox, reach, rays = lit["lsd_accept_len_sq"], lit["lsd_proximity_sq"], lit["lsd_centre_reach"], lit["lsd_rays"]
     assert float(hdr["SMH_LSD_ACCEPT_LEN_SQ"]) == float(accept) and ("max_length > %sf" % accept) in orc_text
     assert float(hdr["SMH_LSD_PROXIMITY_SQ"]) == float(prox) and ("< %sf" % prox) in orc_text
     assert float(hdr["SMH_LSD_CENTRE_REACH"]) == float(reach)
     assert int(hdr["SMH_LSD_RAYS"]) == int(rays) and ("i < %s;" % rays) in orc_text
-    assert int(hdr["SMH_LSD_MAX_LINES"]) == int(nmax)
-    assert int(hdr["SMH_MIN_SCALE_WIDTH"]) == int(re.search(r"MIN_SCALE_WIDTH: u32 = (\d+)", mpx).group(1))
-    assert int(hdr["SMH_MIN_SCALE_VERTICAL_BAR_HEIGHT"]) == int(re.search(r"MIN_SCALE_VERTICAL_BAR_HEIGHT: u32 = (\d+)", mpx).group(1))
+    assert int(hdr["SMH_LSD_MAX_LINES"]) == int(lit["lsd_max_lines"])
+    assert int(hdr["SMH_MIN_SCALE_WIDTH"]) == int(lit["min_scale_width"])
+    assert int(hdr["SMH_MIN_SCALE_VERTICAL_BAR_HEIGHT"]) == int(lit["min_scale_vertical_bar_height"])
+
+
+if __name__ == "__main__":
+    if len(sys.argv) != 2 or not os.path.isdir(os.path.join(sys.argv[1], "vision-common")):
+        raise SystemExit("usage: python tests/test_reference_constants.py <reference dir>")
+    with open(FIXTURE, "w") as f:
+        json.dump(extract(sys.argv[1]), f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("wrote", os.path.relpath(FIXTURE, ROOT))

@@ -12,7 +12,7 @@ R=$(pwd)
 OUT=$R/gpurun_out
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --cpu-sample 0 --ingest-frames 0 --no-depth1 --no-back-to-back --no-real-samples --side-probe 0"   # profiled runs: only warm-up, timed and isolated passes
+B="python3 $R/bench.py --full --cpu-sample 0 --ingest-frames 0 --no-depth1 --no-back-to-back --no-real-samples --side-probe 0"   # profiled runs: only warm-up, timed and isolated passes
 for C in 2 3; do
   P=""; [ $C = 3 ] && P="c3_"
   for D in 1 4 12 16; do
@@ -29,5 +29,6 @@ cd $R
 python tools/pmc_summary.py "$TAG" c2
 python tools/pmc_summary.py "$TAG" c3
 cp $OUT/traffic.json profiles/traffic.json 2>/dev/null
-for C in 1 2 3; do timeout 600 python bench.py --config $C 2>/dev/null | tail -1 > $OUT/${TAG}_bench_config$C.json; done
-timeout 600 python bench.py --pipeline-depth 1 --cpu-sample 0 --ingest-frames 0 2>/dev/null | tail -1 > $OUT/${TAG}_bench_depth1.json
+for C in 1 2 3; do timeout 600 python bench.py --full --config $C 2>/dev/null | tail -1 > $OUT/${TAG}_bench_config$C.json; done
+timeout 600 python bench.py --full --pipeline-depth 1 --cpu-sample 0 --ingest-frames 0 2>/dev/null | tail -1 > $OUT/${TAG}_bench_depth1.json
+for C in 0 4; do timeout 900 python bench.py --full --config $C 2>/dev/null | tail -1 > $OUT/${TAG}_bench_config$C.json; done
