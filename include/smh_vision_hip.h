@@ -435,6 +435,83 @@ SMHV_API uint32_t smhv_crc32_host(const void *data, uint64_t nbytes);
 /* CRC-32/IEEE of nbytes (multiple of 4) of device memory; == crc32fast::hash / zlib crc32 of the same bytes */
 SMHV_API int smhv_crc32_device(smhv_ctx *ctx, const void *d_data, uint64_t nbytes, uint32_t *crc);
 
+/* ---- firing solutions: range, altitude difference, mils and bearings of every marker line -----------------------------
+ * The numbers the app draws beside a marker (src/ui/markers.rs:23-200): the range from the heightmap and the minimap rectangle
+ * when a heightmap is bound (markers.rs:37-91), else from the map scales (the record's meters); the altitude difference between
+ * the two ends (Heightmap::height, heightmap-ripper/src/lib.rs:22-25); the elevation in milliradians for each direction
+ * (src/squadex/milliradians.rs) and the bearing for each direction (markers.rs:98-110).  Per line (p0, p1) in map-ROI
+ * coordinates, with Rust's f32 / f64 semantics:
+ *   P = (x * sw + tx, y * sh + ty) in f32 (the viewport, src/ui/map.rs:80-101; default sw = sh = 1, tx = ty = 0).
+ *   Heightmap branch (the frame has a minimap rectangle and a heightmap is bound): offset = (0, 0) ("fit to minimap", the app's
+ *   default), or with SMHV_FIRING_BOUNDS_OFFSET  off.x = b0.x * ((right - left) as f32 / (W as f32 + b0.x)) * sw, the same in y
+ *   (b0 = bounds[0] as f32, right - left in u32).  R = {left*sw+tx + off.x, top*sh+ty + off.y, right*sw+tx, bottom*sh+ty} in f32;
+ *   p_x = ((P.x as f64 - R.left as f64) / (R.right - R.left) as f64) * W, the same in y; range = sqrt(dx*dx + dy*dy) in f64.  The
+ *   four coordinates are rounded half away from zero and cast `as i32` (saturating, NaN -> 0): if all lie inside [0,W) x [0,H),
+ *   alt_delta = height(p1) - height(p0) with height = (v as f64 / 65535.0) * (scale[2] as f64 / 0.1953125); otherwise the
+ *   heightmap gives no range.
+ *   Range: the heightmap's, else the record's meters when the frame has m/px, else none (source says which).
+ *   Bearings: angle = atan2f(P0.y - P1.y, P0.x - P1.x), d = angle * 57.29578 (f32 to_degrees); d > 0 ? (d -= 90, d < 0 ? d += 360)
+ *   : d += 270; fwd = roundf(d) fmod 360, bck = roundf(fwd + 180) fmod 360 (roundf: half away from zero).
+ *   Mils: calc(m, a) = atan((V^2 + sqrt(V^4 - g(g m m + 2 a V^2))) / (g m)) * (180 / pi) / (360 / 6400) in f64, g = 9.8,
+ *   V = 109.890938; NaN = out of range (the app's "RANGE!").
+ * Directions: [0] = firing from p0 at p1 (alt_delta = height(p1) - height(p0), mils[0] = calc(range, alt_delta), bearing[0] =
+ * fwd); [1] = the reverse (mils[1] = calc(range, -alt_delta), bearing[1] = bck).  Without alt_delta both mils are calc(range, 0).
+ * What the app prints where (markers.rs:131, :202), angle as above:
+ *   with alt_delta (source HEIGHTMAP): the text left of the midpoint ("<- ... mil") is direction 0 when -pi/2 <= angle < pi/2 and
+ *     direction 1 otherwise; the text right of it ("... mil ->") is the other direction.
+ *   without (source SCALES): one block; when -pi/2 <= angle <= pi/2 its lines read "-> bearing[1]" then "<- bearing[0]", otherwise
+ *     "-> bearing[0]" then "<- bearing[1]".
+ *   source NONE: the app draws the line only (the bearings are filled all the same; meters, alt_delta and mils are 0). */
+typedef struct smhv_heightmap smhv_heightmap;
+#define SMHV_STAGE_FIRING 0x80u          /* smhv_batch_run / smhv_pipeline_submit: write the firing slab (needs SMHV_STAGE_MARKERS; the
+                                            heightmap branch needs SMHV_STAGE_MINIMAP in the same run -- without it every line takes
+                                            the scales branch, as the reference does without minimap bounds).  Not in SMHV_STAGE_ALL. */
+#define SMHV_FIRING_BOUNDS_OFFSET 1u     /* smhv_firing_options.flags: the app's "fit to minimap" switched off (bounds[0] offsets the map) */
+#define SMHV_FIRING_NONE 0u              /* smhv_firing.source */
+#define SMHV_FIRING_SCALES 1u
+#define SMHV_FIRING_HEIGHTMAP 2u
+typedef struct {
+	uint32_t size;                       /* sizeof(smhv_firing_options) */
+	uint32_t flags;                      /* SMHV_FIRING_* */
+	float viewport_scale[2];             /* MapViewport::scale_factor_{w,h}; 0 = 1 */
+	float viewport_top_left[2];          /* MapViewport::top_left */
+} smhv_firing_options;
+typedef struct {
+	double meters;                       /* range (0 when source is NONE)                                   */
+	double alt_delta;                    /* height(p1) - height(p0) (source HEIGHTMAP; 0 otherwise)          */
+	double mils[2];                      /* [0] from p0 at p1, [1] from p1 at p0; NaN = out of range          */
+	float bearing[2];                    /* degrees, [0] = fwd, [1] = bck                                     */
+	uint32_t source;                     /* SMHV_FIRING_NONE / _SCALES / _HEIGHTMAP                          */
+	uint32_t reserved;
+} smhv_firing;
+typedef struct {
+	uint32_t n_lines, reserved;          /* == the record's n_lines; lines beyond it are zero                 */
+	smhv_firing line[SMHV_MAX_LINES];
+} smhv_firing_result;
+/* A device copy of a heightmap (Heightmap, heightmap-ripper/src/lib.rs:7-14): w x h u16 texels, row-major; bounds = {b00, b01,
+ * b10, b11}; scale = {x, y, z}.  SMHV_E_INVALID for a zero dimension or w*h > 2^28.  smhv_heightmap_destroy drops the caller's
+ * reference: a batch or pipeline that has it bound keeps its own until it is rebound or destroyed, and the device memory goes
+ * with the last reference once the device has finished everything enqueued before (that release synchronises the device). */
+SMHV_API int smhv_heightmap_create(smhv_ctx *ctx, const uint16_t *data, uint32_t w, uint32_t h, const int32_t bounds[4], const float scale[3],
+                                   smhv_heightmap **out);
+SMHV_API void smhv_heightmap_destroy(smhv_heightmap *hm);
+/* color_map_heightmap (src/ui/heightmaps.rs:169-207): w*h*4 bytes of RGBA into host memory, byte-exact (a min/max pass, then the
+ * per-texel colour in f64) */
+SMHV_API int smhv_heightmap_color_map(smhv_heightmap *hm, uint8_t *rgba);
+/* Bind a heightmap (NULL = none) and options (NULL = defaults) for SMHV_STAGE_FIRING.  A batch's binding applies to its next
+ * smhv_batch_run; a pipeline's to submissions made after the call (submissions in flight keep what they were submitted with). */
+SMHV_API int smhv_batch_set_firing(smhv_batch *b, smhv_heightmap *hm, const smhv_firing_options *opt);
+SMHV_API int smhv_pipeline_set_firing(smhv_pipeline *p, smhv_heightmap *hm, const smhv_firing_options *opt);
+/* The batch's firing slab: one smhv_firing_result per frame, written by runs with SMHV_STAGE_FIRING (allocated by the first
+ * such run).  read: synchronising host copy; ptr: device address (SMHV_E_STATE before the first such run). */
+SMHV_API int smhv_batch_read_firing(smhv_batch *b, uint32_t first, uint32_t n, smhv_firing_result *out);
+SMHV_API int smhv_batch_firing_ptr(smhv_batch *b, void **d_firing);
+/* The same device function for explicit lines (markers::draw of detected and custom markers): n lines in map-ROI coordinates,
+ * mpx = the frame's meters per pixel (NULL: none), minimap = {left, right, top, bottom} (NULL: none), hm (NULL: none), opt (NULL:
+ * defaults).  Runs on the context's stream and returns the n results. */
+SMHV_API int smhv_firing_solutions(smhv_ctx *ctx, const smhv_line *lines, uint32_t n, const double *mpx, const uint32_t minimap[4],
+                                   const smhv_heightmap *hm, const smhv_firing_options *opt, smhv_firing *out);
+
 #ifdef __cplusplus
 }
 #endif

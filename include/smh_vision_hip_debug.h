@@ -32,6 +32,9 @@ SMHV_API int smhv_debug_lsd_threads(uint32_t threads);
  * a thread issues before it stores (0 = 4, 4, 8, 12; the pass itself: 12).  Its rate is what the memory system gives this
  * access pattern; bench.py reports the best variant beside the pass (roofline_isolated.pattern_copy_GBps). */
 SMHV_API int smhv_debug_pattern_copy(smhv_batch *b, const void *d_frames, uint32_t n, uint32_t rows_in_flight, void *stream);
+/* calibration: smhv_heightmap_color_map's two passes into d_rgba (w*h*4 bytes of device memory) on the context's stream; *ms = their
+ * device time (hipEvents around both; synchronises).  tools/firing_cost.py reports the rate this gives against the HBM peak. */
+SMHV_API int smhv_debug_heightmap_color_map_device(smhv_heightmap *hm, void *d_rgba, float *ms);
 /* diagnostic (process-wide): batched runs launch everything but the line search, so that the streaming
  * pass can be timed back to back with itself (bench.py, roofline_isolated.back_to_back).  The records of such a run hold no
  * valid lines. */

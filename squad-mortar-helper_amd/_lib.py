@@ -17,6 +17,9 @@ STAGE_MARKERS, STAGE_UI_MAP, STAGE_OCR, STAGE_SCALES, STAGE_ALL = 0x1, 0x2, 0x4,
 STAGE_MINIMAP = 0x10
 STAGE_EXACT_STATS = 0x20
 STAGE_LSD_HELPERS = 0x40
+STAGE_FIRING = 0x80                        # firing solutions (needs STAGE_MARKERS; the heightmap branch needs STAGE_MINIMAP)
+FIRING_BOUNDS_OFFSET = 1                   # smhv_firing_options.flags: the app's "fit to minimap" switched off
+FIRING_NONE, FIRING_SCALES, FIRING_HEIGHTMAP = 0, 1, 2   # smhv_firing.source
 VIEW_NONE, VIEW_OCR_INPUT, VIEW_FIND_SCALES_INPUT, VIEW_LSD_PREPROCESS, VIEW_LSD_INPUT, VIEW_CROPPED_BRQ = range(6)
 IMAGE_UI_MAP = 100
 
@@ -53,6 +56,19 @@ class BatchLayout(C.Structure):
         ("scales_pitch", C.c_uint64), ("scales_stride", C.c_uint64), ("scales_offset", C.c_uint64),
         ("bits_pitch_words", C.c_uint64), ("bits_stride", C.c_uint64), ("bits_xoff", C.c_uint64),
     ]
+
+
+class FiringOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("viewport_scale", C.c_float * 2), ("viewport_top_left", C.c_float * 2)]
+
+
+class Firing(C.Structure):
+    _fields_ = [("meters", C.c_double), ("alt_delta", C.c_double), ("mils", C.c_double * 2), ("bearing", C.c_float * 2),
+                ("source", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FiringResult(C.Structure):
+    _fields_ = [("n_lines", C.c_uint32), ("reserved", C.c_uint32), ("line", Firing * MAX_LINES)]
 
 
 LOG_FN = C.CFUNCTYPE(None, C.c_int, C.c_char_p)
@@ -142,7 +158,44 @@ SIGNATURES = {
     "smhv_ingest_reset": (C.c_int, [C.c_void_p]),
     "smhv_ingest_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "smhv_crc32_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "smhv_heightmap_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_void_p)]),
+    "smhv_heightmap_destroy": (None, [C.c_void_p]),
+    "smhv_heightmap_color_map": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "smhv_debug_heightmap_color_map_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
+    "smhv_batch_set_firing": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FiringOptions)]),
+    "smhv_pipeline_set_firing": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FiringOptions)]),
+    "smhv_batch_read_firing": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(FiringResult)]),
+    "smhv_batch_firing_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smhv_firing_solutions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_void_p,
+                                        C.POINTER(FiringOptions), C.POINTER(Firing)]),
 }
+
+
+def firing_options(fit_to_minimap=True, viewport=None):
+    """smhv_firing_options: fit_to_minimap=False is the app's switch off (SMHV_FIRING_BOUNDS_OFFSET); viewport = None or
+    (scale_w, scale_h, top_left_x, top_left_y), the app's MapViewport."""
+    o = FiringOptions()
+    o.size = C.sizeof(FiringOptions)
+    o.flags = 0 if fit_to_minimap else FIRING_BOUNDS_OFFSET
+    if viewport is not None:
+        sw, sh, tx, ty = viewport
+        o.viewport_scale[0], o.viewport_scale[1] = sw, sh
+        o.viewport_top_left[0], o.viewport_top_left[1] = tx, ty
+    return o
+
+
+# smhv_firing as a numpy structured dtype (the layout the header declares: 48 bytes)
+FIRING_DTYPE = None
+
+
+def firing_dtype():
+    import numpy as np
+    global FIRING_DTYPE
+    if FIRING_DTYPE is None:
+        FIRING_DTYPE = np.dtype([("meters", "<f8"), ("alt_delta", "<f8"), ("mils", "<f8", (2,)), ("bearing", "<f4", (2,)),
+                                 ("source", "<u4"), ("reserved", "<u4")], align=True)
+        assert FIRING_DTYPE.itemsize == C.sizeof(Firing)
+    return FIRING_DTYPE
 
 
 class PipelineOptions(C.Structure):

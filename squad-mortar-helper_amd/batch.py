@@ -140,6 +140,27 @@ class FrameBatch:
                 raise
         return recs
 
+    def set_firing(self, heightmap=None, fit_to_minimap=True, viewport=None):
+        """Bind a Heightmap (None = none) and the options for STAGE_FIRING runs of this batch (smhv_batch_set_firing; the
+        library keeps its own reference of the heightmap).  Without a call the runs use no heightmap and the default options."""
+        opt = L.firing_options(fit_to_minimap, viewport)
+        L.check(self._lib.smhv_batch_set_firing(self._b, heightmap._hm if heightmap is not None else None, C.byref(opt)))
+
+    def read_firing(self, first=0, n=None):
+        """Synchronising host copy of the firing slab -> (n_lines uint32 [n], numpy structured array [n, MAX_LINES] of smhv_firing)."""
+        n = self.max_frames - first if n is None else n
+        out = (L.FiringResult * n)()
+        L.check(self._lib.smhv_batch_read_firing(self._b, first, n, out))
+        raw = np.frombuffer(out, np.uint8).reshape(n, C.sizeof(L.FiringResult))
+        n_lines = raw[:, :4].copy().view(np.uint32).reshape(n)
+        lines = raw[:, 8:].copy().view(L.firing_dtype()).reshape(n, L.MAX_LINES)
+        return n_lines, lines
+
+    def firing_ptr(self):
+        d = C.c_void_p()
+        L.check(self._lib.smhv_batch_firing_ptr(self._b, C.byref(d)))
+        return d.value or 0
+
     def read_image(self, which, frame):
         x, y, w, h = self.roi
         if which == L.IMAGE_UI_MAP:
@@ -198,6 +219,12 @@ class Pipeline:
         slot = C.c_uint32(0)
         L.check(self._lib.smhv_pipeline_submit(self._p, C.c_void_p(frames_ptr), n, stages, int(bool(grayscale)), max_gap, a, C.c_void_p(after_stream), C.byref(slot)))
         return int(slot.value)
+
+    def set_firing(self, heightmap=None, fit_to_minimap=True, viewport=None):
+        """Bind a Heightmap (None = none) and the options for STAGE_FIRING submissions made after this call
+        (smhv_pipeline_set_firing); submissions in flight keep what they were submitted with."""
+        opt = L.firing_options(fit_to_minimap, viewport)
+        L.check(self._lib.smhv_pipeline_set_firing(self._p, heightmap._hm if heightmap is not None else None, C.byref(opt)))
 
     def search_stats(self):
         """Diagnostic (synchronises): the frame-granular line search of a pipeline of depth >= 3 -> dict, or None."""

@@ -1,0 +1,112 @@
+// smh_firing.h -- firing solutions of the marker lines: range from the heightmap and the minimap rectangle, altitude difference,
+// mils and bearings (src/ui/markers.rs:23-200, src/squadex/milliradians.rs, heightmap-ripper/src/lib.rs:22-25; the semantics are
+// spelt out in include/smh_vision_hip.h).  One lane per line.  Device code shared by the record tail (smh_record.inc: the
+// batch-granular searches' fused tails, the service's frame_record_tail_wave, k_finalize_firing / k_scales_finalize_firing) and by
+// k_firing_lines (smhv_firing_solutions).  Built with -ffp-contract=off: every f32 / f64 operation below is the reference's, in
+// its order, unfused.
+#pragma once
+#include "smh_device.h"
+
+namespace smh {
+
+// VELOCITY.powi(2) and VELOCITY.powi(4) as the Rust build folds them (LLVM evaluates powi of a constant with the host's pow):
+// pow(109.890938, 2) and pow(109.890938, 4), not V * V * V * V
+#define SMH_MORTAR_V2 0x1.79602562a02dfp+13
+#define SMH_MORTAR_V4 0x1.1626291c459a8p+27
+#define SMH_MORTAR_G 9.8
+
+// squadex::milliradians::calc (f64): NaN when out of range
+__device__ __forceinline__ double mortar_mils(double meters, double alt_delta) {
+	const double p1 = sqrt(SMH_MORTAR_V4 - SMH_MORTAR_G * (SMH_MORTAR_G * (meters * meters) + 2.0 * alt_delta * SMH_MORTAR_V2));
+	const double a1 = atan((SMH_MORTAR_V2 + p1) / (SMH_MORTAR_G * meters));
+	return a1 * (180.0 / 3.14159265358979323846264338327950288) / (360.0 / 6400.0);   // f64::to_degrees, then the mil
+}
+
+// Rust `f64.round() as i32`: half away from zero, saturating, NaN -> 0
+__device__ __forceinline__ int32_t round_i32(double v) {
+	const double r = round(v);
+	if (!(r == r)) return 0;
+	if (r >= 2147483647.0) return 2147483647;
+	if (r <= -2147483648.0) return (-2147483647 - 1);
+	return (int32_t)r;
+}
+
+// One line.  has_mm / mm: the frame's minimap rectangle {left, right, top, bottom}; met: the record's meters (valid iff has_mpx).
+// Both heightmap texels of the lane are loaded together, with no dependent chain between them.
+__device__ __forceinline__ smhv_firing firing_line(const FiringRun &r, bool has_mm, const uint32_t mm[4], smhv_line ln, bool has_mpx, double met) {
+	smhv_firing o;
+	// MapViewport::translate_xy
+	const float p0x = ln.x0 * r.sw + r.tx, p0y = ln.y0 * r.sh + r.ty;
+	const float p1x = ln.x1 * r.sw + r.tx, p1y = ln.y1 * r.sh + r.ty;
+	bool hm_ok = false;
+	double hm_m = 0.0, alt = 0.0;
+	if (has_mm && r.hm) {
+		float off0 = 0.0f, off1 = 0.0f;
+		if (r.flags & SMHV_FIRING_BOUNDS_OFFSET) {
+			off0 = r.b0x * ((float)(mm[1] - mm[0]) / ((float)r.hm_w + r.b0x)) * r.sw;
+			off1 = r.b0y * ((float)(mm[3] - mm[2]) / ((float)r.hm_h + r.b0y)) * r.sh;
+		}
+		const float rl = ((float)mm[0] * r.sw + r.tx) + off0, rt = ((float)mm[2] * r.sh + r.ty) + off1;
+		const float rr = (float)mm[1] * r.sw + r.tx, rb = (float)mm[3] * r.sh + r.ty;
+		const double rw = (double)(rr - rl), rh = (double)(rb - rt);
+		const double x0 = (((double)p0x - (double)rl) / rw) * (double)r.hm_w, y0 = (((double)p0y - (double)rt) / rh) * (double)r.hm_h;
+		const double x1 = (((double)p1x - (double)rl) / rw) * (double)r.hm_w, y1 = (((double)p1y - (double)rt) / rh) * (double)r.hm_h;
+		const double dx = x0 - x1, dy = y0 - y1;
+		hm_m = sqrt(dx * dx + dy * dy);
+		const int32_t ix0 = round_i32(x0), iy0 = round_i32(y0), ix1 = round_i32(x1), iy1 = round_i32(y1);
+		const int32_t W = (int32_t)r.hm_w, H = (int32_t)r.hm_h;
+		hm_ok = ix0 >= 0 && iy0 >= 0 && ix1 >= 0 && iy1 >= 0 && ix0 < W && iy0 < H && ix1 < W && iy1 < H;
+		// both texels in one round trip (texel 0 stands in for an end point outside the map)
+		const size_t i0 = hm_ok ? (size_t)iy0 * r.hm_w + (size_t)ix0 : 0u, i1 = hm_ok ? (size_t)iy1 * r.hm_w + (size_t)ix1 : 0u;
+		const uint16_t v0 = r.hm[i0], v1 = r.hm[i1];
+		const double h0 = ((double)v0 / 65535.0) * r.zscale, h1 = ((double)v1 / 65535.0) * r.zscale;
+		alt = h1 - h0;
+	}
+	uint32_t source = SMHV_FIRING_NONE;
+	double meters = 0.0;
+	if (hm_ok) { source = SMHV_FIRING_HEIGHTMAP; meters = hm_m; }
+	else if (has_mpx) { source = SMHV_FIRING_SCALES; meters = met; alt = 0.0; }
+	else alt = 0.0;
+	o.meters = meters;
+	o.alt_delta = alt;
+	if (source != SMHV_FIRING_NONE) {
+		o.mils[0] = mortar_mils(meters, alt);
+		o.mils[1] = mortar_mils(meters, -alt);
+	} else {
+		o.mils[0] = 0.0; o.mils[1] = 0.0;
+	}
+	// bearings (markers.rs:98-110): f32::to_degrees, then whole degrees half away from zero, mod 360
+	const float angle = atan2f(p0y - p1y, p0x - p1x);
+	float d = angle * 57.2957795130823208767981548141051703f;
+	if (d > 0.0f) {
+		d -= 90.0f;
+		if (d < 0.0f) d += 360.0f;
+	} else {
+		d += 270.0f;
+	}
+	const float fwd = fmodf(roundf(d), 360.0f);
+	o.bearing[0] = fwd;
+	o.bearing[1] = fmodf(roundf(fwd + 180.0f), 360.0f);
+	o.source = source;
+	o.reserved = 0u;
+	return o;
+}
+
+// The frame's firing slab from its finished record: lane l (< 64) takes line l.  Called by one wave after a wave barrier behind
+// lane 0's header writes (the record is read back: n_lines, m/px, the minimap rectangle and the line's own fields).
+__device__ __forceinline__ void firing_frame_tail(const Buffers *bp, uint32_t f, uint32_t lane) {
+	const FiringRun *rp = bp->firing;
+	const smhv_frame_result *res = &bp->results[f];
+	const uint32_t n = res->n_lines, has_mpx = res->has_mpx, has_mm = res->has_minimap;
+	const uint32_t mm[4] = {res->minimap[0], res->minimap[1], res->minimap[2], res->minimap[3]};
+	const FiringRun r = *rp;
+	smhv_firing_result *out = &r.out[f];
+	if (lane < SMHV_MAX_LINES) {
+		smhv_firing o{};
+		if (lane < n) o = firing_line(r, has_mm != 0u, mm, res->lines[lane], has_mpx != 0u, res->meters[lane]);
+		out->line[lane] = o;
+	}
+	if (lane == 0) { out->n_lines = n; out->reserved = 0u; }
+}
+
+}  // namespace smh

@@ -143,7 +143,22 @@ struct Buffers {
 	// batches of ONE long ray at the same time (k_lsd_wave).  null: long rays are walked batch after batch.
 	const float *ray_off;
 	LsdCoopBufs co;
+	// SMHV_STAGE_FIRING: the run's firing parameters (smh_firing.h), a per-batch block uploaded with the run (null: no firing)
+	const struct FiringRun *firing;
 };
+// Per-run parameters of the firing solutions (smh_firing.h): what smhv_batch_set_firing / smhv_pipeline_set_firing bound when the
+// run was enqueued, and the batch's firing slab.  Uploaded from pinned staging with the run, so a submission in flight keeps its own.
+struct FiringRun {
+	const uint16_t *hm;            // heightmap texels, row-major (null: none bound)
+	smhv_firing_result *out;       // the batch's firing slab, one entry per frame
+	uint32_t hm_w, hm_h;
+	float b0x, b0y;                // bounds[0] as f32
+	double zscale;                 // scale[2] as f64 / 0.1953125
+	uint32_t flags;                // SMHV_FIRING_*
+	float sw, sh, tx, ty;          // map viewport: scale factors and top left
+	uint32_t pad;
+};
+static_assert(sizeof(FiringRun) == 64, "one 64-byte block per run");
 // ---- the mask as the streaming passes leave it for the line search (round 6) -------------------------------------------------
 // A marker mask is 1-4 % non-empty, and what the search keeps in LDS is its non-empty 32 x 8 px tiles.  Finding them in the
 // row-major bit rows meant walking the bounding box of the set bits: (tile rows x tile columns) x 16 strided dword loads, ~68 KB
@@ -350,6 +365,11 @@ hipError_t launch_scale_ratio(const Geom &g, const Buffers &b, uint32_t n, uint3
 hipError_t launch_find_minimap(const Geom &g, const Buffers &b, uint32_t n, hipStream_t s);
 hipError_t launch_finalize(const Geom &g, const Buffers &b, uint32_t n, uint32_t stages, hipStream_t s);
 hipError_t launch_scales_finalize(const Geom &g, const Buffers &b, uint32_t n, uint32_t stages, uint32_t *d_bars, hipStream_t s);   // scale ratio + finalize
+// firing solutions (smh_firing.h): explicit lines (smhv_firing_solutions), and the heightmap colour map's two passes
+// (mm: two words, {max, min}, initialised to {0, 0xFFFFFFFF} on `s` by the launcher)
+hipError_t launch_firing_lines(const FiringRun &r, const smhv_line *lines, uint32_t n, uint32_t has_mpx, double mpx, uint32_t has_minimap,
+                               const uint32_t minimap[4], smhv_firing *out, hipStream_t s);
+hipError_t launch_heightmap_color_map(const uint16_t *hm, uint64_t n, uint32_t *mm, uint32_t *rgba, hipStream_t s);
 // which: SMHV_VIEW_*; isolated: LSDPreprocess shows the marker-isolated crop (after isolate_map_markers)
 hipError_t launch_debug_view(const Geom &g, const Buffers &b, uint32_t frame, int which, int isolated, uint8_t *d_rgba, hipStream_t s);
 hipError_t launch_marker_table(uint32_t *d_bits, hipStream_t s);

@@ -2,6 +2,8 @@
 //   k_scale_ratio  calc_meters_to_px_ratio / find_scale_width                 (src/vision/mpx_ratio.rs:3-134)
 //   k_find_minimap find_minimap (the caller's next step)                      (src/vision/find_minimap.rs)
 //   k_finalize     derived marker outputs                                     (src/ui/mod.rs:131-140, markers.rs:98)
+//   k_firing_lines firing solutions of explicit lines                         (src/ui/markers.rs:23-200; smh_firing.h)
+//   k_hm_minmax / k_hm_color  heightmap overlay colours                       (src/ui/heightmaps.rs:169-207)
 //   k_debug_view   DebugView images                                           (vision-cpu/src/lib.rs:451-460)
 //   k_marker_table exhaustive colour-predicate table (test support)
 //   k_crc32        CRC-32 of a frame in HBM for the capture hand-off          (src/capture.rs:44-47)
@@ -101,6 +103,115 @@ __global__ void __launch_bounds__(64 * SMHV_MAX_SCALES) k_scales_finalize(Geom g
 	if (threadIdx.x < 64) finalize_body(g, b, blockIdx.x, stages);
 }
 
+// the same two with SMHV_STAGE_FIRING: the firing slab after the record (smh_firing.h)
+__global__ void __launch_bounds__(64) k_finalize_firing(Geom g, Buffers b, uint32_t stages) {
+	finalize_body(g, b, blockIdx.x, stages);
+	firing_after_finalize(&b, blockIdx.x, threadIdx.x);
+}
+__global__ void __launch_bounds__(64 * SMHV_MAX_SCALES) k_scales_finalize_firing(Geom g, Buffers b, uint32_t stages, uint32_t *bars) {
+	scale_ratio_body(g, b, blockIdx.x, bars);
+	__syncthreads();
+	if (threadIdx.x < 64) {
+		finalize_body(g, b, blockIdx.x, stages);
+		firing_after_finalize(&b, blockIdx.x, threadIdx.x);
+	}
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_firing_lines: smhv_firing_solutions -- the record tail's device function on explicit lines, one thread per line.  The
+// record's meters are restated as Marker::new computes them (src/ui/mod.rs:131-140, as finalize_body does).
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_firing_lines(FiringRun r, const smhv_line *lines, uint32_t n, uint32_t has_mpx, double mpx, uint32_t has_mm,
+                                                      uint32_t mm0, uint32_t mm1, uint32_t mm2, uint32_t mm3, smhv_firing *out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const smhv_line ln = lines[i];
+	const double ax = (double)ln.x0 - (double)ln.x1, ay = (double)ln.y0 - (double)ln.y1;
+	const double met = has_mpx ? sqrt(ax * ax + ay * ay) * mpx : 0.0;
+	const uint32_t mm[4] = {mm0, mm1, mm2, mm3};
+	out[i] = firing_line(r, has_mm != 0u, mm, ln, has_mpx != 0u, met);
+}
+
+// ------------------------------------------------------------------------------------------------
+// color_map_heightmap (src/ui/heightmaps.rs:169-207).  Pass 1: max / min of the texels (per wave, then one vector global atomic
+// per workgroup and word).  Pass 2: the colour of every texel in f64, two texels per thread (one 4-byte load, one 8-byte store).
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_hm_minmax(const uint16_t *__restrict__ hm, uint64_t n, uint32_t *mm) {
+	__shared__ uint32_t s_mx[4], s_mn[4];
+	uint32_t mx = 0u, mn = 0xFFFFu;
+	const uint64_t stride = (uint64_t)gridDim.x * blockDim.x * 4u;
+	for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4u; i < n; i += stride) {
+		if (i + 4u <= n) {
+			const uint2 v = *(const uint2 *)(hm + i);
+			const uint32_t a = v.x & 0xFFFFu, b = v.x >> 16, c = v.y & 0xFFFFu, d = v.y >> 16;
+			mx = max(mx, max(max(a, b), max(c, d)));
+			mn = min(mn, min(min(a, b), min(c, d)));
+		} else {
+			for (uint64_t k = i; k < n; ++k) { mx = max(mx, (uint32_t)hm[k]); mn = min(mn, (uint32_t)hm[k]); }
+		}
+	}
+	for (int o = 32; o > 0; o >>= 1) {
+		mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+		mn = min(mn, (uint32_t)__shfl_xor((int)mn, o));
+	}
+	const uint32_t wave = threadIdx.x >> 6;
+	if ((threadIdx.x & 63u) == 0u) { s_mx[wave] = mx; s_mn[wave] = mn; }
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		for (uint32_t w = 1; w < (blockDim.x >> 6); ++w) { mx = max(mx, s_mx[w]); mn = min(mn, s_mn[w]); }
+		atomicMax(&mm[0], mx);
+		atomicMin(&mm[1], mn);
+	}
+}
+
+__device__ __forceinline__ uint32_t hm_color(uint32_t v, uint32_t mx, uint32_t mn) {
+	if (v == 0u && mn != 0u) return 0u;                      // "transparent": never true (a 0 texel makes min 0), kept as written
+	const double h = ((double)v - (double)mn) / (double)(mx - mn);
+	// f64::max(NaN, 0.0) = 0.0 (the NaN of a constant map drops out): fmax does the same
+	const double r = fmax(h - 0.5, 0.0) / 0.5;
+	const double b = fmax((1.0 - h) - 0.5, 0.0) / 0.5;
+	const double g = 1.0 - (h > 0.5 ? r : b);
+	// `as u8`: truncation, saturating (the values are in [0, 255])
+	const uint32_t ri = (uint32_t)(r * 255.0), gi = (uint32_t)(g * 255.0), bi = (uint32_t)(b * 255.0);
+	return ri | gi << 8 | bi << 16 | 0xFF000000u;
+}
+
+__global__ void __launch_bounds__(256) k_hm_color(const uint16_t *__restrict__ hm, uint64_t n, const uint32_t *mm, uint32_t *__restrict__ rgba) {
+	const uint32_t mx = mm[0], mn = mm[1];
+	const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 2u;
+	if (i + 2u <= n) {
+		const uint32_t v = *(const uint32_t *)(hm + i);
+		*(uint2 *)(rgba + i) = make_uint2(hm_color(v & 0xFFFFu, mx, mn), hm_color(v >> 16, mx, mn));
+	} else if (i < n) {
+		rgba[i] = hm_color(hm[i], mx, mn);
+	}
+}
+
+hipError_t launch_firing_lines(const FiringRun &r, const smhv_line *lines, uint32_t n, uint32_t has_mpx, double mpx, uint32_t has_minimap,
+                               const uint32_t minimap[4], smhv_firing *out, hipStream_t s) {
+	hipLaunchKernelGGL(k_firing_lines, dim3((n + 255u) / 256u), dim3(256), 0, s, r, lines, n, has_mpx, mpx, has_minimap, minimap[0], minimap[1], minimap[2],
+	                   minimap[3], out);
+	return hipGetLastError();
+}
+
+hipError_t launch_heightmap_color_map(const uint16_t *hm, uint64_t n, uint32_t *mm, uint32_t *rgba, hipStream_t s) {
+	static const uint32_t init[2] = {0u, 0xFFFFFFFFu};
+	hipError_t e = hipMemcpyAsync(mm, init, sizeof init, hipMemcpyHostToDevice, s);
+	if (e != hipSuccess) return e;
+	int dev = 0, cus = 256;
+	(void)hipGetDevice(&dev);
+	(void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+	const uint64_t quads = (n + 3u) / 4u;
+	uint64_t blocks = (quads + 255u) / 256u;
+	if (blocks > (uint64_t)cus * 8u) blocks = (uint64_t)cus * 8u;     // grid-stride beyond eight workgroups per CU
+	hipLaunchKernelGGL(k_hm_minmax, dim3((uint32_t)blocks), dim3(256), 0, s, hm, n, mm);
+	e = hipGetLastError();
+	if (e != hipSuccess) return e;
+	const uint64_t pairs = (n + 1u) / 2u;
+	hipLaunchKernelGGL(k_hm_color, dim3((uint32_t)((pairs + 255u) / 256u)), dim3(256), 0, s, hm, n, (const uint32_t *)mm, rgba);
+	return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // debug views (vision-cpu/src/lib.rs:451-460) and the exhaustive colour table
 // ------------------------------------------------------------------------------------------------
@@ -169,12 +280,14 @@ hipError_t launch_find_minimap(const Geom &g, const Buffers &b, uint32_t n, hipS
 }
 
 hipError_t launch_finalize(const Geom &g, const Buffers &b, uint32_t n, uint32_t stages, hipStream_t s) {
-	hipLaunchKernelGGL(k_finalize, dim3(n), dim3(64), 0, s, g, b, stages);
+	if (stages & SMHV_STAGE_FIRING) hipLaunchKernelGGL(k_finalize_firing, dim3(n), dim3(64), 0, s, g, b, stages);
+	else hipLaunchKernelGGL(k_finalize, dim3(n), dim3(64), 0, s, g, b, stages);
 	return hipGetLastError();
 }
 
 hipError_t launch_scales_finalize(const Geom &g, const Buffers &b, uint32_t n, uint32_t stages, uint32_t *d_bars, hipStream_t s) {
-	hipLaunchKernelGGL(k_scales_finalize, dim3(n), dim3(64 * SMHV_MAX_SCALES), 0, s, g, b, stages, d_bars);
+	if (stages & SMHV_STAGE_FIRING) hipLaunchKernelGGL(k_scales_finalize_firing, dim3(n), dim3(64 * SMHV_MAX_SCALES), 0, s, g, b, stages, d_bars);
+	else hipLaunchKernelGGL(k_scales_finalize, dim3(n), dim3(64 * SMHV_MAX_SCALES), 0, s, g, b, stages, d_bars);
 	return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 // asks for it (Buffers::rec_stages): one kernel less in every batch's chain on its hardware queue.
 #pragma once
 #include "smh_device.h"
+#include "smh_firing.h"
 
 namespace smh {
 
@@ -162,6 +163,14 @@ __device__ __forceinline__ void finalize_body(const Geom &g, const Buffers &b, u
 
 __device__ __forceinline__ void finalize_body(const Geom &g, const Buffers &b, uint32_t f, uint32_t stages) { finalize_body(g, b, f, stages, threadIdx.x); }
 
+// SMHV_STAGE_FIRING after finalize_body, by the wave that wrote the record: lane 0's header has left before the lanes read it back
+__device__ __forceinline__ void firing_after_finalize(const Buffers *bp, uint32_t f, uint32_t lane) {
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+	__builtin_amdgcn_wave_barrier();
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+	firing_frame_tail(bp, f, lane);
+}
+
 // scale ratio + record by ONE workgroup of at least 64 threads, any size (the waves take the label anchors in turn); every
 // thread of the workgroup must call it, after a barrier behind the line search's own writes of the record
 __device__ __attribute__((noinline)) void frame_record_tail(const Geom *gp, const Buffers *bp, uint32_t f) {
@@ -172,7 +181,10 @@ __device__ __attribute__((noinline)) void frame_record_tail(const Geom *gp, cons
 		scale_ratio_body(g, b, f, b.rec_bars);
 		__syncthreads();                                       // thread 0's has_mpx / mpx are visible to the block
 	}
-	if (threadIdx.x < 64) finalize_body(g, b, f, stages);
+	if (threadIdx.x < 64) {
+		finalize_body(g, b, f, stages);
+		if (stages & SMHV_STAGE_FIRING) firing_after_finalize(bp, f, threadIdx.x);
+	}
 }
 
 // The same by ONE WAVE of a workgroup whose other waves are busy with other frames (k_lsd_service): the wave takes the label
@@ -214,6 +226,7 @@ __device__ __attribute__((noinline)) void frame_record_tail_wave(const Geom *gp,
 	__builtin_amdgcn_wave_barrier();
 	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 	finalize_body(g, b, f, stages, lane);
+	if (stages & SMHV_STAGE_FIRING) firing_after_finalize(bp, f, lane);   // (before the service counts the frame off)
 }
 
 }  // namespace smh

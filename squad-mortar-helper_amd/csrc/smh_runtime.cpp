@@ -221,7 +221,27 @@ struct smhv_batch {
 	// probe of a pipeline that adapts its policy to the workload: start of the streaming pass, its end, end of the line search
 	hipEvent_t ev_probe[3] = {nullptr, nullptr, nullptr};
 	bool probe = false, probe_valid = false;
+	// SMHV_STAGE_FIRING: the bound heightmap (a reference of the batch's own) and options, the firing slab (allocated by the first run
+	// that asks for it), the per-run parameter block on the device and its pinned staging (reused like the anchors')
+	smhv_heightmap *fire_hm = nullptr;
+	smhv_firing_options fire_opt{};
+	smhv_firing_result *d_firing = nullptr;
+	FiringRun *d_fire_run = nullptr;
+	struct FireStage { FiringRun *h = nullptr; hipEvent_t done = nullptr; };
+	std::vector<FireStage> fire_stage;
 };
+
+// a device copy of a heightmap (smhv_heightmap_create); batches and pipelines that have it bound hold references of their own
+struct smhv_heightmap {
+	smhv_ctx *ctx = nullptr;
+	uint16_t *d = nullptr;
+	uint32_t w = 0, h = 0;
+	int32_t bounds[4] = {0, 0, 0, 0};
+	float scale[3] = {0.0f, 0.0f, 0.0f};
+	std::atomic<int> refs{1};
+};
+static void hm_retain(smhv_heightmap *hm) { if (hm) hm->refs.fetch_add(1, std::memory_order_relaxed); }
+static void hm_release(smhv_heightmap *hm);
 
 struct smhv_ctx {
 	int device = 0;
@@ -237,6 +257,9 @@ struct smhv_ctx {
 	size_t h_ui_cap[2] = {0, 0};
 	uint8_t *d_ui_tight = nullptr;                               // the ui_map packed tightly on the device: it leaves as contiguous copies (k_pack_rows)
 	size_t d_ui_tight_cap = 0;
+	uint8_t *d_fire = nullptr, *h_fire = nullptr;               // smhv_firing_solutions: lines in, results out (device and pinned host, grown on demand)
+	size_t fire_cap = 0;
+	std::mutex fire_mu;                                          // ... held by a call from sizing its buffers to its last copy (not `mu`: submissions take that)
 	uint32_t ui_turn = 0;
 	bool ui_pending = false, minimap_cached = false;
 	// current frame (per-call trait path); ~ GpuMemory
@@ -359,6 +382,7 @@ static Buffers make_buffers(smhv_batch *b, const uint8_t *frames, uint32_t resul
 	bf.tiled = b->d_tiled; bf.occ = b->d_occ;
 	bf.results = b->d_results + result_slot;
 	bf.anchors = b->d_anchors;
+	bf.firing = nullptr;
 	bf.co.ctl = nullptr;                                     // k_lsd cooperation is opt-in: smhv_batch_run sets it for SMHV_STAGE_LSD_HELPERS
 	bf.co.coop = (LsdCoop *)(b->d_lsd_ctl + sizeof(LsdCtl));
 	bf.co.req = b->d_lsd_req;
@@ -443,6 +467,9 @@ extern "C" SMHV_API void smhv_shutdown(smhv_ctx *c) {
 	for (int i = 0; i < 2; ++i) { if (c->ev_ui[i]) (void)hipEventDestroy(c->ev_ui[i]); if (c->h_ui[i]) (void)hipHostFree(c->h_ui[i]); c->ev_ui[i] = nullptr; c->h_ui[i] = nullptr; c->h_ui_cap[i] = 0; }
 	if (c->d_ui_tight) (void)hipFree(c->d_ui_tight);
 	c->d_ui_tight = nullptr; c->d_ui_tight_cap = 0;
+	if (c->d_fire) (void)hipFree(c->d_fire);
+	if (c->h_fire) (void)hipHostFree(c->h_fire);
+	c->d_fire = c->h_fire = nullptr; c->fire_cap = 0;
 	c->s_ui = nullptr; c->ev_map = nullptr;
 	c->d_frame = nullptr; c->d_frame_cap = 0; c->h_ocr = c->h_scales = nullptr; c->h_res = nullptr; c->h_aux = nullptr; c->h_bars = nullptr;
 	c->s_main = c->s_markers = c->s_scales = nullptr;
@@ -588,7 +615,7 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	if (b->ctx) (void)hipSetDevice(b->ctx->device);
 	(void)hipDeviceSynchronize();
 	void *ptrs[] = {b->d_ui, b->d_mask, b->d_bits, b->d_tiled, b->d_occ, b->d_ocr, b->d_scales, b->d_aux, b->d_results, b->d_anchors, b->d_bars, b->d_farm,
-	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache};
+	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	if (b->h_err) (void)hipHostFree(b->h_err);
@@ -596,6 +623,11 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 		if (a.h) (void)hipHostFree(a.h);
 		if (a.done) (void)hipEventDestroy(a.done);
 	}
+	for (auto &a : b->fire_stage) {
+		if (a.h) (void)hipHostFree(a.h);
+		if (a.done) (void)hipEventDestroy(a.done);
+	}
+	hm_release(b->fire_hm);
 	if (b->ev) {
 		for (int r = 0; r < smhv_batch::TIMING_RING; ++r)
 			for (int i = 0; i < smhv_batch::TIMING_EVENTS; ++i) if (b->ev[r][i]) (void)hipEventDestroy(b->ev[r][i]);
@@ -668,6 +700,92 @@ extern "C" SMHV_API int smhv_batch_enable_timing(smhv_batch *b, int enable) {
 // s_pro: the pipeline's prologue stream -- the anchor upload and the button test of a submission run there, ahead of time, so
 // that the chain on a streaming stream is pass -> publication -> pass: the button test (45 us inside a busy pipeline, plus a
 // hand-over) is off it.
+// ------------------------------------------------------------------------------------------------
+// firing solutions (smh_firing.h): heightmaps, bindings, the per-run parameter block
+// ------------------------------------------------------------------------------------------------
+// The last reference frees the device copy once everything enqueued before has finished (a batch-granular run reads it on a stream,
+// a frame-granular one in the service: the device-wide synchronize covers both; the service closes when nothing is outstanding).
+// Never called between counting a frame-granular submission and publishing it.
+static void hm_release(smhv_heightmap *hm) {
+	if (!hm || hm->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
+	(void)hipSetDevice(hm->ctx->device);
+	(void)hipDeviceSynchronize();
+	if (hm->d) (void)hipFree(hm->d);
+	ctx_release(hm->ctx);
+	delete hm;
+}
+
+static smhv_firing_options firing_opts(const smhv_firing_options *opt) {
+	smhv_firing_options o{};
+	o.size = sizeof o;
+	if (opt) { o.flags = opt->flags; o.viewport_scale[0] = opt->viewport_scale[0]; o.viewport_scale[1] = opt->viewport_scale[1];
+	           o.viewport_top_left[0] = opt->viewport_top_left[0]; o.viewport_top_left[1] = opt->viewport_top_left[1]; }
+	if (o.viewport_scale[0] == 0.0f) o.viewport_scale[0] = 1.0f;     // a zero scale means 1
+	if (o.viewport_scale[1] == 0.0f) o.viewport_scale[1] = 1.0f;
+	return o;
+}
+
+static void firing_run_params(const smhv_heightmap *hm, const smhv_firing_options *o, FiringRun *r) {
+	memset(r, 0, sizeof *r);
+	if (hm) {
+		r->hm = hm->d; r->hm_w = hm->w; r->hm_h = hm->h;
+		r->b0x = (float)hm->bounds[0]; r->b0y = (float)hm->bounds[1];
+		r->zscale = (double)hm->scale[2] / 0.1953125;
+	}
+	// (every run's and call's block is built here: a zero scale means 1 also for a batch nobody called set_firing on)
+	r->flags = o->flags;
+	r->sw = o->viewport_scale[0] == 0.0f ? 1.0f : o->viewport_scale[0];
+	r->sh = o->viewport_scale[1] == 0.0f ? 1.0f : o->viewport_scale[1];
+	r->tx = o->viewport_top_left[0]; r->ty = o->viewport_top_left[1];
+}
+
+static void firing_bind(smhv_batch *b, smhv_heightmap *hm, const smhv_firing_options *opt) {
+	b->fire_opt = firing_opts(opt);
+	if (b->fire_hm == hm) return;
+	hm_retain(hm);
+	smhv_heightmap *old = b->fire_hm;
+	b->fire_hm = hm;
+	hm_release(old);
+}
+
+static int check_firing_options(const smhv_firing_options *opt) {
+	if (opt && opt->size != 0u && opt->size < sizeof(smhv_firing_options)) return fail(SMHV_E_INVALID, "smhv_firing_options.size %u < %zu", opt->size, sizeof(smhv_firing_options));
+	if (opt && (opt->flags & ~SMHV_FIRING_BOUNDS_OFFSET)) return fail(SMHV_E_INVALID, "unknown firing flags 0x%x", opt->flags);
+	return SMHV_OK;
+}
+
+// SMHV_STAGE_FIRING: the run's parameter block (the batch's binding as it stands now) from pinned staging into the batch's device block,
+// on the stream of the run's first kernel (sb); the slab is allocated by the first run that asks for it
+static int firing_upload(smhv_batch *b, hipStream_t sb) {
+	if (!b->d_firing) {
+		hipError_t e = hipMalloc((void **)&b->d_firing, sizeof(smhv_firing_result) * (size_t)b->max_frames);
+		if (e == hipSuccess) e = hipMalloc((void **)&b->d_fire_run, sizeof(FiringRun));
+		if (e == hipSuccess) e = hipMemset(b->d_firing, 0, sizeof(smhv_firing_result) * (size_t)b->max_frames);
+		if (e != hipSuccess) {
+			if (b->d_firing) (void)hipFree(b->d_firing);
+			if (b->d_fire_run) (void)hipFree(b->d_fire_run);
+			b->d_firing = nullptr; b->d_fire_run = nullptr;
+			return fail(SMHV_E_HIP, "firing slab: %s", hipGetErrorString(e));
+		}
+	}
+	smhv_batch::FireStage *st = nullptr;
+	for (auto &a : b->fire_stage)
+		if (hipEventQuery(a.done) == hipSuccess) { st = &a; break; }
+	if (!st) {
+		smhv_batch::FireStage a;
+		hipError_t e = hipHostMalloc((void **)&a.h, sizeof(FiringRun));
+		if (e == hipSuccess) e = hipEventCreateWithFlags(&a.done, hipEventDisableTiming);
+		if (e != hipSuccess) { if (a.h) (void)hipHostFree(a.h); return fail(SMHV_E_HIP, "firing staging: %s", hipGetErrorString(e)); }
+		b->fire_stage.push_back(a);
+		st = &b->fire_stage.back();
+	}
+	firing_run_params(b->fire_hm, &b->fire_opt, st->h);
+	st->h->out = b->d_firing;
+	HIPCHK(hipMemcpyAsync(b->d_fire_run, st->h, sizeof(FiringRun), hipMemcpyHostToDevice, sb));
+	HIPCHK(hipEventRecord(st->done, sb));
+	return SMHV_OK;
+}
+
 struct SvcPublish { SvcCtl *ctl; unsigned long long *ring; SvcSlot *slots; uint32_t slot, seq, ring_log2; const uint32_t *cull_tab; bool have_cull; hipStream_t s_pro; hipEvent_t ev_pro;
                     bool *published; };   // <- set once k_svc_publish has been enqueued (from then on the device WILL complete the submission)
 static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint32_t stages, int grayscale, uint32_t max_gap,
@@ -675,7 +793,8 @@ static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint3
 	if (!b || !d_frames || n == 0 || n > b->max_frames) return fail(SMHV_E_INVALID, "bad arguments (n=%u, capacity %u)", n, b ? b->max_frames : 0);
 	CTX_OPEN(b->ctx);
 	if ((stages & (SMHV_STAGE_ALL | SMHV_STAGE_MINIMAP)) == 0) return fail(SMHV_E_INVALID, "no stage selected");
-	stages &= SMHV_STAGE_ALL | SMHV_STAGE_MINIMAP | SMHV_STAGE_EXACT_STATS | SMHV_STAGE_LSD_HELPERS;
+	if ((stages & SMHV_STAGE_FIRING) && !(stages & SMHV_STAGE_MARKERS)) return fail(SMHV_E_INVALID, "SMHV_STAGE_FIRING needs SMHV_STAGE_MARKERS");
+	stages &= SMHV_STAGE_ALL | SMHV_STAGE_MINIMAP | SMHV_STAGE_EXACT_STATS | SMHV_STAGE_LSD_HELPERS | SMHV_STAGE_FIRING;
 	HIPCHK(hipSetDevice(b->ctx->device));
 	const Geom &g = b->g;
 	Buffers bf = make_buffers(b, (const uint8_t *)d_frames, 0);
@@ -708,6 +827,11 @@ static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint3
 		memcpy(st->h, anchors, sizeof(smhv_anchors) * n);
 		HIPCHK(hipMemcpyAsync(b->d_anchors, st->h, sizeof(smhv_anchors) * n, hipMemcpyHostToDevice, sb));
 		HIPCHK(hipEventRecord(st->done, sb));
+	}
+	if (stages & SMHV_STAGE_FIRING) {
+		int rc = firing_upload(b, sb);
+		if (rc) return rc;
+		bf.firing = b->d_fire_run;
 	}
 	const bool t = b->timing;
 	hipEvent_t *ev = t ? b->ev[b->timed_runs % smhv_batch::TIMING_RING] : nullptr;
@@ -971,6 +1095,8 @@ struct smhv_pipeline {
 	std::mutex peek_mu;                 // smhv_debug_pipeline_peek (any thread)
 	hipStream_t s_peek = nullptr;
 	SvcCtl *h_peek = nullptr;
+	smhv_heightmap *fire_hm = nullptr;  // smhv_pipeline_set_firing: bound into a slot's batch by each submission with SMHV_STAGE_FIRING
+	smhv_firing_options fire_opt{};
 	std::vector<hipEvent_t> ev_pub;     // per slot: the slot's items have been published
 	std::vector<hipEvent_t> ev_pro;     // per slot: its button test has run
 	std::vector<uint32_t> seq;          // per slot: sequence number of its most recent submission (0: none yet)
@@ -1037,6 +1163,7 @@ extern "C" SMHV_API void smhv_pipeline_destroy(smhv_pipeline *p) {
 	if (p->d_svc_remote) (void)hipFree(p->d_svc_remote);
 	if (p->d_svc_store) (void)hipFree(p->d_svc_store);
 	if (p->h_svc) (void)hipHostFree(p->h_svc);
+	hm_release(p->fire_hm);
 	ctx_release(p->ctx);
 	delete p;
 }
@@ -1493,6 +1620,9 @@ extern "C" SMHV_API int smhv_pipeline_submit(smhv_pipeline *p, const void *d_fra
 	CTX_OPEN(p->ctx);
 	HIPCHK(hipSetDevice(p->ctx->device));
 	const uint32_t slot = (uint32_t)(p->submitted % p->depth);
+	// the submission takes the pipeline's firing binding as it stands now (before anything of it is counted or enqueued: dropping
+	// the last reference of a heightmap synchronises the device)
+	if (stages & SMHV_STAGE_FIRING) firing_bind(p->batch[slot], p->fire_hm, &p->fire_opt);
 	if (p->adaptive) { int rc = mode_control(p, n, stages, max_gap); if (rc) return rc; }
 	if (p->svc && p->mode_frame) {
 		int rc = svc_submit(p, slot, d_frames, n, stages, grayscale, max_gap, anchors, after_stream, slot_out);
@@ -2624,5 +2754,151 @@ extern "C" SMHV_API int smhv_ingest_counts(smhv_ingest *q, uint64_t *n_new, uint
 	if (!q) return fail(SMHV_E_INVALID, "ingest_counts: null argument");
 	if (n_new) *n_new = q->n_new;
 	if (n_dup) *n_dup = q->n_dup;
+	return SMHV_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// firing solutions: public entry points (smh_vision_hip.h; device code in smh_firing.h / smh_misc.hip)
+// ------------------------------------------------------------------------------------------------
+extern "C" SMHV_API int smhv_heightmap_create(smhv_ctx *c, const uint16_t *data, uint32_t w, uint32_t h, const int32_t bounds[4], const float scale[3],
+                                              smhv_heightmap **out) {
+	if (!c || !data || !bounds || !scale || !out) return fail(SMHV_E_INVALID, "heightmap_create: null argument");
+	*out = nullptr;
+	CTX_OPEN(c);
+	if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 28)) return fail(SMHV_E_INVALID, "heightmap_create: %u x %u texels (1 .. 2^28)", w, h);
+	HIPCHK(hipSetDevice(c->device));
+	smhv_heightmap *hm = new (std::nothrow) smhv_heightmap();
+	if (!hm) return fail(SMHV_E_INVALID, "out of host memory");
+	hm->w = w; hm->h = h;
+	memcpy(hm->bounds, bounds, sizeof hm->bounds);
+	memcpy(hm->scale, scale, sizeof hm->scale);
+	const size_t bytes = (size_t)w * h * sizeof(uint16_t);
+	hipError_t e = hipMalloc((void **)&hm->d, bytes);
+	if (e == hipSuccess) e = hipMemcpy(hm->d, data, bytes, hipMemcpyHostToDevice);
+	if (e != hipSuccess) {
+		if (hm->d) (void)hipFree(hm->d);
+		delete hm;
+		return fail(SMHV_E_HIP, "heightmap_create: %s", hipGetErrorString(e));
+	}
+	c->refs.fetch_add(1, std::memory_order_relaxed);
+	hm->ctx = c;
+	*out = hm;
+	return SMHV_OK;
+}
+
+extern "C" SMHV_API void smhv_heightmap_destroy(smhv_heightmap *hm) { hm_release(hm); }
+
+extern "C" SMHV_API int smhv_heightmap_color_map(smhv_heightmap *hm, uint8_t *rgba) {
+	if (!hm || !rgba) return fail(SMHV_E_INVALID, "heightmap_color_map: null argument");
+	smhv_ctx *c = hm->ctx;
+	CTX_OPEN(c);
+	HIPCHK(hipSetDevice(c->device));
+	const uint64_t n = (uint64_t)hm->w * hm->h;
+	uint32_t *d = nullptr;                                    // {max, min}, then the image
+	HIPCHK(hipMalloc((void **)&d, 16 + n * 4));
+	hipError_t e = launch_heightmap_color_map(hm->d, n, d, d + 4, c->s_main);
+	if (e == hipSuccess) e = hipMemcpyAsync(rgba, d + 4, n * 4, hipMemcpyDeviceToHost, c->s_main);
+	if (e == hipSuccess) e = hipStreamSynchronize(c->s_main);
+	(void)hipFree(d);
+	if (e != hipSuccess) return fail(SMHV_E_HIP, "heightmap_color_map: %s", hipGetErrorString(e));
+	return SMHV_OK;
+}
+
+extern "C" SMHV_API int smhv_debug_heightmap_color_map_device(smhv_heightmap *hm, void *d_rgba, float *ms) {
+	if (!hm || !d_rgba) return fail(SMHV_E_INVALID, "heightmap_color_map_device: null argument");
+	smhv_ctx *c = hm->ctx;
+	CTX_OPEN(c);
+	HIPCHK(hipSetDevice(c->device));
+	uint32_t *mm = nullptr;
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	HIPCHK(hipMalloc((void **)&mm, 16));
+	hipError_t e = hipEventCreate(&e0);
+	if (e == hipSuccess) e = hipEventCreate(&e1);
+	if (e == hipSuccess) e = hipEventRecord(e0, c->s_main);
+	if (e == hipSuccess) e = launch_heightmap_color_map(hm->d, (uint64_t)hm->w * hm->h, mm, (uint32_t *)d_rgba, c->s_main);
+	if (e == hipSuccess) e = hipEventRecord(e1, c->s_main);
+	if (e == hipSuccess) e = hipEventSynchronize(e1);
+	float t = 0.0f;
+	if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
+	if (e0) (void)hipEventDestroy(e0);
+	if (e1) (void)hipEventDestroy(e1);
+	(void)hipFree(mm);
+	if (e != hipSuccess) return fail(SMHV_E_HIP, "heightmap_color_map_device: %s", hipGetErrorString(e));
+	if (ms) *ms = t;
+	return SMHV_OK;
+}
+
+extern "C" SMHV_API int smhv_batch_set_firing(smhv_batch *b, smhv_heightmap *hm, const smhv_firing_options *opt) {
+	if (!b) return fail(SMHV_E_INVALID, "batch_set_firing: null batch");
+	CTX_OPEN(b->ctx);
+	int rc = check_firing_options(opt);
+	if (rc) return rc;
+	if (hm && hm->ctx->device != b->ctx->device) return fail(SMHV_E_INVALID, "batch_set_firing: the heightmap lives on device %d, the batch on %d", hm->ctx->device, b->ctx->device);
+	firing_bind(b, hm, opt);
+	return SMHV_OK;
+}
+
+extern "C" SMHV_API int smhv_pipeline_set_firing(smhv_pipeline *p, smhv_heightmap *hm, const smhv_firing_options *opt) {
+	if (!p) return fail(SMHV_E_INVALID, "pipeline_set_firing: null pipeline");
+	CTX_OPEN(p->ctx);
+	int rc = check_firing_options(opt);
+	if (rc) return rc;
+	if (hm && hm->ctx->device != p->ctx->device) return fail(SMHV_E_INVALID, "pipeline_set_firing: the heightmap lives on device %d, the pipeline on %d", hm->ctx->device, p->ctx->device);
+	p->fire_opt = firing_opts(opt);
+	if (p->fire_hm != hm) {
+		hm_retain(hm);
+		smhv_heightmap *old = p->fire_hm;
+		p->fire_hm = hm;
+		hm_release(old);                                      // (the slots' batches keep their own references of what they ran with)
+	}
+	return SMHV_OK;
+}
+
+extern "C" SMHV_API int smhv_batch_read_firing(smhv_batch *b, uint32_t first, uint32_t n, smhv_firing_result *out) {
+	if (!b || !out || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_read_firing: bad arguments");
+	if (!b->d_firing) return fail(SMHV_E_STATE, "batch_read_firing: no run of this batch had SMHV_STAGE_FIRING");
+	HIPCHK(hipSetDevice(b->ctx->device));
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(out, b->d_firing + first, sizeof(smhv_firing_result) * n, hipMemcpyDeviceToHost));
+	return SMHV_OK;
+}
+
+extern "C" SMHV_API int smhv_batch_firing_ptr(smhv_batch *b, void **d_firing) {
+	if (!b || !d_firing) return fail(SMHV_E_INVALID, "batch_firing_ptr: null argument");
+	if (!b->d_firing) return fail(SMHV_E_STATE, "batch_firing_ptr: no run of this batch had SMHV_STAGE_FIRING");
+	*d_firing = b->d_firing;
+	return SMHV_OK;
+}
+
+extern "C" SMHV_API int smhv_firing_solutions(smhv_ctx *c, const smhv_line *lines, uint32_t n, const double *mpx, const uint32_t minimap[4],
+                                              const smhv_heightmap *hm, const smhv_firing_options *opt, smhv_firing *out) {
+	if (!c || (n && (!lines || !out))) return fail(SMHV_E_INVALID, "firing_solutions: null argument");
+	CTX_OPEN(c);
+	int rc = check_firing_options(opt);
+	if (rc) return rc;
+	if (n == 0) return SMHV_OK;
+	if (hm && hm->ctx->device != c->device) return fail(SMHV_E_INVALID, "firing_solutions: the heightmap lives on device %d, the context on %d", hm->ctx->device, c->device);
+	HIPCHK(hipSetDevice(c->device));
+	const smhv_firing_options o = firing_opts(opt);
+	FiringRun r;
+	firing_run_params(hm, &o, &r);
+	const uint32_t mm0[4] = {0, 0, 0, 0};
+	const size_t in_bytes = ((sizeof(smhv_line) * (size_t)n + 255u) & ~(size_t)255u), bytes = in_bytes + sizeof(smhv_firing) * (size_t)n;
+	std::lock_guard<std::mutex> lk(c->fire_mu);
+	if (c->fire_cap < bytes) {
+		if (c->d_fire) (void)hipFree(c->d_fire);
+		if (c->h_fire) (void)hipHostFree(c->h_fire);
+		c->d_fire = c->h_fire = nullptr; c->fire_cap = 0;
+		HIPCHK(hipMalloc((void **)&c->d_fire, bytes));
+		HIPCHK(hipHostMalloc((void **)&c->h_fire, bytes));
+		c->fire_cap = bytes;
+	}
+	memcpy(c->h_fire, lines, sizeof(smhv_line) * (size_t)n);
+	HIPCHK(hipMemcpyAsync(c->d_fire, c->h_fire, sizeof(smhv_line) * (size_t)n, hipMemcpyHostToDevice, c->s_main));
+	HIPCHK(launch_firing_lines(r, (const smhv_line *)c->d_fire, n, mpx ? 1u : 0u, mpx ? *mpx : 0.0, minimap ? 1u : 0u, minimap ? minimap : mm0,
+	                           (smhv_firing *)(c->d_fire + in_bytes), c->s_main));
+	HIPCHK(hipMemcpyAsync(c->h_fire + in_bytes, c->d_fire + in_bytes, sizeof(smhv_firing) * (size_t)n, hipMemcpyDeviceToHost, c->s_main));
+	HIPCHK(wait_stream(c->s_main));
+	memcpy(out, c->h_fire + in_bytes, sizeof(smhv_firing) * (size_t)n);
 	return SMHV_OK;
 }

@@ -220,6 +220,20 @@ class HipVision:
         L.check(self._lib.smhv_trait_times(self._ctx, ns, calls, int(bool(reset))))
         return {k: (int(ns[i]) / 1e6, int(calls[i])) for i, k in enumerate(self.TRAIT_CALLS)}
 
+    def firing_solutions(self, lines, mpx=None, minimap=None, heightmap=None, fit_to_minimap=True, viewport=None):
+        """Firing solutions of explicit lines in map-ROI coordinates (smhv_firing_solutions: markers::draw of detected and custom
+        markers).  lines: float32 [n, 4] (x0, y0, x1, y1); mpx: the frame's meters per pixel or None; minimap: (left, right,
+        top, bottom) or None; heightmap: a Heightmap or None; viewport: None or (scale_w, scale_h, top_left_x, top_left_y).
+        -> numpy structured array [n] of smhv_firing (meters, alt_delta, mils[2], bearing[2], source)."""
+        ln = np.ascontiguousarray(np.asarray(lines, np.float32).reshape(-1, 4))
+        n = ln.shape[0]
+        out = (L.Firing * max(n, 1))()
+        opt = L.firing_options(fit_to_minimap, viewport)
+        m = C.byref(C.c_double(float(mpx))) if mpx is not None else None
+        mm = (C.c_uint32 * 4)(*[int(v) for v in minimap]) if minimap is not None else None
+        L.check(self._lib.smhv_firing_solutions(self._ctx, ln.ctypes.data, n, m, mm, heightmap._hm if heightmap is not None else None, C.byref(opt), out))
+        return np.frombuffer(out, L.firing_dtype(), count=n).copy()
+
     def debug_marker_table(self):
         bits = np.empty((1 << 24) // 32, np.uint32)
         L.check(self._lib.smhv_debug_marker_table(self._ctx, bits.ctypes.data))
