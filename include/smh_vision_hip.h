@@ -512,6 +512,45 @@ SMHV_API int smhv_batch_firing_ptr(smhv_batch *b, void **d_firing);
 SMHV_API int smhv_firing_solutions(smhv_ctx *ctx, const smhv_line *lines, uint32_t n, const double *mpx, const uint32_t minimap[4],
                                    const smhv_heightmap *hm, const smhv_firing_options *opt, smhv_firing *out);
 
+/* ---- heightmap overlay: the colour map drawn over the minimap --------------------------------------------------------
+ * The picture the app shows when a heightmap is lined up with the minimap: the ui_map drawn with nearest filtering
+ * (src/ui/map.rs:250-256), then the heightmap's colour map stretched over the minimap rectangle with linear filtering, tinted
+ * [1, 1, 1, 0.25] (heightmaps::render_overlay, src/ui/heightmaps.rs:794-826).  The output is an image in ui_map pixel space: the
+ * ui_map as the app shows it at viewport scale 1, w x h RGBA8.  The viewport fields of smhv_firing_options do not apply to it;
+ * only flags does (SMHV_FIRING_BOUNDS_OFFSET = "fit to minimap" off).  GL rasterisation and filtering are not bit-reproducible,
+ * so the library pins one exact restatement of the draw: every operation f32, left to right, unfused.  Inputs: U = the frame's
+ * ui_map (w x h RGBA8, grayscale or colour as the run produced it); mm = {left, right, top, bottom}, the frame's minimap
+ * rectangle (u32); C = the colour map, W x H RGBA8, byte-equal to smhv_heightmap_color_map; b00, b01 = bounds[0], bounds[1] as f32.
+ *   1. Offset: (0, 0) ("fit", the default); with SMHV_FIRING_BOUNDS_OFFSET off.x = b00 * ((float)(right - left) / ((float)W + b00)),
+ *      off.y = b01 * ((float)(bottom - top) / ((float)H + b01)) (heightmaps.rs:802-808 at scale 1; right - left in u32).
+ *   2. Quad (imgui's Image at the cursor, bottom right = min + size): x0 = (float)left + off.x, y0 = (float)top + off.y,
+ *      sx = (float)right - x0, sy = (float)bottom - y0, x1 = x0 + sx, y1 = y0 + sy.
+ *   3. Coverage: pixel (x, y) of U, centre cx = x + 0.5f, cy = y + 0.5f, is covered iff x0 <= cx && cx < x1 && y0 <= cy && cy < y1
+ *      (half-open; NaN compares false, so W + b00 == 0 or a degenerate quad covers nothing).  Only pixels inside U are written.
+ *   4. Sampling (GL_LINEAR, no mipmaps): s = ((cx - x0) / sx) * (float)W - 0.5f, i = floorf(s), fx = s - i; t = ((cy - y0) / sy) *
+ *      (float)H - 0.5f, j = floorf(t), fy = t - j.  Taps i, i+1 and j, j+1, each clamped to the image (clamp to edge: for texture
+ *      coordinates in [0, 1] clamp and mirrored wrap give the same taps; this library states clamp).  Per channel, C as f32 in
+ *      0..255, gx = 1.0f - fx, gy = 1.0f - fy: top = C[j][i]*gx + C[j][i+1]*fx, bot = C[j+1][i]*gx + C[j+1][i+1]*fx, c = top*gy + bot*fy.
+ *   5. Blend (imgui's alpha blending; the tint alpha as imgui stores it, 0.25f * 255 + 0.5 truncated = 64; every colour-map texel
+ *      is opaque): A = 64.0f / 255.0f, B = 1.0f - A; for R, G, B  o = c*A + u*B (u = U's channel), byte = (uint8_t)fminf(o + 0.5f,
+ *      255.0f); alpha = 255.
+ *   6. Uncovered pixels keep U's bytes; an open frame without a minimap rectangle is U unchanged (the app draws no overlay then,
+ *      heightmaps.rs:797). */
+#define SMHV_STAGE_HEIGHTMAP_OVERLAY 0x100u /* smhv_batch_run / smhv_pipeline_submit: write the overlay slab.  Needs SMHV_STAGE_UI_MAP,
+                                               SMHV_STAGE_MINIMAP and a heightmap bound with smhv_batch_set_firing /
+                                               smhv_pipeline_set_firing (the same binding and rule as SMHV_STAGE_FIRING); without them
+                                               the call returns SMHV_E_INVALID and enqueues nothing.  Not in SMHV_STAGE_ALL.  The
+                                               heightmap's colour table is built by its first overlay (that call synchronises once). */
+#define SMHV_IMAGE_HEIGHTMAP_OVERLAY 101 /* smhv_batch_read_image: the overlay of a frame, w x h RGBA8 (100 = the ui_map) */
+/* The batch's overlay slab: one image per frame with the ui slab's layout (smhv_batch_layout ui_pitch / ui_stride / ui_offset),
+ * allocated by the first run with SMHV_STAGE_HEIGHTMAP_OVERLAY; such a run writes every open frame and leaves closed frames alone.
+ * Device address (SMHV_E_STATE before the first such run; so is smhv_batch_read_image with SMHV_IMAGE_HEIGHTMAP_OVERLAY). */
+SMHV_API int smhv_batch_overlay_ptr(smhv_batch *b, void **d_overlay);
+/* The per-call path: the overlay of the context's current frame -- the ui_map smhv_crop_to_map left on the device and the rectangle
+ * its walk found (what smhv_find_minimap returns) -- w x h RGBA8 into host memory.  hm required, opt NULL = defaults.  On the
+ * context's stream; SMHV_E_INVALID before load_frame / crop_to_map, SMHV_E_STATE when the map is closed. */
+SMHV_API int smhv_heightmap_overlay(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_firing_options *opt, uint8_t *rgba);
+
 #ifdef __cplusplus
 }
 #endif

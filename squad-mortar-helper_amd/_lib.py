@@ -18,10 +18,12 @@ STAGE_MINIMAP = 0x10
 STAGE_EXACT_STATS = 0x20
 STAGE_LSD_HELPERS = 0x40
 STAGE_FIRING = 0x80                        # firing solutions (needs STAGE_MARKERS; the heightmap branch needs STAGE_MINIMAP)
+STAGE_HEIGHTMAP_OVERLAY = 0x100            # the heightmap's colours over the ui_map (needs STAGE_UI_MAP, STAGE_MINIMAP, a bound heightmap)
 FIRING_BOUNDS_OFFSET = 1                   # smhv_firing_options.flags: the app's "fit to minimap" switched off
 FIRING_NONE, FIRING_SCALES, FIRING_HEIGHTMAP = 0, 1, 2   # smhv_firing.source
 VIEW_NONE, VIEW_OCR_INPUT, VIEW_FIND_SCALES_INPUT, VIEW_LSD_PREPROCESS, VIEW_LSD_INPUT, VIEW_CROPPED_BRQ = range(6)
 IMAGE_UI_MAP = 100
+IMAGE_HEIGHTMAP_OVERLAY = 101
 
 E_INVALID, E_GEOMETRY, E_HIP, E_NO_DEVICE, E_STATE = -1, -2, -3, -4, -5
 FRAME_OK, FRAME_LSD_STUCK = 0, 1          # smhv_frame_result.status
@@ -168,6 +170,8 @@ SIGNATURES = {
     "smhv_batch_firing_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "smhv_firing_solutions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_void_p,
                                         C.POINTER(FiringOptions), C.POINTER(Firing)]),
+    "smhv_batch_overlay_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smhv_heightmap_overlay": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FiringOptions), C.c_void_p]),
 }
 
 

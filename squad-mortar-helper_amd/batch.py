@@ -161,9 +161,19 @@ class FrameBatch:
         L.check(self._lib.smhv_batch_firing_ptr(self._b, C.byref(d)))
         return d.value or 0
 
+    def read_overlay(self, frame):
+        """Synchronising host copy of a frame's heightmap overlay (STAGE_HEIGHTMAP_OVERLAY) -> uint8 [h, w, 4] RGBA."""
+        return self.read_image(L.IMAGE_HEIGHTMAP_OVERLAY, frame)
+
+    def overlay_ptr(self):
+        """Device address of the overlay slab (the ui slab's layout: layout.ui_pitch / ui_stride / ui_offset)."""
+        d = C.c_void_p()
+        L.check(self._lib.smhv_batch_overlay_ptr(self._b, C.byref(d)))
+        return d.value or 0
+
     def read_image(self, which, frame):
         x, y, w, h = self.roi
-        if which == L.IMAGE_UI_MAP:
+        if which in (L.IMAGE_UI_MAP, L.IMAGE_HEIGHTMAP_OVERLAY):
             out = np.empty((h, w, 4), np.uint8)
         elif which == L.VIEW_LSD_INPUT:
             out = np.empty((h, w), np.uint8)

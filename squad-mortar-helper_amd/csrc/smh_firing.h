@@ -31,6 +31,24 @@ __device__ __forceinline__ int32_t round_i32(double v) {
 	return (int32_t)r;
 }
 
+// The heightmap's rectangle on the map (src/ui/markers.rs:37-58 == src/ui/heightmaps.rs:802-815): the minimap rectangle mm =
+// {left, right, top, bottom} through the viewport (scale sw, sh; top left tx, ty), its top left moved by bounds[0] when "fit to
+// minimap" is off (SMHV_FIRING_BOUNDS_OFFSET) -> {left, top, right, bottom} in f32.  The overlay (k_hm_overlay) passes sw = sh = 1,
+// tx = ty = 0: (float)v * 1.0f + 0.0f is (float)v.
+struct HmRect { float l, t, r, b; };
+__device__ __forceinline__ HmRect hm_rect(const uint32_t mm[4], uint32_t flags, float b0x, float b0y, uint32_t hm_w, uint32_t hm_h, float sw, float sh,
+                                          float tx, float ty) {
+	float off0 = 0.0f, off1 = 0.0f;
+	if (flags & SMHV_FIRING_BOUNDS_OFFSET) {
+		off0 = b0x * ((float)(mm[1] - mm[0]) / ((float)hm_w + b0x)) * sw;
+		off1 = b0y * ((float)(mm[3] - mm[2]) / ((float)hm_h + b0y)) * sh;
+	}
+	HmRect q;
+	q.l = ((float)mm[0] * sw + tx) + off0; q.t = ((float)mm[2] * sh + ty) + off1;
+	q.r = (float)mm[1] * sw + tx; q.b = (float)mm[3] * sh + ty;
+	return q;
+}
+
 // One line.  has_mm / mm: the frame's minimap rectangle {left, right, top, bottom}; met: the record's meters (valid iff has_mpx).
 // Both heightmap texels of the lane are loaded together, with no dependent chain between them.
 __device__ __forceinline__ smhv_firing firing_line(const FiringRun &r, bool has_mm, const uint32_t mm[4], smhv_line ln, bool has_mpx, double met) {
@@ -41,13 +59,8 @@ __device__ __forceinline__ smhv_firing firing_line(const FiringRun &r, bool has_
 	bool hm_ok = false;
 	double hm_m = 0.0, alt = 0.0;
 	if (has_mm && r.hm) {
-		float off0 = 0.0f, off1 = 0.0f;
-		if (r.flags & SMHV_FIRING_BOUNDS_OFFSET) {
-			off0 = r.b0x * ((float)(mm[1] - mm[0]) / ((float)r.hm_w + r.b0x)) * r.sw;
-			off1 = r.b0y * ((float)(mm[3] - mm[2]) / ((float)r.hm_h + r.b0y)) * r.sh;
-		}
-		const float rl = ((float)mm[0] * r.sw + r.tx) + off0, rt = ((float)mm[2] * r.sh + r.ty) + off1;
-		const float rr = (float)mm[1] * r.sw + r.tx, rb = (float)mm[3] * r.sh + r.ty;
+		const HmRect q = hm_rect(mm, r.flags, r.b0x, r.b0y, r.hm_w, r.hm_h, r.sw, r.sh, r.tx, r.ty);
+		const float rl = q.l, rt = q.t, rr = q.r, rb = q.b;
 		const double rw = (double)(rr - rl), rh = (double)(rb - rt);
 		const double x0 = (((double)p0x - (double)rl) / rw) * (double)r.hm_w, y0 = (((double)p0y - (double)rt) / rh) * (double)r.hm_h;
 		const double x1 = (((double)p1x - (double)rl) / rw) * (double)r.hm_w, y1 = (((double)p1y - (double)rt) / rh) * (double)r.hm_h;

@@ -159,6 +159,19 @@ struct FiringRun {
 	uint32_t pad;
 };
 static_assert(sizeof(FiringRun) == 64, "one 64-byte block per run");
+// SMHV_STAGE_HEIGHTMAP_OVERLAY / smhv_heightmap_overlay (k_hm_overlay): the heightmap's colours drawn over the ui_map of n frames.
+// Launch arguments (taken by value at the launch: a submission in flight keeps its own); the slabs have the ui slab's layout.
+struct OverlayRun {
+	const uint8_t *ui;                   // the ui slab, frame 0
+	uint8_t *out;                        // the overlay slab, frame 0
+	const FrameAux *aux;                 // per frame: open (the record's map_open is written after the overlay has run)
+	const smhv_frame_result *res;        // per frame: has_minimap, minimap (written by k_find_minimap before the overlay)
+	const uint16_t *hm;                  // heightmap texels, row-major
+	const uint32_t *lut;                 // 65,536 RGBA8 colours: lut[v] = the colour map's colour of a texel v (smh_misc.hip, k_hm_lut)
+	uint32_t hm_w, hm_h;
+	float b0x, b0y;                      // bounds[0] as f32
+	uint32_t flags;                      // SMHV_FIRING_BOUNDS_OFFSET
+};
 // ---- the mask as the streaming passes leave it for the line search (round 6) -------------------------------------------------
 // A marker mask is 1-4 % non-empty, and what the search keeps in LDS is its non-empty 32 x 8 px tiles.  Finding them in the
 // row-major bit rows meant walking the bounding box of the set bits: (tile rows x tile columns) x 16 strided dword loads, ~68 KB
@@ -370,6 +383,10 @@ hipError_t launch_scales_finalize(const Geom &g, const Buffers &b, uint32_t n, u
 hipError_t launch_firing_lines(const FiringRun &r, const smhv_line *lines, uint32_t n, uint32_t has_mpx, double mpx, uint32_t has_minimap,
                                const uint32_t minimap[4], smhv_firing *out, hipStream_t s);
 hipError_t launch_heightmap_color_map(const uint16_t *hm, uint64_t n, uint32_t *mm, uint32_t *rgba, hipStream_t s);
+// the overlay: the colour table of a heightmap (lut: 65,536 words; mm as above), and the composite over n frames of a slab
+#define SMH_HM_LUT_ENTRIES 65536u
+hipError_t launch_heightmap_lut(const uint16_t *hm, uint64_t n, uint32_t *mm, uint32_t *lut, hipStream_t s);
+hipError_t launch_hm_overlay(const Geom &g, const OverlayRun &r, uint32_t n, hipStream_t s);
 // which: SMHV_VIEW_*; isolated: LSDPreprocess shows the marker-isolated crop (after isolate_map_markers)
 hipError_t launch_debug_view(const Geom &g, const Buffers &b, uint32_t frame, int which, int isolated, uint8_t *d_rgba, hipStream_t s);
 hipError_t launch_marker_table(uint32_t *d_bits, hipStream_t s);

@@ -4,6 +4,7 @@
 //   k_finalize     derived marker outputs                                     (src/ui/mod.rs:131-140, markers.rs:98)
 //   k_firing_lines firing solutions of explicit lines                         (src/ui/markers.rs:23-200; smh_firing.h)
 //   k_hm_minmax / k_hm_color  heightmap overlay colours                       (src/ui/heightmaps.rs:169-207)
+//   k_hm_lut / k_hm_overlay   the overlay drawn over the ui_map               (src/ui/map.rs:250-256, heightmaps.rs:794-826)
 //   k_debug_view   DebugView images                                           (vision-cpu/src/lib.rs:451-460)
 //   k_marker_table exhaustive colour-predicate table (test support)
 //   k_crc32        CRC-32 of a frame in HBM for the capture hand-off          (src/capture.rs:44-47)
@@ -187,6 +188,110 @@ __global__ void __launch_bounds__(256) k_hm_color(const uint16_t *__restrict__ h
 	}
 }
 
+// ------------------------------------------------------------------------------------------------
+// The heightmap overlay (src/ui/map.rs:250-256, src/ui/heightmaps.rs:794-826; the f32 restatement is spelt out in
+// include/smh_vision_hip.h).  A texel's colour depends on its value and the map's max / min only, so the colour map is a table of
+// 65,536 colours (256 KB: it stays in L2) built once per heightmap, and the overlay gathers u16 texels through it.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_hm_lut(const uint32_t *mm, uint32_t *__restrict__ lut) {
+	const uint32_t mx = mm[0], mn = mm[1];
+	const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+	// (values outside [min, max] occur in no texel: their entries are never read, and would not fit a byte per channel)
+	lut[v] = (v >= mn && v <= mx) ? hm_color(v, mx, mn) : 0u;
+}
+
+// The composite's arithmetic for one pixel: GL_LINEAR (clamp to edge) of the colour map at the pixel centre from the four
+// taps' colours, then imgui's alpha blend with the tint's alpha 64 / 255 over the ui_map pixel u.  Every operation f32, left to
+// right, unfused (-ffp-contract=off).
+__device__ __forceinline__ uint32_t hm_blend(uint32_t c00, uint32_t c01, uint32_t c10, uint32_t c11, float fx, float fy, float gy, uint32_t u) {
+	const float gx = 1.0f - fx;
+	const float A = 64.0f / 255.0f, B = 1.0f - A;
+	uint32_t o = 0xFF000000u;
+#pragma unroll
+	for (uint32_t k = 0; k < 3; ++k) {
+		const uint32_t sh = 8u * k;
+		const float top = (float)((c00 >> sh) & 255u) * gx + (float)((c01 >> sh) & 255u) * fx;
+		const float bot = (float)((c10 >> sh) & 255u) * gx + (float)((c11 >> sh) & 255u) * fx;
+		const float c = top * gy + bot * fy;
+		const float v = c * A + (float)((u >> sh) & 255u) * B;
+		o |= (uint32_t)fminf(v + 0.5f, 255.0f) << sh;
+	}
+	return o;
+}
+
+// n frames of a slab (grid: row blocks x frames), the padded rows of the ui slab's layout (whole 64-pixel spans: rows are padded
+// to 16 quads).  A wave takes 64 consecutive pixels of a row, one per lane, and every lane OV_PX pixels 256 apart at a time: the
+// ui_map loads and overlay stores are coalesced 256-byte spans, and the chain of a covered pixel -- ui_map, then its four texels,
+// then their four colours -- runs for OV_PX pixels side by side (one pixel per lane and step measured 3.0-3.7 ms per 256 x 1080p
+// launch: the dependent gathers' latency, not the bytes).  Closed frames are left alone; pixels outside the rectangle (all of
+// them in an open frame without one) are a copy of the ui_map.
+#define SMH_OVL_ROWS 4u
+#define SMH_OVL_PX 4u
+__global__ void __launch_bounds__(256) k_hm_overlay(Geom g, OverlayRun r) {
+	const uint32_t f = blockIdx.y;
+	if (!r.aux[f].open) return;
+	const smhv_frame_result *res = &r.res[f];
+	const bool has_mm = res->has_minimap != 0u;
+	const uint32_t mm[4] = {res->minimap[0], res->minimap[1], res->minimap[2], res->minimap[3]};
+	// the quad: imgui's Image at the cursor (heightmaps.rs:802-815 at viewport scale 1), bottom right = top left + size
+	const HmRect q = hm_rect(mm, r.flags, r.b0x, r.b0y, r.hm_w, r.hm_h, 1.0f, 1.0f, 0.0f, 0.0f);
+	const float x0 = q.l, y0 = q.t;
+	const float sx = q.r - x0, sy = q.b - y0;
+	const float x1 = x0 + sx, y1 = y0 + sy;
+	const float fw = (float)r.hm_w, fh = (float)r.hm_h;
+	const int32_t hm1 = (int32_t)r.hm_h - 1, wm1 = (int32_t)r.hm_w - 1;
+	const uint32_t pitch_px = (uint32_t)(g.ui_pitch / 4u);
+	const uint32_t yb = blockIdx.x * SMH_OVL_ROWS, ye = min(yb + SMH_OVL_ROWS, g.rh);
+	for (uint32_t y = yb; y < ye; ++y) {
+		const uint32_t *src = (const uint32_t *)(r.ui + (size_t)f * g.ui_stride + (size_t)y * g.ui_pitch);
+		uint32_t *dst = (uint32_t *)(r.out + (size_t)f * g.ui_stride + (size_t)y * g.ui_pitch);
+		const float cy = (float)y + 0.5f;
+		// (NaN-safe: a NaN or infinite rectangle fails one of the comparisons and covers nothing)
+		const bool row = has_mm && y0 <= cy && cy < y1;
+		const uint16_t *row_a = r.hm, *row_b = r.hm;
+		float fy = 0.0f, gy = 1.0f;
+		if (row) {
+			const float t = ((cy - y0) / sy) * fh - 0.5f;
+			const float j = floorf(t);
+			fy = t - j; gy = 1.0f - fy;
+			const int32_t jj = (int32_t)fmaxf(fminf(j, fh), -1.0f);
+			const uint32_t ja = (uint32_t)min(max(jj, 0), hm1), jb = (uint32_t)min(max(jj + 1, 0), hm1);
+			row_a = r.hm + (size_t)ja * r.hm_w; row_b = r.hm + (size_t)jb * r.hm_w;
+		}
+		for (uint32_t p0 = threadIdx.x; p0 < pitch_px; p0 += SMH_OVL_PX * blockDim.x) {
+			uint32_t v[SMH_OVL_PX], ia[SMH_OVL_PX], ib[SMH_OVL_PX], t[SMH_OVL_PX][4];
+			float fx[SMH_OVL_PX];
+			bool cov[SMH_OVL_PX];
+#pragma unroll
+			for (uint32_t k = 0; k < SMH_OVL_PX; ++k) {
+				const uint32_t px = p0 + k * blockDim.x;
+				v[k] = px < pitch_px ? src[px] : 0u;
+				const int32_t x = (int32_t)px - (int32_t)g.m_xoff;      // ROI x
+				const float cx = (float)x + 0.5f;
+				cov[k] = row && px < pitch_px && x >= 0 && x < (int32_t)g.rw && x0 <= cx && cx < x1;
+				const float s = ((cx - x0) / sx) * fw - 0.5f;
+				const float i = floorf(s);
+				fx[k] = s - i;
+				const int32_t ii = (int32_t)fmaxf(fminf(i, fw), -1.0f);   // (s is finite for a covered pixel; the clamp keeps any value in bounds)
+				ia[k] = (uint32_t)min(max(ii, 0), wm1); ib[k] = (uint32_t)min(max(ii + 1, 0), wm1);
+			}
+			// every pixel's four texels, then their colours: independent loads, issued back to back
+#pragma unroll
+			for (uint32_t k = 0; k < SMH_OVL_PX; ++k)
+				if (cov[k]) { t[k][0] = row_a[ia[k]]; t[k][1] = row_a[ib[k]]; t[k][2] = row_b[ia[k]]; t[k][3] = row_b[ib[k]]; }
+#pragma unroll
+			for (uint32_t k = 0; k < SMH_OVL_PX; ++k)
+				if (cov[k]) { t[k][0] = r.lut[t[k][0]]; t[k][1] = r.lut[t[k][1]]; t[k][2] = r.lut[t[k][2]]; t[k][3] = r.lut[t[k][3]]; }
+#pragma unroll
+			for (uint32_t k = 0; k < SMH_OVL_PX; ++k) {
+				const uint32_t px = p0 + k * blockDim.x;
+				if (cov[k]) v[k] = hm_blend(t[k][0], t[k][1], t[k][2], t[k][3], fx[k], fy, gy, v[k]);
+				if (px < pitch_px) dst[px] = v[k];
+			}
+		}
+	}
+}
+
 hipError_t launch_firing_lines(const FiringRun &r, const smhv_line *lines, uint32_t n, uint32_t has_mpx, double mpx, uint32_t has_minimap,
                                const uint32_t minimap[4], smhv_firing *out, hipStream_t s) {
 	hipLaunchKernelGGL(k_firing_lines, dim3((n + 255u) / 256u), dim3(256), 0, s, r, lines, n, has_mpx, mpx, has_minimap, minimap[0], minimap[1], minimap[2],
@@ -194,7 +299,7 @@ hipError_t launch_firing_lines(const FiringRun &r, const smhv_line *lines, uint3
 	return hipGetLastError();
 }
 
-hipError_t launch_heightmap_color_map(const uint16_t *hm, uint64_t n, uint32_t *mm, uint32_t *rgba, hipStream_t s) {
+static hipError_t launch_hm_minmax(const uint16_t *hm, uint64_t n, uint32_t *mm, hipStream_t s) {
 	static const uint32_t init[2] = {0u, 0xFFFFFFFFu};
 	hipError_t e = hipMemcpyAsync(mm, init, sizeof init, hipMemcpyHostToDevice, s);
 	if (e != hipSuccess) return e;
@@ -205,10 +310,26 @@ hipError_t launch_heightmap_color_map(const uint16_t *hm, uint64_t n, uint32_t *
 	uint64_t blocks = (quads + 255u) / 256u;
 	if (blocks > (uint64_t)cus * 8u) blocks = (uint64_t)cus * 8u;     // grid-stride beyond eight workgroups per CU
 	hipLaunchKernelGGL(k_hm_minmax, dim3((uint32_t)blocks), dim3(256), 0, s, hm, n, mm);
-	e = hipGetLastError();
+	return hipGetLastError();
+}
+
+hipError_t launch_heightmap_color_map(const uint16_t *hm, uint64_t n, uint32_t *mm, uint32_t *rgba, hipStream_t s) {
+	hipError_t e = launch_hm_minmax(hm, n, mm, s);
 	if (e != hipSuccess) return e;
 	const uint64_t pairs = (n + 1u) / 2u;
 	hipLaunchKernelGGL(k_hm_color, dim3((uint32_t)((pairs + 255u) / 256u)), dim3(256), 0, s, hm, n, (const uint32_t *)mm, rgba);
+	return hipGetLastError();
+}
+
+hipError_t launch_heightmap_lut(const uint16_t *hm, uint64_t n, uint32_t *mm, uint32_t *lut, hipStream_t s) {
+	hipError_t e = launch_hm_minmax(hm, n, mm, s);
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(k_hm_lut, dim3(SMH_HM_LUT_ENTRIES / 256u), dim3(256), 0, s, (const uint32_t *)mm, lut);
+	return hipGetLastError();
+}
+
+hipError_t launch_hm_overlay(const Geom &g, const OverlayRun &r, uint32_t n, hipStream_t s) {
+	hipLaunchKernelGGL(k_hm_overlay, dim3((g.rh + SMH_OVL_ROWS - 1u) / SMH_OVL_ROWS, n), dim3(256), 0, s, g, r);
 	return hipGetLastError();
 }
 

@@ -229,6 +229,8 @@ struct smhv_batch {
 	FiringRun *d_fire_run = nullptr;
 	struct FireStage { FiringRun *h = nullptr; hipEvent_t done = nullptr; };
 	std::vector<FireStage> fire_stage;
+	// SMHV_STAGE_HEIGHTMAP_OVERLAY: the overlay slab, the ui slab's layout (allocated by the first run that asks for it)
+	uint8_t *d_overlay = nullptr;
 };
 
 // a device copy of a heightmap (smhv_heightmap_create); batches and pipelines that have it bound hold references of their own
@@ -239,6 +241,10 @@ struct smhv_heightmap {
 	int32_t bounds[4] = {0, 0, 0, 0};
 	float scale[3] = {0.0f, 0.0f, 0.0f};
 	std::atomic<int> refs{1};
+	// the overlay's colour table (SMH_HM_LUT_ENTRIES RGBA8 words, then {max, min}): built by the first overlay that needs it, under
+	// lut_mu (pipelines and contexts may share one heightmap), never rebuilt
+	mutable std::mutex lut_mu;
+	mutable std::atomic<uint32_t *> d_lut{nullptr};
 };
 static void hm_retain(smhv_heightmap *hm) { if (hm) hm->refs.fetch_add(1, std::memory_order_relaxed); }
 static void hm_release(smhv_heightmap *hm);
@@ -615,7 +621,7 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	if (b->ctx) (void)hipSetDevice(b->ctx->device);
 	(void)hipDeviceSynchronize();
 	void *ptrs[] = {b->d_ui, b->d_mask, b->d_bits, b->d_tiled, b->d_occ, b->d_ocr, b->d_scales, b->d_aux, b->d_results, b->d_anchors, b->d_bars, b->d_farm,
-	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run};
+	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run, b->d_overlay};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	if (b->h_err) (void)hipHostFree(b->h_err);
@@ -711,6 +717,7 @@ static void hm_release(smhv_heightmap *hm) {
 	(void)hipSetDevice(hm->ctx->device);
 	(void)hipDeviceSynchronize();
 	if (hm->d) (void)hipFree(hm->d);
+	if (uint32_t *l = hm->d_lut.load(std::memory_order_acquire)) (void)hipFree(l);
 	ctx_release(hm->ctx);
 	delete hm;
 }
@@ -786,6 +793,67 @@ static int firing_upload(smhv_batch *b, hipStream_t sb) {
 	return SMHV_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// the heightmap overlay (k_hm_overlay, smh_misc.hip): the colour table, the slab, the launch arguments
+// ------------------------------------------------------------------------------------------------
+// The heightmap's colour table, built on first use: a stream of its own and one wait for it (no device-wide synchronize: a
+// frame-granular pipeline may have counted a submission it has not published yet).
+static int hm_lut(const smhv_heightmap *hm, const uint32_t **lut) {
+	uint32_t *l = hm->d_lut.load(std::memory_order_acquire);
+	if (!l) {
+		std::lock_guard<std::mutex> lk(hm->lut_mu);
+		l = hm->d_lut.load(std::memory_order_relaxed);
+		if (!l) {
+			HIPCHK(hipSetDevice(hm->ctx->device));
+			hipStream_t s = nullptr;
+			hipError_t e = hipMalloc((void **)&l, sizeof(uint32_t) * (SMH_HM_LUT_ENTRIES + 4u));
+			if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+			if (e == hipSuccess) e = launch_heightmap_lut(hm->d, (uint64_t)hm->w * hm->h, l + SMH_HM_LUT_ENTRIES, l, s);
+			if (e == hipSuccess) e = hipStreamSynchronize(s);
+			if (s) (void)hipStreamDestroy(s);
+			if (e != hipSuccess) {
+				if (l) (void)hipFree(l);
+				return fail(SMHV_E_HIP, "heightmap overlay colour table: %s", hipGetErrorString(e));
+			}
+			hm->d_lut.store(l, std::memory_order_release);
+		}
+	}
+	*lut = l;
+	return SMHV_OK;
+}
+
+// The batch's overlay slab (zeroed on `s` when the first run that asks for it allocates it) and the launch arguments of a run:
+// the heightmap and flags as bound now, the records at `res`.
+static int overlay_prepare(smhv_batch *b, const smhv_heightmap *hm, uint32_t flags, const smhv_frame_result *res, hipStream_t s, OverlayRun *r) {
+	const uint32_t *lut = nullptr;
+	int rc = hm_lut(hm, &lut);
+	if (rc) return rc;
+	if (!b->d_overlay) {
+		const size_t bytes = b->g.ui_stride * (size_t)b->max_frames;
+		hipError_t e = hipMalloc((void **)&b->d_overlay, bytes);
+		if (e == hipSuccess) e = hipMemsetAsync(b->d_overlay, 0, bytes, s);
+		if (e != hipSuccess) {
+			if (b->d_overlay) (void)hipFree(b->d_overlay);
+			b->d_overlay = nullptr;
+			return fail(SMHV_E_HIP, "overlay slab: %s", hipGetErrorString(e));
+		}
+	}
+	memset(r, 0, sizeof *r);
+	r->ui = b->d_ui; r->out = b->d_overlay; r->aux = b->d_aux; r->res = res;
+	r->hm = hm->d; r->lut = lut; r->hm_w = hm->w; r->hm_h = hm->h;
+	r->b0x = (float)hm->bounds[0]; r->b0y = (float)hm->bounds[1];
+	r->flags = flags;
+	return SMHV_OK;
+}
+
+static int check_overlay_stages(uint32_t stages, const smhv_heightmap *hm) {
+	if (!(stages & SMHV_STAGE_HEIGHTMAP_OVERLAY)) return SMHV_OK;
+	if ((stages & (SMHV_STAGE_UI_MAP | SMHV_STAGE_MINIMAP)) != (SMHV_STAGE_UI_MAP | SMHV_STAGE_MINIMAP))
+		return fail(SMHV_E_INVALID, "SMHV_STAGE_HEIGHTMAP_OVERLAY needs SMHV_STAGE_UI_MAP and SMHV_STAGE_MINIMAP");
+	if (!hm) return fail(SMHV_E_INVALID, "SMHV_STAGE_HEIGHTMAP_OVERLAY needs a heightmap (smhv_batch_set_firing / smhv_pipeline_set_firing)");
+	return SMHV_OK;
+}
+
 struct SvcPublish { SvcCtl *ctl; unsigned long long *ring; SvcSlot *slots; uint32_t slot, seq, ring_log2; const uint32_t *cull_tab; bool have_cull; hipStream_t s_pro; hipEvent_t ev_pro;
                     bool *published; };   // <- set once k_svc_publish has been enqueued (from then on the device WILL complete the submission)
 static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint32_t stages, int grayscale, uint32_t max_gap,
@@ -794,10 +862,17 @@ static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint3
 	CTX_OPEN(b->ctx);
 	if ((stages & (SMHV_STAGE_ALL | SMHV_STAGE_MINIMAP)) == 0) return fail(SMHV_E_INVALID, "no stage selected");
 	if ((stages & SMHV_STAGE_FIRING) && !(stages & SMHV_STAGE_MARKERS)) return fail(SMHV_E_INVALID, "SMHV_STAGE_FIRING needs SMHV_STAGE_MARKERS");
-	stages &= SMHV_STAGE_ALL | SMHV_STAGE_MINIMAP | SMHV_STAGE_EXACT_STATS | SMHV_STAGE_LSD_HELPERS | SMHV_STAGE_FIRING;
+	{ int rc = check_overlay_stages(stages, b->fire_hm); if (rc) return rc; }
+	// (the record kernels test single bits of the mask: the overlay's bit changes none of them)
+	stages &= SMHV_STAGE_ALL | SMHV_STAGE_MINIMAP | SMHV_STAGE_EXACT_STATS | SMHV_STAGE_LSD_HELPERS | SMHV_STAGE_FIRING | SMHV_STAGE_HEIGHTMAP_OVERLAY;
 	HIPCHK(hipSetDevice(b->ctx->device));
 	const Geom &g = b->g;
 	Buffers bf = make_buffers(b, (const uint8_t *)d_frames, 0);
+	OverlayRun orun{};
+	if (stages & SMHV_STAGE_HEIGHTMAP_OVERLAY) {
+		int rc = overlay_prepare(b, b->fire_hm, b->fire_opt.flags, bf.results, s, &orun);
+		if (rc) return rc;
+	}
 	// the helper exchange of k_lsd_tile tags its words with 16 bits of the launch epoch: start every 65,536th launch of a batch
 	// from a clean slate, so that a stale word of the launch 65,536 ago can never read as this launch's
 	if ((bf.co.epoch & 0xFFFFu) == 0u && b->d_farm) HIPCHK(hipMemsetAsync(b->d_farm, 0, sizeof(FarmFrame) * (size_t)b->max_frames, s));
@@ -868,6 +943,9 @@ static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint3
 		// ---- frame-granular: publish the frames; the service searches them and writes the records (minimap first: its kernel
 		// needs nothing of the search and the record keeps what it wrote) ----
 		if (stages & SMHV_STAGE_MINIMAP) HIPCHK(launch_find_minimap(g, bf, n, s));
+		// the overlay before the publication: a submission's completion is the service's count, and only what precedes the
+		// publication on this stream is inside it
+		if (stages & SMHV_STAGE_HEIGHTMAP_OVERLAY) HIPCHK(launch_hm_overlay(g, orun, n, s));
 		bf.rec_stages = SMH_REC_ON | (scales ? stages : (stages & ~SMHV_STAGE_SCALES));
 		bf.rec_bars = b->d_bars;
 		STAGE_BEGIN(3, s);
@@ -898,6 +976,7 @@ static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint3
 	STAGE_END(3, sl);
 	if (b->probe) { HIPCHK(hipEventRecord(b->ev_probe[2], sl)); b->probe_valid = (stages & SMHV_STAGE_MARKERS) && mflags; }
 	if (stages & SMHV_STAGE_MINIMAP) HIPCHK(launch_find_minimap(g, bf, n, sl));
+	if (stages & SMHV_STAGE_HEIGHTMAP_OVERLAY) HIPCHK(launch_hm_overlay(g, orun, n, sl));
 	STAGE_BEGIN(4, sl);
 	if (record_fused) { /* written by the search's own workgroups */ }
 	else if (scales) HIPCHK(launch_scales_finalize(g, bf, n, stages, b->d_bars, sl));
@@ -1031,9 +1110,12 @@ extern "C" SMHV_API int smhv_batch_read_image(smhv_batch *b, int which, uint32_t
 	const Geom &g = b->g;
 	HIPCHK(hipSetDevice(b->ctx->device));
 	HIPCHK(hipDeviceSynchronize());
+	if (which == SMHV_IMAGE_HEIGHTMAP_OVERLAY && !b->d_overlay) return fail(SMHV_E_STATE, "batch_read_image: no run of this batch had SMHV_STAGE_HEIGHTMAP_OVERLAY");
 	switch (which) {
 	case 100:
-		HIPCHK(hipMemcpy2D(out, (size_t)g.rw * 4, b->d_ui + frame * g.ui_stride + (size_t)g.m_xoff * 4, g.ui_pitch, (size_t)g.rw * 4, g.rh, hipMemcpyDeviceToHost));
+	case SMHV_IMAGE_HEIGHTMAP_OVERLAY:
+		HIPCHK(hipMemcpy2D(out, (size_t)g.rw * 4, (which == 100 ? b->d_ui : b->d_overlay) + frame * g.ui_stride + (size_t)g.m_xoff * 4, g.ui_pitch, (size_t)g.rw * 4,
+		                   g.rh, hipMemcpyDeviceToHost));
 		break;
 	case SMHV_VIEW_LSD_INPUT: {
 		std::lock_guard<std::mutex> lk(b->ctx->mu);
@@ -1620,9 +1702,16 @@ extern "C" SMHV_API int smhv_pipeline_submit(smhv_pipeline *p, const void *d_fra
 	CTX_OPEN(p->ctx);
 	HIPCHK(hipSetDevice(p->ctx->device));
 	const uint32_t slot = (uint32_t)(p->submitted % p->depth);
+	// the overlay's requirements, and the heightmap's colour table (its first overlay builds it), before anything is enqueued
+	if (stages & SMHV_STAGE_HEIGHTMAP_OVERLAY) {
+		int rc = check_overlay_stages(stages, p->fire_hm);
+		const uint32_t *lut = nullptr;
+		if (!rc) rc = hm_lut(p->fire_hm, &lut);
+		if (rc) return rc;
+	}
 	// the submission takes the pipeline's firing binding as it stands now (before anything of it is counted or enqueued: dropping
 	// the last reference of a heightmap synchronises the device)
-	if (stages & SMHV_STAGE_FIRING) firing_bind(p->batch[slot], p->fire_hm, &p->fire_opt);
+	if (stages & (SMHV_STAGE_FIRING | SMHV_STAGE_HEIGHTMAP_OVERLAY)) firing_bind(p->batch[slot], p->fire_hm, &p->fire_opt);
 	if (p->adaptive) { int rc = mode_control(p, n, stages, max_gap); if (rc) return rc; }
 	if (p->svc && p->mode_frame) {
 		int rc = svc_submit(p, slot, d_frames, n, stages, grayscale, max_gap, anchors, after_stream, slot_out);
@@ -2901,4 +2990,37 @@ extern "C" SMHV_API int smhv_firing_solutions(smhv_ctx *c, const smhv_line *line
 	HIPCHK(wait_stream(c->s_main));
 	memcpy(out, c->h_fire + in_bytes, sizeof(smhv_firing) * (size_t)n);
 	return SMHV_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// heightmap overlay: public entry points (smh_vision_hip.h; device code in smh_misc.hip, k_hm_overlay)
+// ------------------------------------------------------------------------------------------------
+extern "C" SMHV_API int smhv_batch_overlay_ptr(smhv_batch *b, void **d_overlay) {
+	if (!b || !d_overlay) return fail(SMHV_E_INVALID, "batch_overlay_ptr: null argument");
+	if (!b->d_overlay) return fail(SMHV_E_STATE, "batch_overlay_ptr: no run of this batch had SMHV_STAGE_HEIGHTMAP_OVERLAY");
+	*d_overlay = b->d_overlay;
+	return SMHV_OK;
+}
+
+// The current frame's ui_map (frame 0 of the single-frame batch's ui slab, written by crop_to_map's pass) and the minimap
+// rectangle of crop_to_map's walk (the minimap's own record slot, 3), composited into that batch's overlay slab on the context's
+// stream, then copied out tightly.
+extern "C" SMHV_API int smhv_heightmap_overlay(smhv_ctx *c, const smhv_heightmap *hm, const smhv_firing_options *opt, uint8_t *rgba) {
+	int rc = require_open(c, "heightmap_overlay");
+	if (rc) return rc;
+	if (!hm || !rgba) return fail(SMHV_E_INVALID, "heightmap_overlay: null argument");
+	rc = check_firing_options(opt);
+	if (rc) return rc;
+	if (hm->ctx->device != c->device) return fail(SMHV_E_INVALID, "heightmap_overlay: the heightmap lives on device %d, the context on %d", hm->ctx->device, c->device);
+	HIPCHK(hipSetDevice(c->device));
+	const smhv_firing_options o = firing_opts(opt);
+	smhv_batch *b = c->fb;
+	const Geom &g = b->g;
+	std::lock_guard<std::mutex> lk(c->fire_mu);
+	OverlayRun r;
+	rc = overlay_prepare(b, hm, o.flags, b->d_results + 3, c->s_main, &r);
+	if (rc) return rc;
+	HIPCHK(launch_hm_overlay(g, r, 1, c->s_main));
+	std::lock_guard<std::mutex> lk2(c->mu);                   // (staging slot 2: the batch read-back's)
+	return copy_image_d2h(c, 2, rgba, b->d_overlay, g.ui_pitch, (size_t)g.m_xoff * 4, (size_t)g.rw * 4, g.rh, c->s_main);
 }

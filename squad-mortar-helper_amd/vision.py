@@ -234,6 +234,17 @@ class HipVision:
         L.check(self._lib.smhv_firing_solutions(self._ctx, ln.ctypes.data, n, m, mm, heightmap._hm if heightmap is not None else None, C.byref(opt), out))
         return np.frombuffer(out, L.firing_dtype(), count=n).copy()
 
+    def heightmap_overlay(self, heightmap, fit_to_minimap=True):
+        """The heightmap's colour map drawn over the current frame's ui_map in the minimap rectangle crop_to_map found
+        (smhv_heightmap_overlay; src/ui/heightmaps.rs:794-826 at viewport scale 1) -> uint8 [h, w, 4] RGBA."""
+        if getattr(self, "_size", None) is None:
+            raise L.VisionError(L.E_INVALID, "heightmap_overlay called before load_frame")
+        _, _, rw, rh = map_bounds(*self._size)
+        out = np.empty((rh, rw, 4), np.uint8)
+        opt = L.firing_options(fit_to_minimap)
+        L.check(self._lib.smhv_heightmap_overlay(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(opt), out.ctypes.data))
+        return out
+
     def debug_marker_table(self):
         bits = np.empty((1 << 24) // 32, np.uint32)
         L.check(self._lib.smhv_debug_marker_table(self._ctx, bits.ctypes.data))
