@@ -551,6 +551,81 @@ SMHV_API int smhv_batch_overlay_ptr(smhv_batch *b, void **d_overlay);
  * context's stream; SMHV_E_INVALID before load_frame / crop_to_map, SMHV_E_STATE when the map is closed. */
 SMHV_API int smhv_heightmap_overlay(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_firing_options *opt, uint8_t *rgba);
 
+/* ---- map view: what the app's window shows, at any viewport ------------------------------------------------------------
+ * map::render (src/ui/map.rs:209-273) draws, in this order: the ui_map as a quad placed by MapViewport::calc (letter-boxed into
+ * the window, zoomed, panned; nearest filtering, map.rs:180-199, 250-254), the heightmap overlay through that viewport
+ * (heightmaps.rs:794-826), then every marker line (markers.rs:28-30, thickness 2, colours map.rs:260-267).  A render call draws
+ * that picture on the device from results that are already there -- the ui slab and the records -- into the batch's render
+ * slab: out_w x out_h RGBA8 per frame, tightly packed.  The viewport belongs to the display loop, not to the vision loop, so this
+ * is a call of its own and no stage bit; it works the same after smhv_pipeline_wait on a slot's batch, for both searches.
+ * GL's and imgui's rasterisation are not bit-reproducible, so, as for the overlay, the library pins ONE exact restatement: every
+ * operation one f32 operation, left to right, unfused.  Output pixel (X, Y), centre cx = X + 0.5f, cy = Y + 0.5f in window
+ * coordinates; U = the frame's ui_map (w x h), rec = its record; {ql, qt, qr, qb} = quad; sw, sh = viewport_scale (0 means 1, as
+ * in smhv_firing_options); tx, ty = viewport_top_left.
+ *   0. o = background.  A frame whose map is closed is background everywhere (the slab never keeps stale pixels).
+ *   1. Map quad: covered iff ql <= cx && cx < qr && qt <= cy && cy < qb (half-open; NaN covers nothing).
+ *      u = ((cx - ql) / (qr - ql)) * (float)w, ix = clamp((int)floorf(u), 0, w - 1); v = ((cy - qt) / (qb - qt)) * (float)h,
+ *      iy = clamp((int)floorf(v), 0, h - 1); o = U[iy][ix] (R, G, B; alpha 255).
+ *   2. Overlay (SMHV_RENDER_HEIGHTMAP, rec.has_minimap): R = the heightmap's rectangle WITH the viewport, exactly the firing
+ *      solutions' (see there): off = (0, 0), or with SMHV_RENDER_BOUNDS_OFFSET off.x = b00 * ((float)(right - left) / ((float)W +
+ *      b00)) * sw, the same in y; R = {(left*sw + tx) + off.x, (top*sh + ty) + off.y, right*sw + tx, bottom*sh + ty}.  Then steps
+ *      2-5 of the overlay above with x0 = R.left, y0 = R.top, sx = R.right - x0, sy = R.bottom - y0 (x1 = x0 + sx, y1 = y0 + sy)
+ *      and `o` in the place of the ui_map pixel u; alpha 255.  Coverage does not depend on step 1: the overlay is also drawn
+ *      over the background.
+ *   3. Marker lines (SMHV_RENDER_MARKERS): line i of n (rec.lines / rec.n_lines, or the explicit ones): P = (x * sw + tx,
+ *      y * sh + ty) for both ends; dx = P1.x - P0.x, dy = P1.y - P0.y; len2 = dx*dx + dy*dy; skipped unless len2 > 0.
+ *      ax = cx - P0.x, ay = cy - P0.y; t = ax*dx + ay*dy; c = ax*dy - ay*dx.  Painted iff 0 <= t && t <= len2 && c*c <= len2
+ *      (the centre within 1.0 of the segment, butt ends; no square root).  f = (float)(i + 1) / (float)n; r = (uint8_t)((1.0f -
+ *      f) * 255.0f + 0.5f), g = (uint8_t)(f * 255.0f + 0.5f), b = 0, alpha 255.  Later lines paint over earlier ones.  This is
+ *      a HARD-EDGED stroke in the place of imgui's anti-aliased one.  Text labels are not drawn (the numbers are smhv_firing's).
+ * Two identities follow: with out = (w, h), quad = {0, 0, w, h}, scale 1, top left 0 and no flags the image is the ui_map; with
+ * SMHV_RENDER_HEIGHTMAP added it is SMHV_STAGE_HEIGHTMAP_OVERLAY's image of the same heightmap, byte for byte. */
+#define SMHV_RENDER_HEIGHTMAP 1u       /* smhv_render_options.flags: draw the heightmap overlay (needs hm) */
+#define SMHV_RENDER_MARKERS 2u         /*   ... the marker lines */
+#define SMHV_RENDER_BOUNDS_OFFSET 4u   /*   ... the app's "fit to minimap" switched off (as SMHV_FIRING_BOUNDS_OFFSET) */
+#define SMHV_RENDER_MAX_LINES 256u     /* explicit lines of one smhv_render_map call */
+typedef struct {
+	uint32_t size;                       /* sizeof(smhv_render_options) */
+	uint32_t flags;                      /* SMHV_RENDER_* */
+	uint32_t out_w, out_h;               /* the window (display_size), in pixels; at most 16384 each */
+	float quad[4];                       /* {left, top, right, bottom}: the Rect MapViewport::calc returns */
+	float viewport_scale[2];             /* MapViewport::scale_factor_{w,h}; 0 = 1 */
+	float viewport_top_left[2];          /* MapViewport::top_left */
+	uint8_t background[4];               /* RGBA of pixels nothing is drawn on */
+} smhv_render_options;
+/* MapViewport::calc (src/ui/map.rs:21-77) in f32; host only, needs no device.  region = the window, map = the ui_map's size,
+ * zoom = the wheel's level (0 = none; levels above 10 zoom as 10), zoom_pos / pan_pos may be NULL (0, 0).  Fills opt->quad,
+ * opt->viewport_scale and opt->viewport_top_left and nothing else -- the two viewport fields are what smhv_firing_options takes,
+ * so the numbers and the picture use one viewport. */
+SMHV_API int smhv_map_viewport_calc(float region_w, float region_h, float map_w, float map_h, uint32_t zoom, const float zoom_pos[2],
+                                    const float pan_pos[2], smhv_render_options *opt);
+/* Draws frames [first, first + n) of the batch from the ui slab and the records as they are when `stream` reaches this point;
+ * asynchronous, on `stream`.  The image of frame f lies at d_images + f * stride of the render slab.  The slab holds the batch's
+ * whole capacity at the window's size (capacity * out_w * out_h * 4 bytes), so a batch may be rendered in parts.  It is allocated
+ * by the first render and re-allocated when a later one asks for a larger window: that call waits (host) for the batch's previous
+ * render and frees the old slab, which waits for the device to run dry; pointers handed out before are stale then and the earlier
+ * images are gone (frames the renders since have not drawn hold undefined bytes).  A render at another window size of equal or
+ * fewer bytes re-uses the slab with the new stride: images of the previous size are not readable any more.  SMHV_E_INVALID: a zero or too large out_w / out_h, a size mismatch, unknown flags, n == 0 or first + n beyond the
+ * batch's capacity, SMHV_RENDER_HEIGHTMAP without hm, a quad edge that is not finite (MapViewport::calc produces none from finite arguments);
+ * SMHV_E_STATE: no run of the batch has produced a ui_map.  A failed call
+ * enqueues nothing.  The batch keeps a reference of hm until a later render takes another heightmap or the batch is destroyed,
+ * so the caller may drop its own right after the call.  The heightmap's colour table is built by its first overlay or render
+ * (that call waits for it once, on a stream of its own). */
+SMHV_API int smhv_batch_render(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_render_options *opt, void *stream);
+/* the render slab and its per-frame stride, out_w * out_h * 4, of the most recent render (SMHV_E_STATE before the first) */
+SMHV_API int smhv_batch_render_ptr(smhv_batch *b, void **d_images, uint64_t *stride);
+/* the window of the most recent render (SMHV_E_STATE before the first): what smhv_batch_read_render copies per frame */
+SMHV_API int smhv_batch_render_size(smhv_batch *b, uint32_t *out_w, uint32_t *out_h);
+/* synchronising host copy of one frame's image as the most recent render sized it (out_w * out_h * 4 bytes) */
+SMHV_API int smhv_batch_read_render(smhv_batch *b, uint32_t frame, uint8_t *rgba);
+/* The per-call path: the context's current frame -- the ui_map smhv_crop_to_map left on the device, the rectangle its walk found --
+ * and explicit lines in map-ROI coordinates (detected and custom markers; n_lines <= SMHV_RENDER_MAX_LINES), out_w x out_h RGBA8
+ * into host memory.  On the context's stream; SMHV_E_INVALID before load_frame / crop_to_map, SMHV_E_STATE when the map is closed.
+ * The image crosses in one piece through pinned staging of the context, which grows to the largest window rendered and stays
+ * (out_w * out_h * 4 bytes: 14 MB at 2560 x 1440; the 16384 limit would pin 1 GiB -- windows of that size belong to smhv_batch_render). */
+SMHV_API int smhv_render_map(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *opt, const smhv_line *lines, uint32_t n_lines,
+                             uint8_t *rgba);
+
 #ifdef __cplusplus
 }
 #endif

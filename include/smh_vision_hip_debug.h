@@ -89,6 +89,16 @@ SMHV_API int smhv_debug_band_rows(uint32_t frame_w, uint32_t frame_h, uint32_t n
  * always / never (neither: the rule -- band-major where the launch runs alone, frame-major beside the search service).
  * Process-wide; for measuring band heights and work-item orders against each other. */
 SMHV_API int smhv_debug_map_band_rows(uint32_t rows);
+/* diagnostic (process-wide): the form in which k_render_map fetches the heightmap overlay's taps -- 0 = the library's rule (LDS
+ * staging of the tile's texel footprint up to a texels-per-pixel ratio -- 0 as measured: never -- and above it persistent
+ * workgroups with the heightmap's colour table in LDS), 1 = gathers through the table in global memory, 2 = LDS staging (a band whose footprint does not fit its LDS
+ * still gathers), 3 = the table in LDS.  All give the same bytes; the tests and tools/render_cost.py run every one. */
+SMHV_API int smhv_debug_render_form(uint32_t form);
+/* host logic only (no device needed): for a ui_map of map_w x map_h drawn at viewport scale (sw, sh) with a hm_w x hm_h heightmap
+ * over the whole map -- the texels-per-pixel ratio the rule goes by, the ratio at which it switches, the LDS texels of the staged
+ * form, and the form it takes (2 or 3). */
+SMHV_API int smhv_debug_render_rule(uint32_t map_w, uint32_t map_h, float sw, float sh, uint32_t hm_w, uint32_t hm_h, float *ratio, float *switch_ratio,
+                                    uint32_t *lds_texels, uint32_t *form);
 /* benchmark driver: a NATIVE capture loop for the ingest queue (the reference's capture thread is native code, src/capture.rs) --
  * n times: smhv_ingest_acquire, stamp the 24-bit value (*counter)++ into pixel (0, 0) of the staging buffer (whose other
  * pixels keep what they last held; (0, 0) lies outside every region the path reads, so every frame hashes differently and

@@ -10,3 +10,5 @@ from .vision import DebugView, HipVision, VisionResults, VisionState, button_bou
 from .batch import FrameBatch, Pipeline, make_anchors, results_to_dicts  # noqa: F401
 from .ingest import IngestQueue, crc32_device  # noqa: F401
 from .heightmap import Heightmap  # noqa: F401
+from .render import MapViewport, RenderOptions, render_options  # noqa: F401
+from ._lib import RENDER_BOUNDS_OFFSET, RENDER_HEIGHTMAP, RENDER_MARKERS  # noqa: F401

@@ -24,6 +24,9 @@ FIRING_NONE, FIRING_SCALES, FIRING_HEIGHTMAP = 0, 1, 2   # smhv_firing.source
 VIEW_NONE, VIEW_OCR_INPUT, VIEW_FIND_SCALES_INPUT, VIEW_LSD_PREPROCESS, VIEW_LSD_INPUT, VIEW_CROPPED_BRQ = range(6)
 IMAGE_UI_MAP = 100
 IMAGE_HEIGHTMAP_OVERLAY = 101
+RENDER_HEIGHTMAP, RENDER_MARKERS, RENDER_BOUNDS_OFFSET = 1, 2, 4   # smhv_render_options.flags
+RENDER_MAX_LINES = 256                     # explicit lines of one smhv_render_map call
+RENDER_FORM_RULE, RENDER_FORM_GATHER, RENDER_FORM_STAGED, RENDER_FORM_TABLE = 0, 1, 2, 3   # smhv_debug_render_form
 
 E_INVALID, E_GEOMETRY, E_HIP, E_NO_DEVICE, E_STATE = -1, -2, -3, -4, -5
 FRAME_OK, FRAME_LSD_STUCK = 0, 1          # smhv_frame_result.status
@@ -62,6 +65,12 @@ class BatchLayout(C.Structure):
 
 class FiringOptions(C.Structure):
     _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("viewport_scale", C.c_float * 2), ("viewport_top_left", C.c_float * 2)]
+
+
+class RenderOptions(C.Structure):
+    """smhv_render_options (include/smh_vision_hip.h): the window, the map quad and the viewport of a map view."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("out_w", C.c_uint32), ("out_h", C.c_uint32), ("quad", C.c_float * 4),
+                ("viewport_scale", C.c_float * 2), ("viewport_top_left", C.c_float * 2), ("background", C.c_uint8 * 4)]
 
 
 class Firing(C.Structure):
@@ -172,6 +181,16 @@ SIGNATURES = {
                                         C.POINTER(FiringOptions), C.POINTER(Firing)]),
     "smhv_batch_overlay_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "smhv_heightmap_overlay": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FiringOptions), C.c_void_p]),
+    "smhv_map_viewport_calc": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                         C.POINTER(RenderOptions)]),
+    "smhv_batch_render": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RenderOptions), C.c_void_p]),
+    "smhv_batch_render_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "smhv_batch_render_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "smhv_batch_read_render": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "smhv_render_map": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.c_void_p, C.c_uint32, C.c_void_p]),
+    "smhv_debug_render_form": (C.c_int, [C.c_uint32]),
+    "smhv_debug_render_rule": (C.c_int, [C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 
 

@@ -171,6 +171,35 @@ class FrameBatch:
         L.check(self._lib.smhv_batch_overlay_ptr(self._b, C.byref(d)))
         return d.value or 0
 
+    def render(self, viewport, out_w, out_h, first=0, n=None, heightmap=None, markers=False, fit_to_minimap=True, background=(0, 0, 0, 255),
+               stream=None, options=None):
+        """Draw the map view of frames [first, first + n) into the render slab on `stream` (smhv_batch_render): the ui_map through
+        `viewport` (a MapViewport) into a window of out_w x out_h, the heightmap's overlay when `heightmap` is given, the records'
+        marker lines when `markers`.  Asynchronous.  options: a ready RenderOptions instead of the keyword arguments."""
+        from .render import render_options
+        n = self.max_frames - first if n is None else n
+        opt = options if options is not None else render_options(viewport, out_w, out_h, heightmap is not None, markers, fit_to_minimap, background)
+        L.check(self._lib.smhv_batch_render(self._b, first, n, heightmap._hm if heightmap is not None else None, C.byref(opt), stream))
+
+    def render_size(self):
+        """(out_w, out_h) of the most recent render, from the library."""
+        w, h = C.c_uint32(), C.c_uint32()
+        L.check(self._lib.smhv_batch_render_size(self._b, C.byref(w), C.byref(h)))
+        return int(w.value), int(h.value)
+
+    def read_render(self, frame):
+        """Synchronising host copy of a frame's image of the most recent render -> uint8 [out_h, out_w, 4] RGBA."""
+        w, h = self.render_size()
+        out = np.empty((h, w, 4), np.uint8)
+        L.check(self._lib.smhv_batch_read_render(self._b, frame, out.ctypes.data))
+        return out
+
+    def render_ptr(self):
+        """(device address of the render slab, bytes per frame) of the most recent render."""
+        d, st = C.c_void_p(), C.c_uint64()
+        L.check(self._lib.smhv_batch_render_ptr(self._b, C.byref(d), C.byref(st)))
+        return d.value or 0, int(st.value)
+
     def read_image(self, which, frame):
         x, y, w, h = self.roi
         if which in (L.IMAGE_UI_MAP, L.IMAGE_HEIGHTMAP_OVERLAY):

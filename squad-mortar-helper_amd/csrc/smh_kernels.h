@@ -172,6 +172,30 @@ struct OverlayRun {
 	float b0x, b0y;                      // bounds[0] as f32
 	uint32_t flags;                      // SMHV_FIRING_BOUNDS_OFFSET
 };
+// smhv_batch_render / smhv_render_map (k_render_map, smh_render.hip): the app's map view of n frames at one viewport.  Launch
+// arguments, taken by value at the launch.
+#define SMH_RND_MAX_LINES 256u           // explicit lines of smhv_render_map (a record holds at most SMHV_MAX_LINES)
+struct RenderRun {
+	const uint8_t *ui;                   // the ui slab, at the first frame of the call
+	uint8_t *out;                        // the render slab, at the first frame of the call: out_w x out_h RGBA8, tightly packed
+	const FrameAux *aux;                 // per frame: open
+	const smhv_frame_result *res;        // per frame: has_minimap, minimap, n_lines, lines
+	const smhv_line *lines;              // explicit lines for every frame of the call (null: the record's)
+	const uint16_t *hm;                  // heightmap texels, row-major (null: none)
+	const uint32_t *lut;                 // its colour table (hm_lut); word SMH_HM_LUT_ENTRIES + 2 = vr of the 16-bit table
+	const uint16_t *lut16;               // the same colours in 16 bits (k_hm_lut16), what the table form keeps in LDS
+	uint64_t out_stride;                 // out_w * out_h * 4
+	uint32_t hm_w, hm_h;
+	float b0x, b0y;                      // bounds[0] as f32
+	uint32_t flags;                      // SMHV_RENDER_*
+	uint32_t n_lines;                    // of `lines`
+	uint32_t out_w, out_h;
+	float ql, qt, qr, qb;                // the map quad
+	float sw, sh, tx, ty;                // the viewport: scale factors and top left
+	uint32_t bg;                         // background, RGBA8 as a little-endian word
+	uint32_t lds_texels;                 // set by the launcher: texels of LDS of the staged form (0: another form)
+	uint32_t n_frames;                   // set by the launcher
+};
 // ---- the mask as the streaming passes leave it for the line search (round 6) -------------------------------------------------
 // A marker mask is 1-4 % non-empty, and what the search keeps in LDS is its non-empty 32 x 8 px tiles.  Finding them in the
 // row-major bit rows meant walking the bounding box of the set bits: (tile rows x tile columns) x 16 strided dword loads, ~68 KB
@@ -387,6 +411,16 @@ hipError_t launch_heightmap_color_map(const uint16_t *hm, uint64_t n, uint32_t *
 #define SMH_HM_LUT_ENTRIES 65536u
 hipError_t launch_heightmap_lut(const uint16_t *hm, uint64_t n, uint32_t *mm, uint32_t *lut, hipStream_t s);
 hipError_t launch_hm_overlay(const Geom &g, const OverlayRun &r, uint32_t n, hipStream_t s);
+// the map view (smh_render.hip).  render_set_form: 0 = the launcher's rule, 1 = gathers, 2 = LDS staging, 3 = the colour table in LDS (smhv_debug_render_form);
+// render_rule: the form the rule takes for a call (2 or 3), *texels <- the LDS texels of the staged form (the footprint of one band
+// of a tile), *ratio <- heightmap texels per output pixel; render_switch_ratio: the ratio up to which the rule stages
+hipError_t launch_render_map(const Geom &g, const RenderRun &r, uint32_t n, hipStream_t s);
+// the 16-bit form of a heightmap's colour table: lut16 = SMH_HM_LUT_ENTRIES halfwords, *vr = the lowest value with red in its colour
+hipError_t launch_heightmap_lut16(const uint32_t *lut, uint16_t *lut16, uint32_t *vr, hipStream_t s);
+#define SMH_HM_LUT_WORDS (SMH_HM_LUT_ENTRIES + 4u + SMH_HM_LUT_ENTRIES / 2u)   // 32-bit table, {max, min, vr, -}, 16-bit table
+void render_set_form(uint32_t form);
+uint32_t render_rule(const Geom &g, const RenderRun &r, uint32_t *texels, float *ratio);
+float render_switch_ratio();
 // which: SMHV_VIEW_*; isolated: LSDPreprocess shows the marker-isolated crop (after isolate_map_markers)
 hipError_t launch_debug_view(const Geom &g, const Buffers &b, uint32_t frame, int which, int isolated, uint8_t *d_rgba, hipStream_t s);
 hipError_t launch_marker_table(uint32_t *d_bits, hipStream_t s);

@@ -231,6 +231,15 @@ struct smhv_batch {
 	std::vector<FireStage> fire_stage;
 	// SMHV_STAGE_HEIGHTMAP_OVERLAY: the overlay slab, the ui slab's layout (allocated by the first run that asks for it)
 	uint8_t *d_overlay = nullptr;
+	// smhv_batch_render: the render slab (render_cap bytes; images of render_w x render_h RGBA8, tightly packed, indexed by frame),
+	// the heightmap the last render drew (a reference of the batch's own), the event of that render, and whether a run of this
+	// batch has written the ui slab
+	uint8_t *d_render = nullptr;
+	size_t render_cap = 0;
+	uint32_t render_w = 0, render_h = 0;
+	smhv_heightmap *render_hm = nullptr;
+	hipEvent_t ev_render = nullptr;
+	bool ui_written = false;
 };
 
 // a device copy of a heightmap (smhv_heightmap_create); batches and pipelines that have it bound hold references of their own
@@ -621,7 +630,7 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	if (b->ctx) (void)hipSetDevice(b->ctx->device);
 	(void)hipDeviceSynchronize();
 	void *ptrs[] = {b->d_ui, b->d_mask, b->d_bits, b->d_tiled, b->d_occ, b->d_ocr, b->d_scales, b->d_aux, b->d_results, b->d_anchors, b->d_bars, b->d_farm,
-	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run, b->d_overlay};
+	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run, b->d_overlay, b->d_render};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	if (b->h_err) (void)hipHostFree(b->h_err);
@@ -634,6 +643,8 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 		if (a.done) (void)hipEventDestroy(a.done);
 	}
 	hm_release(b->fire_hm);
+	hm_release(b->render_hm);
+	if (b->ev_render) (void)hipEventDestroy(b->ev_render);
 	if (b->ev) {
 		for (int r = 0; r < smhv_batch::TIMING_RING; ++r)
 			for (int i = 0; i < smhv_batch::TIMING_EVENTS; ++i) if (b->ev[r][i]) (void)hipEventDestroy(b->ev[r][i]);
@@ -806,9 +817,11 @@ static int hm_lut(const smhv_heightmap *hm, const uint32_t **lut) {
 		if (!l) {
 			HIPCHK(hipSetDevice(hm->ctx->device));
 			hipStream_t s = nullptr;
-			hipError_t e = hipMalloc((void **)&l, sizeof(uint32_t) * (SMH_HM_LUT_ENTRIES + 4u));
+			hipError_t e = hipMalloc((void **)&l, sizeof(uint32_t) * SMH_HM_LUT_WORDS);
 			if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
 			if (e == hipSuccess) e = launch_heightmap_lut(hm->d, (uint64_t)hm->w * hm->h, l + SMH_HM_LUT_ENTRIES, l, s);
+			// ... and its 16-bit form behind it (what the map view's table form keeps in LDS)
+			if (e == hipSuccess) e = launch_heightmap_lut16(l, (uint16_t *)(l + SMH_HM_LUT_ENTRIES + 4u), l + SMH_HM_LUT_ENTRIES + 2u, s);
 			if (e == hipSuccess) e = hipStreamSynchronize(s);
 			if (s) (void)hipStreamDestroy(s);
 			if (e != hipSuccess) {
@@ -932,6 +945,7 @@ static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint3
 	if (mflags && qflags) HIPCHK(launch_map_brq_pass(g, bf, n, mflags, qflags, grayscale, 0, 1, s, &b->tune));
 	else if (mflags) HIPCHK(launch_map_pass(g, bf, n, mflags, grayscale, s, true, b->tune.map_overlapped != 0u));
 	STAGE_END(1, s);
+	if (mflags & MAP_UI) b->ui_written = true;                 // (the pass that writes the ui slab is enqueued: smhv_batch_render)
 	STAGE_BEGIN(2, s);
 	if (qflags && !mflags) HIPCHK(launch_brq_pass(g, bf, n, qflags, 0, 1, s));
 	STAGE_END(2, s);
@@ -2016,6 +2030,7 @@ extern "C" SMHV_API int smhv_crop_to_map(smhv_ctx *c, int grayscale, int *map_op
 	// waits for it).
 	HIPCHK(launch_button(g, bf, 1, 0, s));
 	HIPCHK(launch_map_pass(g, bf, 1, MAP_UI | MAP_MASK, grayscale, s));
+	b->ui_written = true;                                      // (enqueued)
 	HIPCHK(hipEventRecord(c->ev_map, s));
 	Buffers bm = make_buffers(b, c->frame_ptr, 3);             // the minimap's own record slot
 	HIPCHK(launch_find_minimap(g, bm, 1, s));
@@ -3023,4 +3038,227 @@ extern "C" SMHV_API int smhv_heightmap_overlay(smhv_ctx *c, const smhv_heightmap
 	HIPCHK(launch_hm_overlay(g, r, 1, c->s_main));
 	std::lock_guard<std::mutex> lk2(c->mu);                   // (staging slot 2: the batch read-back's)
 	return copy_image_d2h(c, 2, rgba, b->d_overlay, g.ui_pitch, (size_t)g.m_xoff * 4, (size_t)g.rw * 4, g.rh, c->s_main);
+}
+
+// ------------------------------------------------------------------------------------------------
+// map view: public entry points (smh_vision_hip.h; device code in smh_render.hip, k_render_map)
+// ------------------------------------------------------------------------------------------------
+#define SMH_RENDER_MAX_DIM 16384u
+static const float SMH_MAX_ZOOM = 4.0f;          // src/ui/map.rs:128-129
+static const uint32_t SMH_ZOOM_LEVELS = 10u;
+
+// MapViewport::calc (src/ui/map.rs:21-77), restated in f32.  This translation unit is compiled with -ffp-contract=off: every
+// operation below is one f32 operation.
+extern "C" SMHV_API int smhv_map_viewport_calc(float region_w, float region_h, float map_w, float map_h, uint32_t zoom, const float zoom_pos[2],
+                                               const float pan_pos[2], smhv_render_options *opt) {
+	if (!opt) return fail(SMHV_E_INVALID, "map_viewport_calc: null options");
+	const float map_ar = map_w / map_h, win_ar = region_w / region_h;
+	float size[2];
+	if (win_ar > map_ar) { size[0] = region_h * map_ar; size[1] = region_h; }
+	else { const float inv_ar = map_h / map_w; size[0] = region_w; size[1] = region_w * inv_ar; }
+	float tl[2] = {(region_w - size[0]) / 2.0f, (region_h - size[1]) / 2.0f};
+	if (zoom != 0u) {
+		const float zx = zoom_pos ? zoom_pos[0] : 0.0f, zy = zoom_pos ? zoom_pos[1] : 0.0f;
+		const float px = pan_pos ? pan_pos[0] : 0.0f, py = pan_pos ? pan_pos[1] : 0.0f;
+		const float level = (float)(zoom > 255u ? 255u : zoom);                     // (the app's level is a u8)
+		float amount = fminf(level / (float)SMH_ZOOM_LEVELS, 1.0f) * SMH_MAX_ZOOM;
+		tl[0] -= zx * size[0] * amount;
+		tl[1] -= zy * size[1] * amount;
+		tl[0] += px * (size[0] / map_w);
+		tl[1] += py * (size[1] / map_h);
+		amount += 1.0f;
+		size[0] *= amount;
+		size[1] *= amount;
+	}
+	opt->quad[0] = tl[0]; opt->quad[1] = tl[1];
+	opt->quad[2] = tl[0] + size[0]; opt->quad[3] = tl[1] + size[1];
+	opt->viewport_scale[0] = size[0] / map_w; opt->viewport_scale[1] = size[1] / map_h;
+	opt->viewport_top_left[0] = tl[0]; opt->viewport_top_left[1] = tl[1];
+	return SMHV_OK;
+}
+
+static int check_render_options(const smhv_render_options *opt, const smhv_heightmap *hm, const char *what) {
+	if (!opt) return fail(SMHV_E_INVALID, "%s: null options", what);
+	if (opt->size != sizeof(smhv_render_options)) return fail(SMHV_E_INVALID, "%s: smhv_render_options.size %u != %zu", what, opt->size, sizeof(smhv_render_options));
+	if (opt->flags & ~(SMHV_RENDER_HEIGHTMAP | SMHV_RENDER_MARKERS | SMHV_RENDER_BOUNDS_OFFSET)) return fail(SMHV_E_INVALID, "%s: unknown render flags 0x%x", what, opt->flags);
+	if (opt->out_w == 0u || opt->out_h == 0u || opt->out_w > SMH_RENDER_MAX_DIM || opt->out_h > SMH_RENDER_MAX_DIM)
+		return fail(SMHV_E_INVALID, "%s: window %u x %u (1 .. %u each)", what, opt->out_w, opt->out_h, SMH_RENDER_MAX_DIM);
+	if ((opt->flags & SMHV_RENDER_HEIGHTMAP) && !hm) return fail(SMHV_E_INVALID, "%s: SMHV_RENDER_HEIGHTMAP needs a heightmap", what);
+	for (int i = 0; i < 4; ++i)
+		if (!std::isfinite(opt->quad[i])) return fail(SMHV_E_INVALID, "%s: quad[%d] is not finite", what, i);
+	return SMHV_OK;
+}
+
+// The launch arguments of a render of frames [first, first + n) of `b` with the records at `res` (frame `first`'s), after
+// everything that can fail without the device has been checked; grows the slab.  Nothing is enqueued before this returns SMHV_OK.
+static int render_prepare(smhv_batch *b, uint32_t first, uint32_t n, const smhv_frame_result *res, const smhv_heightmap *hm, const smhv_render_options *opt,
+                          RenderRun *r) {
+	const Geom &g = b->g;
+	const bool use_hm = (opt->flags & SMHV_RENDER_HEIGHTMAP) != 0u;
+	const uint32_t *lut = nullptr;
+	if (use_hm) {
+		if (hm->ctx->device != b->ctx->device) return fail(SMHV_E_INVALID, "render: the heightmap lives on device %d, the batch on %d", hm->ctx->device, b->ctx->device);
+		int rc = hm_lut(hm, &lut);
+		if (rc) return rc;
+	}
+	const uint64_t stride = (uint64_t)opt->out_w * opt->out_h * 4u;
+	const uint64_t need = stride * (uint64_t)b->max_frames;       // the whole batch: rendering it in parts keeps the earlier parts
+	(void)first; (void)n;
+	if (!b->ev_render) HIPCHK(hipEventCreateWithFlags(&b->ev_render, hipEventDisableTiming));
+	if (b->render_cap < need) {
+		if (b->d_render) {
+			HIPCHK(wait_event(b->ev_render));                    // the previous render has left the old slab
+			(void)hipFree(b->d_render);
+			b->d_render = nullptr; b->render_cap = 0;
+		}
+		hipError_t e = hipMalloc((void **)&b->d_render, (size_t)need);
+		if (e != hipSuccess) { b->d_render = nullptr; return fail(SMHV_E_HIP, "render slab (%llu bytes): %s", (unsigned long long)need, hipGetErrorString(e)); }
+		b->render_cap = (size_t)need;
+	}
+	b->render_w = opt->out_w; b->render_h = opt->out_h;
+	memset(r, 0, sizeof *r);
+	r->ui = b->d_ui + (size_t)first * g.ui_stride;
+	r->out = b->d_render + (size_t)first * stride;
+	r->aux = b->d_aux + first;
+	r->res = res;
+	r->out_stride = stride;
+	if (use_hm) {
+		r->hm = hm->d; r->lut = lut; r->hm_w = hm->w; r->hm_h = hm->h;
+		r->lut16 = (const uint16_t *)(lut + SMH_HM_LUT_ENTRIES + 4u);
+		r->b0x = (float)hm->bounds[0]; r->b0y = (float)hm->bounds[1];
+	}
+	r->flags = opt->flags;
+	r->out_w = opt->out_w; r->out_h = opt->out_h;
+	r->ql = opt->quad[0]; r->qt = opt->quad[1]; r->qr = opt->quad[2]; r->qb = opt->quad[3];
+	r->sw = opt->viewport_scale[0] == 0.0f ? 1.0f : opt->viewport_scale[0];
+	r->sh = opt->viewport_scale[1] == 0.0f ? 1.0f : opt->viewport_scale[1];
+	r->tx = opt->viewport_top_left[0]; r->ty = opt->viewport_top_left[1];
+	memcpy(&r->bg, opt->background, 4);
+	return SMHV_OK;
+}
+
+// the batch's reference of the heightmap its enqueued render reads (the previous one goes: if that was the last reference, its
+// release waits for the device, as every release of a heightmap does)
+static void render_bind(smhv_batch *b, const smhv_heightmap *hm) {
+	smhv_heightmap *h = const_cast<smhv_heightmap *>(hm);
+	if (b->render_hm == h) return;
+	hm_retain(h);
+	smhv_heightmap *old = b->render_hm;
+	b->render_hm = h;
+	hm_release(old);
+}
+
+extern "C" SMHV_API int smhv_batch_render(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_render_options *opt, void *stream) {
+	if (!b) return fail(SMHV_E_INVALID, "batch_render: null batch");
+	CTX_OPEN(b->ctx);
+	int rc = check_render_options(opt, hm, "batch_render");
+	if (rc) return rc;
+	if (n == 0u || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_render: frames [%u, %u + %u) of a batch of %u", first, first, n, b->max_frames);
+	if (!b->ui_written) return fail(SMHV_E_STATE, "batch_render: no run of this batch has produced a ui_map (SMHV_STAGE_UI_MAP)");
+	HIPCHK(hipSetDevice(b->ctx->device));
+	const bool use_hm = (opt->flags & SMHV_RENDER_HEIGHTMAP) != 0u;
+	RenderRun r;
+	rc = render_prepare(b, first, n, b->d_results + first, use_hm ? hm : nullptr, opt, &r);
+	if (rc) return rc;
+	render_bind(b, use_hm ? hm : nullptr);
+	hipStream_t s = (hipStream_t)stream;
+	// at most 65,535 frames per launch (the grid's third dimension)
+	for (uint32_t done = 0; done < n;) {
+		const uint32_t k = std::min(n - done, 65535u);
+		RenderRun part = r;
+		part.ui += (size_t)done * b->g.ui_stride; part.out += (size_t)done * r.out_stride; part.aux += done; part.res += done;
+		HIPCHK(launch_render_map(b->g, part, k, s));
+		done += k;
+	}
+	HIPCHK(hipEventRecord(b->ev_render, s));
+	return SMHV_OK;
+}
+
+extern "C" SMHV_API int smhv_batch_render_ptr(smhv_batch *b, void **d_images, uint64_t *stride) {
+	if (!b || !d_images) return fail(SMHV_E_INVALID, "batch_render_ptr: null argument");
+	if (!b->d_render) return fail(SMHV_E_STATE, "batch_render_ptr: this batch has not rendered");
+	*d_images = b->d_render;
+	if (stride) *stride = (uint64_t)b->render_w * b->render_h * 4u;
+	return SMHV_OK;
+}
+
+extern "C" SMHV_API int smhv_batch_render_size(smhv_batch *b, uint32_t *out_w, uint32_t *out_h) {
+	if (!b || !out_w || !out_h) return fail(SMHV_E_INVALID, "batch_render_size: null argument");
+	if (!b->d_render) return fail(SMHV_E_STATE, "batch_render_size: this batch has not rendered");
+	*out_w = b->render_w; *out_h = b->render_h;
+	return SMHV_OK;
+}
+
+extern "C" SMHV_API int smhv_batch_read_render(smhv_batch *b, uint32_t frame, uint8_t *rgba) {
+	if (!b || !rgba || frame >= b->max_frames) return fail(SMHV_E_INVALID, "batch_read_render: bad arguments");
+	if (!b->d_render) return fail(SMHV_E_STATE, "batch_read_render: this batch has not rendered");
+	const size_t stride = (size_t)b->render_w * b->render_h * 4u;
+	if (((size_t)frame + 1u) * stride > b->render_cap) return fail(SMHV_E_INVALID, "batch_read_render: frame %u lies beyond the render slab", frame);
+	HIPCHK(hipSetDevice(b->ctx->device));
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(rgba, b->d_render + (size_t)frame * stride, stride, hipMemcpyDeviceToHost));
+	return SMHV_OK;
+}
+
+// The current frame: frame 0 of the single-frame batch's ui slab (crop_to_map's pass), the rectangle of crop_to_map's walk (the
+// minimap's own record slot, 3), the caller's lines through the context's pinned staging; drawn into that batch's render slab on
+// the context's stream and copied out.
+extern "C" SMHV_API int smhv_render_map(smhv_ctx *c, const smhv_heightmap *hm, const smhv_render_options *opt, const smhv_line *lines, uint32_t n_lines,
+                                        uint8_t *rgba) {
+	int rc = require_open(c, "render_map");
+	if (rc) return rc;
+	CTX_OPEN(c);
+	if (!rgba || (n_lines && !lines)) return fail(SMHV_E_INVALID, "render_map: null argument");
+	if (n_lines > SMHV_RENDER_MAX_LINES) return fail(SMHV_E_INVALID, "render_map: %u lines (at most %u)", n_lines, SMHV_RENDER_MAX_LINES);
+	rc = check_render_options(opt, hm, "render_map");
+	if (rc) return rc;
+	HIPCHK(hipSetDevice(c->device));
+	smhv_batch *b = c->fb;
+	const bool use_hm = (opt->flags & SMHV_RENDER_HEIGHTMAP) != 0u;
+	std::lock_guard<std::mutex> lk(c->fire_mu);
+	RenderRun r;
+	rc = render_prepare(b, 0, 1, b->d_results + 3, use_hm ? hm : nullptr, opt, &r);
+	if (rc) return rc;
+	const size_t line_bytes = sizeof(smhv_line) * (size_t)SMHV_RENDER_MAX_LINES;
+	if (c->fire_cap < line_bytes) {
+		if (c->d_fire) (void)hipFree(c->d_fire);
+		if (c->h_fire) (void)hipHostFree(c->h_fire);
+		c->d_fire = c->h_fire = nullptr; c->fire_cap = 0;
+		HIPCHK(hipMalloc((void **)&c->d_fire, line_bytes));
+		HIPCHK(hipHostMalloc((void **)&c->h_fire, line_bytes));
+		c->fire_cap = line_bytes;
+	}
+	if (n_lines && (opt->flags & SMHV_RENDER_MARKERS)) {
+		memcpy(c->h_fire, lines, sizeof(smhv_line) * (size_t)n_lines);
+		HIPCHK(hipMemcpyAsync(c->d_fire, c->h_fire, sizeof(smhv_line) * (size_t)n_lines, hipMemcpyHostToDevice, c->s_main));
+		r.lines = (const smhv_line *)c->d_fire; r.n_lines = n_lines;
+	} else
+		r.flags &= ~SMHV_RENDER_MARKERS;                      // (no explicit lines: none are drawn, whatever the spare record holds)
+	HIPCHK(launch_render_map(b->g, r, 1, c->s_main));
+	HIPCHK(hipEventRecord(b->ev_render, c->s_main));
+	std::lock_guard<std::mutex> lk2(c->mu);                   // (staging slot 2: the batch read-back's)
+	return copy_image_d2h(c, 2, rgba, b->d_render, (size_t)r.out_stride / opt->out_h, 0, (size_t)opt->out_w * 4, opt->out_h, c->s_main);
+}
+
+extern "C" SMHV_API int smhv_debug_render_form(uint32_t form) {
+	if (form > 3u) return fail(SMHV_E_INVALID, "render form %u (0 = the rule, 1 = gathers, 2 = LDS staging, 3 = the colour table in LDS)", form);
+	render_set_form(form);
+	return SMHV_OK;
+}
+
+extern "C" SMHV_API int smhv_debug_render_rule(uint32_t map_w, uint32_t map_h, float sw, float sh, uint32_t hm_w, uint32_t hm_h, float *ratio, float *switch_ratio,
+                                               uint32_t *lds_texels, uint32_t *form) {
+	if (!map_w || !map_h || !hm_w || !hm_h) return fail(SMHV_E_INVALID, "render_rule: zero dimension");
+	Geom g{};
+	g.rw = map_w; g.rh = map_h;
+	RenderRun r{};
+	r.sw = sw == 0.0f ? 1.0f : sw; r.sh = sh == 0.0f ? 1.0f : sh; r.hm_w = hm_w; r.hm_h = hm_h;
+	float ra = 0.0f;
+	uint32_t tx = 0;
+	const uint32_t f = render_rule(g, r, &tx, &ra);
+	if (ratio) *ratio = ra;
+	if (switch_ratio) *switch_ratio = render_switch_ratio();
+	if (lds_texels) *lds_texels = tx;
+	if (form) *form = f;
+	return SMHV_OK;
 }

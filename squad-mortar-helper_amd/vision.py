@@ -245,6 +245,18 @@ class HipVision:
         L.check(self._lib.smhv_heightmap_overlay(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(opt), out.ctypes.data))
         return out
 
+    def render_map(self, viewport, out_w, out_h, lines=None, heightmap=None, fit_to_minimap=True, background=(0, 0, 0, 255), options=None):
+        """The app's map view of the current frame (smhv_render_map; src/ui/map.rs:209-273): the ui_map through `viewport` (a
+        MapViewport) into a window of out_w x out_h, the heightmap's overlay when `heightmap` is given, and `lines` (float32
+        [n, 4] in map-ROI coordinates: detected and custom markers) -> uint8 [out_h, out_w, 4] RGBA."""
+        from .render import render_options
+        ln = np.ascontiguousarray(lines if lines is not None else np.zeros((0, 4)), np.float32).reshape(-1, 4)
+        opt = options if options is not None else render_options(viewport, out_w, out_h, heightmap is not None, len(ln) > 0, fit_to_minimap, background)
+        out = np.empty((max(int(opt.out_h), 1), max(int(opt.out_w), 1), 4), np.uint8)
+        L.check(self._lib.smhv_render_map(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(opt), ln.ctypes.data if len(ln) else None,
+                                          len(ln), out.ctypes.data))
+        return out
+
     def debug_marker_table(self):
         bits = np.empty((1 << 24) // 32, np.uint32)
         L.check(self._lib.smhv_debug_marker_table(self._ctx, bits.ctypes.data))
