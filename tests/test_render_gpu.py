@@ -15,11 +15,11 @@ BG = (12, 34, 56, 255)
 WINDOWS = ((1280, 720), (2560, 1440), (640, 360))
 
 
-def _hm(seed, side, lo=0, hi=65536):
-    return np.random.default_rng(seed).integers(lo, hi, size=(side, side), dtype=np.uint16)
+def _hm(seed, side, lo=0, hi=65536, height=None):
+    return np.random.default_rng(seed).integers(lo, hi, size=(side if height is None else height, side), dtype=np.uint16)
 
 
-HM_SMALL = (lambda: (_hm(31, 1024), ((-15, 9), (0, 0))))
+HM_SMALL = (lambda: (_hm(31, 1024, height=640), ((-15, 9), (0, 0))))   # not square: 1024 wide, 640 high
 HM_LARGE = (lambda: (_hm(32, 4096, 100, 60000), ((37, -21), (0, 0))))
 
 
