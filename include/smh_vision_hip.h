@@ -626,6 +626,82 @@ SMHV_API int smhv_batch_read_render(smhv_batch *b, uint32_t frame, uint8_t *rgba
 SMHV_API int smhv_render_map(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *opt, const smhv_line *lines, uint32_t n_lines,
                              uint8_t *rgba);
 
+/* ---- remote-viewer feed: the web server's events of every processed frame ----------------------------------------------
+ * The outward interface of a processed frame in the reference is the event stream of its web server (web/src/lib.rs:127-214),
+ * fed once per new frame from src/ui/state.rs:81-88 and src/ui/map.rs:213-233: UpdateState, then Map -- but only when the CRC-32
+ * (crc32fast::hash) of the map's bytes differs from the one the current texture was made from -- then Markers.  A feed is the
+ * producer side of that protocol on the device: it hashes every frame's ui_map where it lies, applies the "changed since the
+ * last texture" rule in frame order (the stored CRC lives in device memory and carries over from call to call) and writes the
+ * byte-exact messages into one compact buffer, so what crosses to the host is proportional to what changed.  Transport
+ * (sockets, HTTP) is the caller's; the debug view that can replace the map (map.rs:210) is not covered: the feed sends the ui_map.
+ * Messages, all little endian, each starting with its u16 id (the macro at lib.rs:74-126 numbers the variants from 1):
+ *   UpdateState (state.rs:81-88, lib.rs:154-176): 03 00, f64 metres per pixel (0.0 for None: !has_mpx), then 01 and the record's
+ *     minimap[4] = left, right, top, bottom as u32 when has_minimap, else 00.  27 or 11 bytes.
+ *   Map (map.rs:213-226, lib.rs:130-140): 01 00, w and h as u32, then w*h*4 bytes of RGBA, tightly packed.  Sent iff the CRC-32 of
+ *     those w*h*4 bytes differs from the stored CRC (nothing stored: sent); the stored CRC becomes this frame's when it is sent.
+ *   Markers, custom = false (map.rs:228-233, lib.rs:142-152): 02 00, 00, n as u32, then per line x0, y0, x1, y1 as f32 (the
+ *     record's lines, bit for bit).  Sent for every such frame, also with n = 0.
+ * A frame whose map is closed, or whose status is not SMHV_FRAME_OK (the reference drops it on Err), sends nothing and leaves the
+ * stored CRC alone (vision/mod.rs:282-288).  With SMHV_FEED_SNAPSHOT the call writes what a client that has just connected gets
+ * for each of the given open frames instead (web/src/ws.rs:35-55), in that order: Map always, UpdateState only when the ratio or
+ * the bounds are present, Markers only when there are lines; the stored CRC is neither used nor changed.
+ * Buffer: one call's events replace the previous call's.  Frames are taken in index order, entries are in frame order and within
+ * a frame in the order above.  The first message starts at offset 6 and every message at an offset = 6 (mod 16), so every Map
+ * payload is 16-byte aligned; bytes between messages are unspecified.  A frame's events are written whole or not at all: a frame
+ * fits when its last message ends at or before capacity_bytes; if the next frame does not fit the call stops there -- frames_done
+ * says how many frames of [first, first + n) were consumed (frames without events that follow the last fitting frame included),
+ * the stored CRC reflects only those, and the caller continues with first + frames_done.  A feed is used by one thread at a time. */
+#define SMHV_WEB_MAP 1u
+#define SMHV_WEB_MARKERS 2u
+#define SMHV_WEB_UPDATE_STATE 3u
+#define SMHV_WEB_HEIGHTMAP 4u
+#define SMHV_WEB_FIT_TO_MINIMAP 5u
+#define SMHV_FEED_SNAPSHOT 1u   /* ws.rs:35-55 for the given frames: Map always, UpdateState / Markers only when they carry
+                                   something; the feed's stored CRC is neither used nor changed */
+typedef struct smhv_feed smhv_feed;
+typedef struct { uint64_t offset; uint32_t length, frame, kind, crc; } smhv_feed_entry;   /* a message: bytes [offset, offset + length) of the buffer,
+                                   frame = its index in the batch, kind = SMHV_WEB_*, crc = CRC-32 of that frame's ui_map */
+typedef struct { uint32_t n_entries, frames_done, n_maps, has_last_crc, last_crc, reserved; uint64_t bytes_used; } smhv_feed_header;   /* bytes_used: the end
+                                   of the last message; has_last_crc / last_crc: the stored CRC after the call */
+/* capacity_bytes: the message buffer; max_frames: the most frames one call covers (1 .. 65535) */
+SMHV_API int smhv_feed_create(smhv_ctx *ctx, uint64_t capacity_bytes, uint32_t max_frames, smhv_feed **out);
+SMHV_API void smhv_feed_destroy(smhv_feed *feed);
+/* forget the stored CRC: the next open frame sends its map.  Waits (host) for the feed's previous call. */
+SMHV_API int smhv_feed_reset(smhv_feed *feed);
+/* The events of frames [first, first + n) of the batch, drawn from its ui slab and records as they are when `stream` reaches the
+ * call (as smhv_batch_render: a plain batch after smhv_batch_run, or a pipeline slot's batch after smhv_pipeline_wait, on either
+ * search schedule).  Asynchronous: three kernels on `stream` (CRC, plan, compacting copy) and no host round trip; the library
+ * orders the call behind the feed's previous call, on whatever stream that was.  SMHV_E_INVALID: capacity_bytes below one
+ * frame's worst case for this batch's geometry (6 + 32 + (10 + w*h*4 rounded up to 16) + 519), n == 0, a range beyond the batch's
+ * capacity or beyond the feed's max_frames, unknown flags, a batch on another device; SMHV_E_STATE: no run of the batch has
+ * produced a ui_map.  A failed call enqueues nothing. */
+SMHV_API int smhv_batch_feed(smhv_batch *b, smhv_feed *feed, uint32_t first, uint32_t n, uint32_t flags, void *stream);
+/* Waits for the feed's last call and copies the header, then n_entries entries (entries may be NULL) and bytes_used bytes (bytes
+ * may be NULL) -- nothing else crosses.  SMHV_E_INVALID when max_entries or cap is too small (the header is filled in then). */
+SMHV_API int smhv_feed_read(smhv_feed *feed, smhv_feed_header *header, smhv_feed_entry *entries, uint32_t max_entries, uint8_t *bytes, uint64_t cap);
+/* device addresses of the header, the entries (3 * max_frames) and the message buffer (valid for the life of the feed) */
+SMHV_API int smhv_feed_ptrs(smhv_feed *feed, void **d_header, void **d_entries, void **d_bytes);
+/* The per-call path: the context's current frame -- the ui_map smhv_crop_to_map left on the device -- with explicit lines
+ * (n_lines <= SMHV_MAX_LINES; custom markers travel in a message of their own: smhv_web_event_markers), mpx (NULL: None) and
+ * minimap = {left, right, top, bottom} (NULL: None), as frame 0.  On the context's stream; SMHV_E_INVALID before load_frame /
+ * crop_to_map, SMHV_E_STATE when the map is closed. */
+SMHV_API int smhv_feed_frame(smhv_ctx *ctx, smhv_feed *feed, const smhv_line *lines, uint32_t n_lines, const double *mpx, const uint32_t minimap[4],
+                             uint32_t flags);
+/* The rest of the protocol, host only (no device needed).  Encoders: *len <- the message's length; the message is written when
+ * out != NULL and cap >= *len (out == NULL asks for the length), SMHV_E_INVALID when cap is too small.
+ *   Markers (lib.rs:142-152): 02 00, custom as a byte, n as u32, n x 4 f32.
+ *   Heightmap (lib.rs:178-206): 04 00 01 00 -- the flag, then a pad byte that keeps the texels on an even offset -- w, h as u32,
+ *     bounds[0] and bounds[1] (the reference's bounds[0][0], bounds[0][1]) as i32, scale[2] as f32, then w*h u16 texels: 24 bytes
+ *     and the texels; data == NULL is None: 04 00 00.
+ *   HeightmapFitToMinimap (lib.rs:208-213): 05 00 and the flag as a byte.
+ * Interaction::deserialize (lib.rs:37-71), the client's replies: *kind <- 1 (AddCustomMarker: exactly 16 more bytes, line <- p0.x,
+ * p0.y, p1.x, p1.y bit for bit) or 2 (DeleteCustomMarker: exactly 4 more bytes, *index), or 0 for anything else (None). */
+SMHV_API int smhv_web_event_markers(const smhv_line *lines, uint32_t n, int custom, uint8_t *out, uint64_t cap, uint64_t *len);
+SMHV_API int smhv_web_event_heightmap(const uint16_t *data, uint32_t w, uint32_t h, const int32_t bounds[4], const float scale[3], uint8_t *out,
+                                      uint64_t cap, uint64_t *len);
+SMHV_API int smhv_web_event_fit(int fit_to_minimap, uint8_t *out, uint64_t cap, uint64_t *len);
+SMHV_API int smhv_web_interaction_parse(const uint8_t *data, uint64_t len, uint32_t *kind, float line[4], uint32_t *index);
+
 #ifdef __cplusplus
 }
 #endif

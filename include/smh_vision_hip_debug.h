@@ -99,6 +99,10 @@ SMHV_API int smhv_debug_render_form(uint32_t form);
  * form, and the form it takes (2 or 3). */
 SMHV_API int smhv_debug_render_rule(uint32_t map_w, uint32_t map_h, float sw, float sh, uint32_t hm_w, uint32_t hm_h, float *ratio, float *switch_ratio,
                                     uint32_t *lds_texels, uint32_t *form);
+/* process-wide: rows of the ui_map a wave of the feed's CRC kernel takes (k_map_crc): 0 = the launcher's rule (as many as leave a
+ * launch some 2048 workgroups, at most 8: one for a handful of frames, eight for a batch of hundreds), 1 .. 64 = that many.  All
+ * give the same CRC; the tests force several so that a batch of a few frames runs the form a large one takes. */
+SMHV_API int smhv_debug_feed_rows(uint32_t rows);
 /* benchmark driver: a NATIVE capture loop for the ingest queue (the reference's capture thread is native code, src/capture.rs) --
  * n times: smhv_ingest_acquire, stamp the 24-bit value (*counter)++ into pixel (0, 0) of the staging buffer (whose other
  * pixels keep what they last held; (0, 0) lies outside every region the path reads, so every frame hashes differently and

@@ -12,3 +12,5 @@ from .ingest import IngestQueue, crc32_device  # noqa: F401
 from .heightmap import Heightmap  # noqa: F401
 from .render import MapViewport, RenderOptions, render_options  # noqa: F401
 from ._lib import RENDER_BOUNDS_OFFSET, RENDER_HEIGHTMAP, RENDER_MARKERS  # noqa: F401
+from .web import WebFeed, encode_fit, encode_heightmap, encode_markers, parse_interaction  # noqa: F401
+from ._lib import FEED_SNAPSHOT, WEB_FIT_TO_MINIMAP, WEB_HEIGHTMAP, WEB_MAP, WEB_MARKERS, WEB_UPDATE_STATE  # noqa: F401

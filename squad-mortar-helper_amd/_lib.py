@@ -28,6 +28,9 @@ RENDER_HEIGHTMAP, RENDER_MARKERS, RENDER_BOUNDS_OFFSET = 1, 2, 4   # smhv_render
 RENDER_MAX_LINES = 256                     # explicit lines of one smhv_render_map call
 RENDER_FORM_RULE, RENDER_FORM_GATHER, RENDER_FORM_STAGED, RENDER_FORM_TABLE = 0, 1, 2, 3   # smhv_debug_render_form
 
+WEB_MAP, WEB_MARKERS, WEB_UPDATE_STATE, WEB_HEIGHTMAP, WEB_FIT_TO_MINIMAP = 1, 2, 3, 4, 5   # the web server's event ids (SMHV_WEB_*)
+FEED_SNAPSHOT = 1                          # smhv_batch_feed / smhv_feed_frame flags: what a client that has just connected gets
+
 E_INVALID, E_GEOMETRY, E_HIP, E_NO_DEVICE, E_STATE = -1, -2, -3, -4, -5
 FRAME_OK, FRAME_LSD_STUCK = 0, 1          # smhv_frame_result.status
 
@@ -80,6 +83,17 @@ class Firing(C.Structure):
 
 class FiringResult(C.Structure):
     _fields_ = [("n_lines", C.c_uint32), ("reserved", C.c_uint32), ("line", Firing * MAX_LINES)]
+
+
+class FeedEntry(C.Structure):
+    """smhv_feed_entry: a message of a feed's buffer (24 bytes)."""
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint32), ("frame", C.c_uint32), ("kind", C.c_uint32), ("crc", C.c_uint32)]
+
+
+class FeedHeader(C.Structure):
+    """smhv_feed_header: what a feed's last call wrote (32 bytes)."""
+    _fields_ = [("n_entries", C.c_uint32), ("frames_done", C.c_uint32), ("n_maps", C.c_uint32), ("has_last_crc", C.c_uint32),
+                ("last_crc", C.c_uint32), ("reserved", C.c_uint32), ("bytes_used", C.c_uint64)]
 
 
 LOG_FN = C.CFUNCTYPE(None, C.c_int, C.c_char_p)
@@ -188,6 +202,19 @@ SIGNATURES = {
     "smhv_batch_render_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "smhv_batch_read_render": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "smhv_render_map": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.c_void_p, C.c_uint32, C.c_void_p]),
+    "smhv_feed_create": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "smhv_feed_destroy": (None, [C.c_void_p]),
+    "smhv_feed_reset": (C.c_int, [C.c_void_p]),
+    "smhv_batch_feed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "smhv_feed_read": (C.c_int, [C.c_void_p, C.POINTER(FeedHeader), C.POINTER(FeedEntry), C.c_uint32, C.c_void_p, C.c_uint64]),
+    "smhv_feed_ptrs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "smhv_feed_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_uint32]),
+    "smhv_web_event_markers": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "smhv_web_event_heightmap": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_void_p, C.c_uint64,
+                                           C.POINTER(C.c_uint64)]),
+    "smhv_web_event_fit": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "smhv_web_interaction_parse": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "smhv_debug_feed_rows": (C.c_int, [C.c_uint32]),
     "smhv_debug_render_form": (C.c_int, [C.c_uint32]),
     "smhv_debug_render_rule": (C.c_int, [C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -200,6 +200,13 @@ class FrameBatch:
         L.check(self._lib.smhv_batch_render_ptr(self._b, C.byref(d), C.byref(st)))
         return d.value or 0, int(st.value)
 
+    def feed(self, feed, first=0, n=None, snapshot=False, stream=0):
+        """The web server's events of frames [first, first + n) into `feed` (a WebFeed) on `stream` (smhv_batch_feed):
+        UpdateState, Map when the ui_map's CRC-32 differs from the one the feed last sent, Markers -- or, with snapshot, what a
+        client that has just connected gets.  Asynchronous; feed.read() waits for it."""
+        n = self.max_frames - first if n is None else n
+        L.check(self._lib.smhv_batch_feed(self._b, feed._f, first, n, L.FEED_SNAPSHOT if snapshot else 0, C.c_void_p(stream)))
+
     def read_image(self, which, frame):
         x, y, w, h = self.roi
         if which in (L.IMAGE_UI_MAP, L.IMAGE_HEIGHTMAP_OVERLAY):

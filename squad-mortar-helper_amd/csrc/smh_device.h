@@ -22,6 +22,18 @@ __device__ __forceinline__ uint32_t luma8(uint32_t r, uint32_t g, uint32_t b) {
 	return u > 255u ? 255u : u;
 }
 
+// CRC-32/IEEE, reflected polynomial; a * b mod P in the reflected representation (x^0 = 0x80000000)
+#define SMH_CRC_POLY 0xEDB88320u
+__host__ __device__ __forceinline__ uint32_t gf2_mulmod(uint32_t a, uint32_t b) {
+	uint32_t p = 0;
+	for (int i = 0; i < 32; ++i) {
+		p ^= (a & 0x80000000u) ? b : 0u;
+		a <<= 1;
+		b = (b >> 1) ^ ((b & 1u) ? SMH_CRC_POLY : 0u);
+	}
+	return p;
+}
+
 __device__ __forceinline__ uint32_t absdiff(uint32_t a, uint32_t b) { return a > b ? a - b : b - a; }
 
 // util/src/image.rs:159-187 hsv() + vision-common/src/markers/mod.rs:17-19,40-54, evaluated exactly

@@ -453,4 +453,31 @@ hipError_t launch_crc32(const void *d_msg, uint64_t n_dwords, uint32_t wgs, uint
 uint32_t crc32_xpow(uint64_t n);                 // x^n mod P (reflected representation, x^0 = 0x80000000)
 uint32_t crc32_mul(uint32_t a, uint32_t b);      // a * b mod P
 
+// ---- the remote-viewer feed (smh_feed.hip; smhv_batch_feed / smhv_feed_frame) -------------------------------------------------
+// Launch arguments of a feed call over n frames, taken by value at the launch.  Everything a frame index applies to (ui, res, raw)
+// points at the call's first frame.
+struct FeedMap { uint64_t dst; uint32_t frame, pad; };   // a Map entry of the call: payload offset in the buffer, frame (index in the call)
+struct FeedRun {
+	const uint8_t *ui;                   // the ui slab
+	const smhv_frame_result *res;        // the records: map_open, status, mpx, minimap, lines
+	uint64_t ui_stride, ui_pitch;
+	uint32_t w, h, xoff, quads;          // the map; ROI pixel 0 sits xoff pixels into a slab row; 16-byte groups of a slab row that hold map bytes
+	uint32_t n, first, flags;            // frames of the call, the batch index of the first (for the entries), SMHV_FEED_*
+	uint32_t len_term;                   // the init / final-xor term of a CRC-32 over w h 4 bytes
+	uint32_t rows_per_wave;              // of k_map_crc (feed_rows_per_wave)
+	uint64_t capacity;                   // bytes of the message buffer
+	uint32_t *raw;                       // n words: the frames' CRCs without that term (zeroed by the launcher)
+	const uint32_t *tab;                 // k_feed_tables for (w, h, xoff): quads + h words
+	uint32_t *state;                     // {has, crc}: the stored CRC
+	smhv_feed_header *header;
+	smhv_feed_entry *entries;            // 3 n
+	uint8_t *bytes;
+	FeedMap *maps;                       // n
+};
+#define SMH_FEED_MAX_ROWS 16384u         // rows of a ui_map a feed's tables hold (a slab row has at most 1024 groups: compute_geom)
+hipError_t launch_feed_tables(uint32_t *d_tab, uint32_t w, uint32_t h, uint32_t xoff, uint32_t quads, hipStream_t s);
+uint32_t feed_rows_per_wave(uint32_t h, uint32_t n);
+void feed_set_rows(uint32_t rows);   // diagnostic: rows per wave of every k_map_crc launch (0 = the rule)
+hipError_t launch_feed(const FeedRun &r, hipStream_t s);   // CRC, plan, compacting copy
+
 }  // namespace smh

@@ -457,19 +457,8 @@ hipError_t launch_marker_table(uint32_t *d_bits, hipStream_t s) {
 // depend on the length only and are applied by the host (smh_runtime.cpp: crc32_finish).
 // HBM-bound: 1 byte read per byte; ~30 VALU + 16 LDS lookups per 16 bytes.
 // ------------------------------------------------------------------------------------------------
-#define CRC_POLY 0xEDB88320u
+#define CRC_POLY SMH_CRC_POLY   // (gf2_mulmod: smh_device.h)
 #define CRC_BS 1024
-
-// a * b mod P in the reflected representation (x^0 = 0x80000000)
-__host__ __device__ __forceinline__ uint32_t gf2_mulmod(uint32_t a, uint32_t b) {
-	uint32_t p = 0;
-	for (int i = 0; i < 32; ++i) {
-		p ^= (a & 0x80000000u) ? b : 0u;
-		a <<= 1;
-		b = (b >> 1) ^ ((b & 1u) ? CRC_POLY : 0u);
-	}
-	return p;
-}
 
 // n_dwords: message length in 32-bit words; rounds * gridDim.x * CRC_BS * 4 >= n_dwords.
 // x_skip = x^(128 (G - 1)); x_local[t] = x^(128 (CRC_BS - 1 - t)); x_wg[g] = x^(128 CRC_BS (gridDim.x - 1 - g)).

@@ -3262,3 +3262,5 @@ extern "C" SMHV_API int smhv_debug_render_rule(uint32_t map_w, uint32_t map_h, f
 	if (form) *form = f;
 	return SMHV_OK;
 }
+
+#include "smh_feed.inc"

@@ -257,6 +257,15 @@ class HipVision:
                                           len(ln), out.ctypes.data))
         return out
 
+    def feed_frame(self, feed, lines, mpx=None, minimap=None, snapshot=False):
+        """The web server's events of the current frame into `feed` (a WebFeed; smhv_feed_frame): the ui_map crop_to_map left on
+        the device, `lines` (float32 [n, 4], n <= 32: the detected markers), mpx (None: none) and minimap = (left, right, top,
+        bottom) or None.  feed.read() hands the messages out."""
+        ln = np.ascontiguousarray(lines if lines is not None else np.zeros((0, 4)), np.float32).reshape(-1, 4)
+        m = C.byref(C.c_double(float(mpx))) if mpx is not None else None
+        mm = (C.c_uint32 * 4)(*[int(v) for v in minimap]) if minimap is not None else None
+        L.check(self._lib.smhv_feed_frame(self._ctx, feed._f, ln.ctypes.data if len(ln) else None, len(ln), m, mm, L.FEED_SNAPSHOT if snapshot else 0))
+
     def debug_marker_table(self):
         bits = np.empty((1 << 24) // 32, np.uint32)
         L.check(self._lib.smhv_debug_marker_table(self._ctx, bits.ctypes.data))
