@@ -626,6 +626,72 @@ SMHV_API int smhv_batch_read_render(smhv_batch *b, uint32_t frame, uint8_t *rgba
 SMHV_API int smhv_render_map(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *opt, const smhv_line *lines, uint32_t n_lines,
                              uint8_t *rgba);
 
+/* ---- map view: layers -- custom markers, the Debug menu's overlays, a debug view as the map ---------------------------------
+ * What the reference's window shows beside the three layers above: draw::render (src/ui/draw.rs:135-198) draws the user's custom
+ * markers and the marker being dragged in magenta and the measuring line in red BEFORE the detected markers (map.rs:258 runs
+ * before map.rs:260-270); the Debug menu (src/ui/debug.rs:286-345) puts OCR boxes (1 px outlines), the computed scale bars (2 px
+ * lines) and the minimap bounds (a 1 px outline, shifted by one pixel) on the foreground draw list, above everything; and
+ * map::render starts with debug_view.unwrap_or(map) (map.rs:210): a debug view can be the map quad's texture.  The two calls below
+ * draw the map view with these layers; smhv_batch_render / smhv_render_map are unchanged and keep their kernels.  Every operation
+ * one f32 operation, left to right, unfused; cx, cy, sw, sh, tx, ty as in the map view.
+ *   0. Background: unchanged.  A closed frame is background everywhere.
+ *   1. Map quad: with map_source != SMHV_VIEW_NONE step 1 samples that image, at its own width and height, in the place of U, w, h.
+ *      Nothing else changes: the overlay, the lines and the prims stay in map-ROI coordinates through the same viewport, as the
+ *      reference does when a quadrant view is the map.
+ *   2. Overlay: unchanged.
+ *   3. Paint order, later over earlier: (1) prims without SMHV_PRIM_FOREGROUND, in list order; (2) the detected marker lines
+ *      (SMHV_RENDER_MARKERS: exactly the map view's rule and colours, f = (i + 1) / n over the lines alone); (3) prims with
+ *      SMHV_PRIM_FOREGROUND, in list order; (4) the minimap bounds.
+ *      A prim's end points: P0 = (x0 * sw + tx, y0 * sh + ty), P1 likewise; with SMHV_PRIM_SHIFT1 1.0f is then added to all four
+ *      values.  Colour = rgba[0..2], alpha 255.
+ *      SMHV_PRIM_LINE: the map view's stroke: dx = P1.x - P0.x, dy = P1.y - P0.y, len2 = dx*dx + dy*dy, skipped unless len2 > 0;
+ *      painted iff 0 <= t && t <= len2 && c*c <= len2.
+ *      SMHV_PRIM_RECT: a = (fminf(P0.x, P1.x), fminf(P0.y, P1.y)), b = (fmaxf(P0.x, P1.x), fmaxf(P0.y, P1.y)) -- a NaN operand yields
+ *      the other one.  Painted iff a.x <= cx && cx < b.x && a.y <= cy && cy < b.y and not (a.x + 1.0f <= cx && cx < b.x - 1.0f &&
+ *      a.y + 1.0f <= cy && cy < b.y - 1.0f): a HARD-EDGED 1 px frame in the place of imgui's stroke of the rectangle [a + 0.5,
+ *      b - 0.5] with thickness 1.  A rectangle narrower or flatter than 2 is filled; a degenerate or NaN one paints nothing.
+ *      SMHV_LAYER_MINIMAP_BOUNDS: when rec.has_minimap, a RECT with corners ((float)left, (float)top), ((float)right, (float)bottom)
+ *      with SMHV_PRIM_SHIFT1 (debug.rs:326-329), colour (0, 255, 0); without a rectangle nothing.  The reference's text is not drawn.
+ * Two identities: with n_prims = 0, flags = 0 and map_source = SMHV_VIEW_NONE the image is smhv_batch_render's / smhv_render_map's,
+ * byte for byte; with the identity viewport at the view's size and nothing else the image is the view (smhv_get_debug_view's on the
+ * per-call path).
+ * Map sources.  Per call: U is exactly what smhv_get_debug_view(ctx, which, ...) returns at that moment, under its state rules.
+ * Batch: sampled in the kernel from the slabs the run left (nothing the size of a batch is materialised):
+ *   SMHV_VIEW_OCR_INPUT, SMHV_VIEW_FIND_SCALES_INPUT   (L, L, L, 255) from the ocr / scales slab, brq_w x brq_h
+ *   SMHV_VIEW_LSD_INPUT                                (L, L, L, 255) from the mask slab, w x h
+ *   SMHV_VIEW_LSD_PREPROCESS   the colour ui_map with every pixel that fails the marker predicate (0, 0, 0), alpha 255 (the batch
+ *                              always isolates), w x h
+ *   SMHV_VIEW_CROPPED_BRQ      pixel (x, y) = the colour ui_map's (x + w/2, y + h/2), w/2 x h/2
+ * A batch (a pipeline slot's too) remembers which of these its runs have produced: SMHV_E_STATE when no run had the OCR / SCALES
+ * (with anchors) / MARKERS stage for the first three, or when the ui_map is missing or the last one written is grayscale for the
+ * last two. */
+#define SMHV_PRIM_LINE        0u      /* kind, low byte: a 2 px stroke, the rule of step 3 of the map view            */
+#define SMHV_PRIM_RECT        1u      /*                 a 1 px rectangle outline with corners (x0, y0), (x1, y1)     */
+#define SMHV_PRIM_FOREGROUND  0x100u  /* painted above the detected markers (the foreground draw list); without it:
+                                         below them (draw::render)                                                     */
+#define SMHV_PRIM_SHIFT1      0x200u  /* 1.0f is added to both translated corners (debug.rs:326-329)                  */
+#define SMHV_RENDER_MAX_PRIMS 256u
+typedef struct { float x0, y0, x1, y1; uint8_t rgba[4]; uint32_t kind; } smhv_render_prim;   /* 24 bytes; map-ROI coordinates */
+
+#define SMHV_LAYER_MINIMAP_BOUNDS 1u  /* smhv_render_layers.flags: the record's minimap rectangle, drawn by the device */
+typedef struct {
+	uint32_t size;                     /* sizeof(smhv_render_layers) */
+	uint32_t flags;                    /* SMHV_LAYER_* */
+	uint32_t map_source;               /* SMHV_VIEW_NONE = the ui_map, or a SMHV_VIEW_*: that image is the map quad's texture */
+	uint32_t n_prims;                  /* <= SMHV_RENDER_MAX_PRIMS */
+	const smhv_render_prim *prims;     /* host memory; copied before the call returns; the same list for every frame of the call */
+} smhv_render_layers;
+/* smhv_batch_render with layers: the same slab, growth, stride and read rules, asynchronous on `stream`.  The prims cross through
+ * pinned staging of the batch: a call with prims waits (host) until the previous call's copy of them has run.  Errors as
+ * smhv_batch_render, and SMHV_E_INVALID for a wrong size, unknown flags, an unknown kind or unknown kind bits, an unknown map_source,
+ * n_prims > SMHV_RENDER_MAX_PRIMS, n_prims != 0 with prims == NULL, a prim whose rgba[3] != 255; SMHV_E_STATE when the chosen source
+ * is not there.  A failed call enqueues nothing. */
+SMHV_API int smhv_batch_render_layers(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_render_options *opt,
+                                      const smhv_render_layers *layers, void *stream);
+/* smhv_render_map with layers: host memory through the context's pinned staging, synchronous.  Errors as smhv_render_map and as above. */
+SMHV_API int smhv_render_map_layers(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *opt, const smhv_render_layers *layers,
+                                    const smhv_line *lines, uint32_t n_lines, uint8_t *rgba);
+
 /* ---- remote-viewer feed: the web server's events of every processed frame ----------------------------------------------
  * The outward interface of a processed frame in the reference is the event stream of its web server (web/src/lib.rs:127-214),
  * fed once per new frame from src/ui/state.rs:81-88 and src/ui/map.rs:213-233: UpdateState, then Map -- but only when the CRC-32

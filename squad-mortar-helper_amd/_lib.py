@@ -26,6 +26,9 @@ IMAGE_UI_MAP = 100
 IMAGE_HEIGHTMAP_OVERLAY = 101
 RENDER_HEIGHTMAP, RENDER_MARKERS, RENDER_BOUNDS_OFFSET = 1, 2, 4   # smhv_render_options.flags
 RENDER_MAX_LINES = 256                     # explicit lines of one smhv_render_map call
+PRIM_LINE, PRIM_RECT, PRIM_FOREGROUND, PRIM_SHIFT1 = 0, 1, 0x100, 0x200   # smhv_render_prim.kind
+RENDER_MAX_PRIMS = 256                     # prims of one render call with layers
+LAYER_MINIMAP_BOUNDS = 1                   # smhv_render_layers.flags
 RENDER_FORM_RULE, RENDER_FORM_GATHER, RENDER_FORM_STAGED, RENDER_FORM_TABLE = 0, 1, 2, 3   # smhv_debug_render_form
 
 WEB_MAP, WEB_MARKERS, WEB_UPDATE_STATE, WEB_HEIGHTMAP, WEB_FIT_TO_MINIMAP = 1, 2, 3, 4, 5   # the web server's event ids (SMHV_WEB_*)
@@ -74,6 +77,16 @@ class RenderOptions(C.Structure):
     """smhv_render_options (include/smh_vision_hip.h): the window, the map quad and the viewport of a map view."""
     _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("out_w", C.c_uint32), ("out_h", C.c_uint32), ("quad", C.c_float * 4),
                 ("viewport_scale", C.c_float * 2), ("viewport_top_left", C.c_float * 2), ("background", C.c_uint8 * 4)]
+
+
+class RenderPrim(C.Structure):
+    """smhv_render_prim: a line or a rectangle outline in map-ROI coordinates (24 bytes)."""
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("x1", C.c_float), ("y1", C.c_float), ("rgba", C.c_uint8 * 4), ("kind", C.c_uint32)]
+
+
+class RenderLayersStruct(C.Structure):
+    """smhv_render_layers: what a render call with layers draws beside the map view."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("map_source", C.c_uint32), ("n_prims", C.c_uint32), ("prims", C.POINTER(RenderPrim))]
 
 
 class Firing(C.Structure):
@@ -201,6 +214,8 @@ SIGNATURES = {
     "smhv_batch_render_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "smhv_batch_render_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "smhv_batch_read_render": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "smhv_batch_render_layers": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(RenderLayersStruct), C.c_void_p]),
+    "smhv_render_map_layers": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(RenderLayersStruct), C.c_void_p, C.c_uint32, C.c_void_p]),
     "smhv_render_map": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.c_void_p, C.c_uint32, C.c_void_p]),
     "smhv_feed_create": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
     "smhv_feed_destroy": (None, [C.c_void_p]),

@@ -172,13 +172,19 @@ class FrameBatch:
         return d.value or 0
 
     def render(self, viewport, out_w, out_h, first=0, n=None, heightmap=None, markers=False, fit_to_minimap=True, background=(0, 0, 0, 255),
-               stream=None, options=None):
+               stream=None, options=None, layers=None):
         """Draw the map view of frames [first, first + n) into the render slab on `stream` (smhv_batch_render): the ui_map through
         `viewport` (a MapViewport) into a window of out_w x out_h, the heightmap's overlay when `heightmap` is given, the records'
-        marker lines when `markers`.  Asynchronous.  options: a ready RenderOptions instead of the keyword arguments."""
+        marker lines when `markers`.  Asynchronous.  options: a ready RenderOptions instead of the keyword arguments.  layers: a
+        RenderLayers (smhv_batch_render_layers): prims, the minimap bounds, a debug view as the map."""
         from .render import render_options
         n = self.max_frames - first if n is None else n
         opt = options if options is not None else render_options(viewport, out_w, out_h, heightmap is not None, markers, fit_to_minimap, background)
+        if layers is not None:
+            ly, keep = layers.struct()
+            L.check(self._lib.smhv_batch_render_layers(self._b, first, n, heightmap._hm if heightmap is not None else None, C.byref(opt), C.byref(ly), stream))
+            del keep
+            return
         L.check(self._lib.smhv_batch_render(self._b, first, n, heightmap._hm if heightmap is not None else None, C.byref(opt), stream))
 
     def render_size(self):

@@ -196,6 +196,25 @@ struct RenderRun {
 	uint32_t lds_texels;                 // set by the launcher: texels of LDS of the staged form (0: another form)
 	uint32_t n_frames;                   // set by the launcher
 };
+// The layers of smhv_batch_render_layers / smhv_render_map_layers (k_render_map_layers): a further launch argument, so RenderRun
+// and the kernels that take it alone stay what they were.
+#define SMH_RND_MAX_ITEMS (SMH_RND_MAX_LINES + SMHV_RENDER_MAX_PRIMS + 1u)   // the kernel's LDS list: lines, prims, the minimap bounds
+#define SMH_RND_SRC_UI 0u                // step 1 samples the ui slab (RenderRun::ui)
+#define SMH_RND_SRC_GRAY 1u              //   ... a plane of one byte per pixel at `src` (the ocr, scales or mask slab): (L, L, L, 255)
+#define SMH_RND_SRC_RGBA 2u              //   ... one RGBA8 image at `src` for the call's single frame (the per-call path's debug view)
+#define SMH_RND_SRC_PREPROCESS 3u        //   ... the colour ui slab, every pixel that is no marker black
+#define SMH_RND_SRC_CROPPED 4u           //   ... the colour ui slab's bottom right quarter
+struct RenderLayersRun {
+	const smhv_render_prim *prims;       // device memory: the prims without SMHV_PRIM_FOREGROUND in list order, then those with it
+	const uint8_t *src;                  // SRC_GRAY: the slab at the first frame of the call; SRC_RGBA: the image
+	uint64_t src_pitch, src_stride;      // bytes per row and per frame of `src`
+	uint32_t src_xoff;                   // SRC_GRAY: bytes from a row's start to its first pixel
+	uint32_t src_mode;                   // SMH_RND_SRC_*
+	uint32_t src_w, src_h;               // the size of step 1's texture, whichever it is
+	uint32_t n_below, n_fg;              // prims of either kind
+	uint32_t flags;                      // SMHV_LAYER_*
+	uint32_t pad;
+};
 // ---- the mask as the streaming passes leave it for the line search (round 6) -------------------------------------------------
 // A marker mask is 1-4 % non-empty, and what the search keeps in LDS is its non-empty 32 x 8 px tiles.  Finding them in the
 // row-major bit rows meant walking the bounding box of the set bits: (tile rows x tile columns) x 16 strided dword loads, ~68 KB
@@ -415,6 +434,8 @@ hipError_t launch_hm_overlay(const Geom &g, const OverlayRun &r, uint32_t n, hip
 // render_rule: the form the rule takes for a call (2 or 3), *texels <- the LDS texels of the staged form (the footprint of one band
 // of a tile), *ratio <- heightmap texels per output pixel; render_switch_ratio: the ratio up to which the rule stages
 hipError_t launch_render_map(const Geom &g, const RenderRun &r, uint32_t n, hipStream_t s);
+// the same with layers: k_render_map_layers of the form the same rule (or smhv_debug_render_form) takes
+hipError_t launch_render_map_layers(const Geom &g, const RenderRun &r, const RenderLayersRun &y, uint32_t n, hipStream_t s);
 // the 16-bit form of a heightmap's colour table: lut16 = SMH_HM_LUT_ENTRIES halfwords, *vr = the lowest value with red in its colour
 hipError_t launch_heightmap_lut16(const uint32_t *lut, uint16_t *lut16, uint32_t *vr, hipStream_t s);
 #define SMH_HM_LUT_WORDS (SMH_HM_LUT_ENTRIES + 4u + SMH_HM_LUT_ENTRIES / 2u)   // 32-bit table, {max, min, vr, -}, 16-bit table

@@ -29,6 +29,15 @@
 //                     The gathers look the colour up per tap in the heightmap's 65,536-entry table (k_hm_lut): four lookups per
 //                     pixel, against texels-per-pixel lookups of the staged form.  The host would take the staged form up to
 //                     SMH_RND_STAGE_RATIO texels per pixel and the table form above; the plain gathers are kept for comparison.
+//   k_render_map_layers<form, waves>   the same picture with the layers of smhv_batch_render_layers / smhv_render_map_layers (the
+//                     header's "map view: layers"): caller's primitives below and above the marker lines, the minimap bounds, and a
+//                     debug view as the quad's texture.  One body (render_map_body<.., LAYERS>) serves both kernels; with LAYERS
+//                     false every line of the layers is compiled out, so k_render_map is the kernel it was.  Lines, primitives and
+//                     the bounds go through the viewport once per workgroup into ONE ordered LDS list (below-prims, marker lines,
+//                     foreground prims, bounds); the pixel loop walks it from its end and takes the first hit, which is the paint
+//                     order.  An item is 32 bytes, the list at most 256 + 256 + 1 items = 16.4 KB: beside the table form's 128 KB
+//                     that is 144.5 KB of the CU's 160 KB, one workgroup per CU as before; the four-wave forms (at most 48 KB of
+//                     staging) still fit two.
 #include "smh_device.h"
 #include "smh_firing.h"
 
@@ -45,6 +54,13 @@ namespace smh {
 static_assert(SMH_RND_MAX_LINES == SMHV_RENDER_MAX_LINES, "the LDS line list holds what the runtime admits");
 
 struct RndLine { float px, py, dx, dy, len2; uint32_t color; };
+// an entry of the layers' list: a line as RndLine (a, b = P0; c, d = P1 - P0), or a rectangle (a, b = the lesser corner; c, d = the
+// greater one; kind = SMHV_PRIM_RECT)
+struct RndItem { float a, b, c, d, len2; uint32_t color, kind, pad; };
+static_assert(sizeof(RndItem) == 32, "two 16-byte LDS reads per item");
+static_assert(sizeof(smhv_render_prim) == 24, "the prim's layout is public");
+template <bool LAYERS> struct RndListOf { typedef RndLine T; static constexpr uint32_t N = SMH_RND_MAX_LINES; };
+template <> struct RndListOf<true> { typedef RndItem T; static constexpr uint32_t N = SMH_RND_MAX_ITEMS; };
 
 // step 5 of the overlay (imgui's blend, tint alpha 64 / 255) over `u`, from the four taps' colours: the arithmetic of k_hm_overlay
 __device__ __forceinline__ uint32_t rnd_blend(uint32_t c00, uint32_t c01, uint32_t c10, uint32_t c11, float fx, float fy, float gy, uint32_t u) {
@@ -83,12 +99,13 @@ __device__ __forceinline__ uint32_t rnd_tab_color(const uint16_t *tab, uint32_t 
 // FORM: how the overlay's taps are fetched (the file's header); WAVES: waves per workgroup.  Forms GATHER and STAGE take one tile
 // per workgroup (grid: tiles x tiles x frames); form TABLE is persistent -- gridDim.x workgroups of 16 waves copy the heightmap's
 // 16-bit colour table (128 KB) into LDS once and then take tiles in turn.
-template <int FORM, uint32_t WAVES>
-__global__ void __launch_bounds__(64 * WAVES) k_render_map(Geom g, RenderRun r) {
+// LAYERS: `y` holds the layers of the call (k_render_map_layers); false: `y` is not read.
+template <int FORM, uint32_t WAVES, bool LAYERS>
+__device__ __forceinline__ void render_map_body(const Geom g, const RenderRun r, const RenderLayersRun y) {
 	constexpr bool STAGE = FORM == SMH_RND_FORM_STAGE, TABLE = FORM == SMH_RND_FORM_TABLE;
 	constexpr uint32_t SMH_RND_BAND_ = WAVES, SMH_RND_BANDS = SMH_RND_TH / WAVES;
 	extern __shared__ uint32_t s_tex[];                       // STAGE: the colours of r.lds_texels texels of the band's footprint; TABLE: the table
-	__shared__ RndLine s_line[SMH_RND_MAX_LINES];
+	__shared__ typename RndListOf<LAYERS>::T s_line[RndListOf<LAYERS>::N];
 	__shared__ uint32_t s_wave_n[WAVES], s_col[2], s_row[SMH_RND_MAX_BANDS][2];
 
 	const uint32_t tid = threadIdx.x;
@@ -140,7 +157,9 @@ __global__ void __launch_bounds__(64 * WAVES) k_render_map(Geom g, RenderRun r) 
 	const float x1 = x0 + sx, y1 = y0 + sy;
 	const float fw = (float)r.hm_w, fh = (float)r.hm_h;
 	const int32_t wm1 = (int32_t)r.hm_w - 1, hm1 = (int32_t)r.hm_h - 1;
-	const float mw = (float)g.rw, mh = (float)g.rh;
+	uint32_t src_w = g.rw, src_h = g.rh;                       // step 1's texture: the ui_map, or the layers' source
+	if constexpr (LAYERS) { src_w = y.src_w; src_h = y.src_h; }
+	const float mw = (float)src_w, mh = (float)src_h;
 	const float qw = r.qr - r.ql, qh = r.qb - r.qt;
 
 	if (tid < 2u + 2u * SMH_RND_BANDS) {
@@ -158,7 +177,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_render_map(Geom g, RenderRun r) 
 		const bool inx = X0 + 64u * k < r.out_w;
 		mcov[k] = inx && r.ql <= cx && cx < r.qr;
 		const float u = ((cx - r.ql) / qw) * mw;
-		ix[k] = rnd_clamp_index(floorf(u), mw, (int32_t)g.rw - 1, 0);
+		ix[k] = rnd_clamp_index(floorf(u), mw, (int32_t)src_w - 1, 0);
 		ocov[k] = inx && ovl && x0 <= cx && cx < x1;
 		const float s = ((cx - x0) / sx) * fw - 0.5f;
 		const float i = floorf(s);
@@ -195,6 +214,75 @@ __global__ void __launch_bounds__(64 * WAVES) k_render_map(Geom g, RenderRun r) 
 		else { lines = res->lines; n_lines = min(res->n_lines, (uint32_t)SMHV_MAX_LINES); }
 	}
 	uint32_t n_list = 0;
+	if constexpr (LAYERS) {
+		// ---- the layers' list: below-prims, the marker lines, foreground prims, the minimap bounds -- in paint order, culled
+		// against the tile and compacted in that order, a workgroup's worth of entries at a time ----
+		const bool bounds = (y.flags & SMHV_LAYER_MINIMAP_BOUNDS) && res->has_minimap != 0u;
+		const uint32_t e_lines = y.n_below + n_lines, e_fg = e_lines + y.n_fg, n_total = e_fg + (bounds ? 1u : 0u);
+		const float cxl = (float)(bx * SMH_RND_TW) + 0.5f, cxh = cxl + (float)(SMH_RND_TW - 1u);
+		const float cyl = (float)tile_y + 0.5f, cyh = cyl + (float)(SMH_RND_TH - 1u);
+		for (uint32_t chunk = 0; chunk < n_total; chunk += 64u * WAVES) {   // (uniform)
+			const uint32_t idx = chunk + tid;
+			bool keep = false;
+			RndItem it{};
+			if (idx < n_total) {
+				float p0x, p0y, p1x, p1y;
+				uint32_t kind;
+				if (idx >= y.n_below && idx < e_lines) {
+					const uint32_t li = idx - y.n_below;
+					const smhv_line l = lines[li];
+					p0x = l.x0 * r.sw + r.tx; p0y = l.y0 * r.sh + r.ty;
+					p1x = l.x1 * r.sw + r.tx; p1y = l.y1 * r.sh + r.ty;
+					const float fl = (float)(li + 1u) / (float)n_lines;
+					it.color = 0xFF000000u | (uint32_t)(uint8_t)((1.0f - fl) * 255.0f + 0.5f) | ((uint32_t)(uint8_t)(fl * 255.0f + 0.5f) << 8);
+					kind = SMHV_PRIM_LINE;
+				} else if (idx < e_fg) {
+					const smhv_render_prim p = y.prims[idx < y.n_below ? idx : idx - n_lines];
+					p0x = p.x0 * r.sw + r.tx; p0y = p.y0 * r.sh + r.ty;
+					p1x = p.x1 * r.sw + r.tx; p1y = p.y1 * r.sh + r.ty;
+					if (p.kind & SMHV_PRIM_SHIFT1) { p0x = p0x + 1.0f; p0y = p0y + 1.0f; p1x = p1x + 1.0f; p1y = p1y + 1.0f; }
+					it.color = 0xFF000000u | (uint32_t)p.rgba[0] | ((uint32_t)p.rgba[1] << 8) | ((uint32_t)p.rgba[2] << 16);
+					kind = p.kind & 0xFFu;
+				} else {                                           // the record's rectangle (left, right, top, bottom), shifted by one
+					p0x = ((float)mm[0] * r.sw + r.tx) + 1.0f; p0y = ((float)mm[2] * r.sh + r.ty) + 1.0f;
+					p1x = ((float)mm[1] * r.sw + r.tx) + 1.0f; p1y = ((float)mm[3] * r.sh + r.ty) + 1.0f;
+					it.color = 0xFF00FF00u;
+					kind = SMHV_PRIM_RECT;
+				}
+				it.kind = kind;
+				const float big = fmaxf(fmaxf(fmaxf(fabsf(p0x), fabsf(p0y)), fmaxf(fabsf(p1x), fabsf(p1y))), fmaxf(cxh, cyh));
+				const bool fin = rnd_finite(p0x) && rnd_finite(p0y) && rnd_finite(p1x) && rnd_finite(p1y);
+				if (kind == SMHV_PRIM_RECT) {
+					// fminf / fmaxf return the other operand for a NaN one.  The test compares the centres with the corners
+					// themselves, so the outer box alone decides; it is grown by the rounding of coordinates of this size all the same
+					it.a = fminf(p0x, p1x); it.b = fminf(p0y, p1y); it.c = fmaxf(p0x, p1x); it.d = fmaxf(p0y, p1y);
+					const float m = 4e-6f * big;
+					const bool away = it.c + m < cxl || it.a - m > cxh || it.d + m < cyl || it.b - m > cyh;
+					keep = !fin || !away;
+				} else {
+					it.a = p0x; it.b = p0y;
+					it.c = p1x - p0x; it.d = p1y - p0y;
+					it.len2 = it.c * it.c + it.d * it.d;
+					if (it.len2 > 0.0f) {                          // (the cull of the lines below, word for word)
+						const float m = 2.0f + 4e-6f * big;
+						const bool away = fmaxf(p0x, p1x) + m < cxl || fminf(p0x, p1x) - m > cxh || fmaxf(p0y, p1y) + m < cyl || fminf(p0y, p1y) - m > cyh;
+						keep = !(fin && rnd_finite(it.len2)) || !away;
+					}
+				}
+			}
+			const unsigned long long bal = __ballot(keep);
+			const uint32_t wave = tid >> 6, lane = tid & 63u;
+			if (lane == 0u) s_wave_n[wave] = (uint32_t)__popcll(bal);
+			__syncthreads();
+			uint32_t base = n_list;
+			for (uint32_t w = 0; w < WAVES; ++w) {
+				if (w < wave) base += s_wave_n[w];
+				n_list += s_wave_n[w];
+			}
+			if (keep) s_line[base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = it;
+			__syncthreads();                                       // (the next chunk rewrites the waves' counts)
+		}
+	} else
 	if (n_lines) {                                             // (uniform)
 		bool keep = false;
 		RndLine ln{};
@@ -260,11 +348,41 @@ __global__ void __launch_bounds__(64 * WAVES) k_render_map(Geom g, RenderRun r) 
 			const float cy = (float)Y + 0.5f;
 			// step 1: the map quad's texel row
 			const bool mrow = r.qt <= cy && cy < r.qb;
-			const uint32_t iy = rnd_clamp_index(floorf(((cy - r.qt) / qh) * mh), mh, (int32_t)g.rh - 1, 0);
-			const uint32_t *src = (const uint32_t *)(r.ui + (size_t)f * g.ui_stride + (size_t)iy * g.ui_pitch) + g.m_xoff;
+			const uint32_t iy = rnd_clamp_index(floorf(((cy - r.qt) / qh) * mh), mh, (int32_t)src_h - 1, 0);
 			uint32_t o[4];
+			bool other = false;
+			if constexpr (LAYERS) other = y.src_mode != SMH_RND_SRC_UI;
+			if (other) {            // (uniform) a debug view is the quad's texture
+#pragma unroll
+				for (uint32_t k = 0; k < 4u; ++k) o[k] = r.bg;
+				if (mrow) {
+					if (y.src_mode == SMH_RND_SRC_GRAY) {              // one byte per pixel, 64 neighbouring bytes per load
+						const uint8_t *row = y.src + (size_t)f * y.src_stride + (size_t)iy * y.src_pitch + y.src_xoff;
+#pragma unroll
+						for (uint32_t k = 0; k < 4u; ++k)
+							if (mcov[k]) o[k] = (uint32_t)row[ix[k]] * 0x00010101u | 0xFF000000u;
+					} else if (y.src_mode == SMH_RND_SRC_RGBA) {        // the per-call path: smhv_get_debug_view's image, tightly packed
+						const uint32_t *row = (const uint32_t *)(y.src + (size_t)iy * y.src_pitch);
+#pragma unroll
+						for (uint32_t k = 0; k < 4u; ++k)
+							if (mcov[k]) o[k] = row[ix[k]] | 0xFF000000u;
+					} else {                                           // the colour ui_map: isolated (LSD_PREPROCESS) or its bottom right quarter
+						const bool crop = y.src_mode == SMH_RND_SRC_CROPPED;
+						const uint32_t oy = crop ? g.rh / 2u : 0u, ox = crop ? g.rw / 2u : 0u;
+						const uint32_t *row = (const uint32_t *)(r.ui + (size_t)f * g.ui_stride + (size_t)(iy + oy) * g.ui_pitch) + g.m_xoff + ox;
+#pragma unroll
+						for (uint32_t k = 0; k < 4u; ++k)
+							if (mcov[k]) {
+								const uint32_t p = row[ix[k]];
+								o[k] = (crop || is_marker(p & 255u, (p >> 8) & 255u, (p >> 16) & 255u)) ? (p | 0xFF000000u) : 0xFF000000u;
+							}
+					}
+				}
+			} else {
+			const uint32_t *src = (const uint32_t *)(r.ui + (size_t)f * g.ui_stride + (size_t)iy * g.ui_pitch) + g.m_xoff;
 #pragma unroll
 			for (uint32_t k = 0; k < 4u; ++k) o[k] = (mrow && mcov[k]) ? (src[ix[k]] | 0xFF000000u) : r.bg;
+			}
 			// step 2: the overlay
 			if (ovl && y0 <= cy && cy < y1) {
 				const float t = ((cy - y0) / sy) * fh - 0.5f;
@@ -303,6 +421,28 @@ __global__ void __launch_bounds__(64 * WAVES) k_render_map(Geom g, RenderRun r) 
 			if (n_list) {
 				bool done[4] = {false, false, false, false};
 				for (uint32_t li = n_list; li-- > 0u;) {
+					if constexpr (LAYERS) {
+						const RndItem it = s_line[li];
+						if (it.kind == SMHV_PRIM_RECT) {               // (uniform) a 1 px frame: the outer box without the inner one
+							const bool yin = it.b <= cy && cy < it.d, yinner = it.b + 1.0f <= cy && cy < it.d - 1.0f;
+#pragma unroll
+							for (uint32_t k = 0; k < 4u; ++k) {
+								const float cx = (float)(X0 + 64u * k) + 0.5f;
+								const bool in = yin && it.a <= cx && cx < it.c;
+								const bool inner = yinner && it.a + 1.0f <= cx && cx < it.c - 1.0f;
+								if (!done[k] && in && !inner) { o[k] = it.color; done[k] = true; }
+							}
+						} else {
+							const float ay = cy - it.b;
+#pragma unroll
+							for (uint32_t k = 0; k < 4u; ++k) {
+								const float ax = ((float)(X0 + 64u * k) + 0.5f) - it.a;
+								const float t = ax * it.c + ay * it.d;
+								const float c = ax * it.d - ay * it.c;
+								if (!done[k] && 0.0f <= t && t <= it.len2 && c * c <= it.len2) { o[k] = it.color; done[k] = true; }
+							}
+						}
+					} else {
 					const RndLine ln = s_line[li];
 					const float ay = cy - ln.py;
 #pragma unroll
@@ -311,6 +451,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_render_map(Geom g, RenderRun r) 
 						const float t = ax * ln.dx + ay * ln.dy;
 						const float c = ax * ln.dy - ay * ln.dx;
 						if (!done[k] && 0.0f <= t && t <= ln.len2 && c * c <= ln.len2) { o[k] = ln.color; done[k] = true; }
+					}
 					}
 				}
 			}
@@ -324,6 +465,15 @@ __global__ void __launch_bounds__(64 * WAVES) k_render_map(Geom g, RenderRun r) 
 	if (!TABLE) break;
 	tile += gridDim.x;
 	}
+}
+
+template <int FORM, uint32_t WAVES>
+__global__ void __launch_bounds__(64 * WAVES) k_render_map(Geom g, RenderRun r) {
+	render_map_body<FORM, WAVES, false>(g, r, RenderLayersRun{});
+}
+template <int FORM, uint32_t WAVES>
+__global__ void __launch_bounds__(64 * WAVES) k_render_map_layers(Geom g, RenderRun r, RenderLayersRun y) {
+	render_map_body<FORM, WAVES, true>(g, r, y);
 }
 
 // The 16-bit colour table of a heightmap from its 32-bit one, and vr = the lowest texel value whose colour has red (65,536: none).
@@ -372,7 +522,8 @@ uint32_t render_rule(const Geom &g, const RenderRun &r, uint32_t *texels, float 
 	return (fits && ra <= (double)SMH_RND_STAGE_RATIO) ? 2u : 3u;
 }
 
-hipError_t launch_render_map(const Geom &g, const RenderRun &run, uint32_t n, hipStream_t s) {
+// y == nullptr: the kernels without layers (k_render_map); else k_render_map_layers of the same form
+static hipError_t launch_render(const Geom &g, const RenderRun &run, const RenderLayersRun *y, uint32_t n, hipStream_t s) {
 	RenderRun r = run;
 	const uint32_t tiles_x = (r.out_w + SMH_RND_TW - 1u) / SMH_RND_TW, tiles_y = (r.out_h + SMH_RND_TH - 1u) / SMH_RND_TH;
 	const dim3 grid(tiles_x, tiles_y, n);
@@ -387,12 +538,13 @@ hipError_t launch_render_map(const Geom &g, const RenderRun &run, uint32_t n, hi
 	}
 	if (form == 3u) {
 		// persistent: one workgroup of 16 waves per CU (the table takes 128 of its 160 KB of LDS), fewer when there are fewer tiles
-		static bool attr_set = false;
+		static bool attr_set[2] = {false, false};
 		const size_t tab_bytes = (size_t)SMH_HM_LUT_ENTRIES * 2u;
-		if (!attr_set) {
-			hipError_t e = hipFuncSetAttribute((const void *)k_render_map<SMH_RND_FORM_TABLE, SMH_RND_TABLE_WAVES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tab_bytes);
+		const void *fn = y ? (const void *)k_render_map_layers<SMH_RND_FORM_TABLE, SMH_RND_TABLE_WAVES> : (const void *)k_render_map<SMH_RND_FORM_TABLE, SMH_RND_TABLE_WAVES>;
+		if (!attr_set[y ? 1 : 0]) {
+			hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tab_bytes);
 			if (e != hipSuccess) return e;
-			attr_set = true;
+			attr_set[y ? 1 : 0] = true;
 		}
 		int dev = 0, cus = 0;
 		hipError_t e = hipGetDevice(&dev);
@@ -400,10 +552,19 @@ hipError_t launch_render_map(const Geom &g, const RenderRun &run, uint32_t n, hi
 		if (e != hipSuccess) return e;
 		const uint64_t total = (uint64_t)tiles_x * tiles_y * n;
 		const uint32_t wgs = (uint32_t)(total < (uint64_t)cus ? total : (uint64_t)cus);
-		hipLaunchKernelGGL((k_render_map<SMH_RND_FORM_TABLE, SMH_RND_TABLE_WAVES>), dim3(wgs), dim3(64u * SMH_RND_TABLE_WAVES), tab_bytes, s, g, r);
-	} else if (form == 2u) hipLaunchKernelGGL((k_render_map<SMH_RND_FORM_STAGE, 4u>), grid, dim3(256), (size_t)r.lds_texels * 4u, s, g, r);
-	else hipLaunchKernelGGL((k_render_map<SMH_RND_FORM_GATHER, 4u>), grid, dim3(256), 0, s, g, r);
+		if (y) hipLaunchKernelGGL((k_render_map_layers<SMH_RND_FORM_TABLE, SMH_RND_TABLE_WAVES>), dim3(wgs), dim3(64u * SMH_RND_TABLE_WAVES), tab_bytes, s, g, r, *y);
+		else hipLaunchKernelGGL((k_render_map<SMH_RND_FORM_TABLE, SMH_RND_TABLE_WAVES>), dim3(wgs), dim3(64u * SMH_RND_TABLE_WAVES), tab_bytes, s, g, r);
+	} else if (form == 2u) {
+		if (y) hipLaunchKernelGGL((k_render_map_layers<SMH_RND_FORM_STAGE, 4u>), grid, dim3(256), (size_t)r.lds_texels * 4u, s, g, r, *y);
+		else hipLaunchKernelGGL((k_render_map<SMH_RND_FORM_STAGE, 4u>), grid, dim3(256), (size_t)r.lds_texels * 4u, s, g, r);
+	} else {
+		if (y) hipLaunchKernelGGL((k_render_map_layers<SMH_RND_FORM_GATHER, 4u>), grid, dim3(256), 0, s, g, r, *y);
+		else hipLaunchKernelGGL((k_render_map<SMH_RND_FORM_GATHER, 4u>), grid, dim3(256), 0, s, g, r);
+	}
 	return hipGetLastError();
 }
+
+hipError_t launch_render_map(const Geom &g, const RenderRun &run, uint32_t n, hipStream_t s) { return launch_render(g, run, nullptr, n, s); }
+hipError_t launch_render_map_layers(const Geom &g, const RenderRun &run, const RenderLayersRun &y, uint32_t n, hipStream_t s) { return launch_render(g, run, &y, n, s); }
 
 }  // namespace smh

@@ -240,6 +240,11 @@ struct smhv_batch {
 	smhv_heightmap *render_hm = nullptr;
 	hipEvent_t ev_render = nullptr;
 	bool ui_written = false;
+	// smhv_batch_render_layers: what the runs of this batch have left in its slabs (a map source has to be there), and the prims'
+	// way to the device: pinned staging, a device copy, and the event of the most recent copy (the staging is free once it has run)
+	bool ui_gray = false, mask_written = false, ocr_written = false, scales_written = false;
+	smhv_render_prim *h_prims = nullptr, *d_prims = nullptr;
+	hipEvent_t ev_prims = nullptr;
 };
 
 // a device copy of a heightmap (smhv_heightmap_create); batches and pipelines that have it bound hold references of their own
@@ -630,9 +635,11 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	if (b->ctx) (void)hipSetDevice(b->ctx->device);
 	(void)hipDeviceSynchronize();
 	void *ptrs[] = {b->d_ui, b->d_mask, b->d_bits, b->d_tiled, b->d_occ, b->d_ocr, b->d_scales, b->d_aux, b->d_results, b->d_anchors, b->d_bars, b->d_farm,
-	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run, b->d_overlay, b->d_render};
+	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run, b->d_overlay, b->d_render, b->d_prims};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
+	if (b->h_prims) (void)hipHostFree(b->h_prims);
+	if (b->ev_prims) (void)hipEventDestroy(b->ev_prims);
 	if (b->h_err) (void)hipHostFree(b->h_err);
 	for (auto &a : b->anchor_stage) {
 		if (a.h) (void)hipHostFree(a.h);
@@ -945,7 +952,10 @@ static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint3
 	if (mflags && qflags) HIPCHK(launch_map_brq_pass(g, bf, n, mflags, qflags, grayscale, 0, 1, s, &b->tune));
 	else if (mflags) HIPCHK(launch_map_pass(g, bf, n, mflags, grayscale, s, true, b->tune.map_overlapped != 0u));
 	STAGE_END(1, s);
-	if (mflags & MAP_UI) b->ui_written = true;                 // (the pass that writes the ui slab is enqueued: smhv_batch_render)
+	if (mflags & MAP_UI) { b->ui_written = true; b->ui_gray = grayscale != 0; }   // (the pass that writes the ui slab is enqueued: smhv_batch_render)
+	if (mflags & MAP_MASK) b->mask_written = true;             // (... and the slabs smhv_batch_render_layers can take as the map)
+	if (qflags & BRQ_OCR) b->ocr_written = true;
+	if (qflags & BRQ_SCALES) b->scales_written = true;
 	STAGE_BEGIN(2, s);
 	if (qflags && !mflags) HIPCHK(launch_brq_pass(g, bf, n, qflags, 0, 1, s));
 	STAGE_END(2, s);
@@ -2030,7 +2040,7 @@ extern "C" SMHV_API int smhv_crop_to_map(smhv_ctx *c, int grayscale, int *map_op
 	// waits for it).
 	HIPCHK(launch_button(g, bf, 1, 0, s));
 	HIPCHK(launch_map_pass(g, bf, 1, MAP_UI | MAP_MASK, grayscale, s));
-	b->ui_written = true;                                      // (enqueued)
+	b->ui_written = true; b->ui_gray = grayscale != 0;         // (enqueued)
 	HIPCHK(hipEventRecord(c->ev_map, s));
 	Buffers bm = make_buffers(b, c->frame_ptr, 3);             // the minimap's own record slot
 	HIPCHK(launch_find_minimap(g, bm, 1, s));
@@ -3238,6 +3248,171 @@ extern "C" SMHV_API int smhv_render_map(smhv_ctx *c, const smhv_heightmap *hm, c
 	HIPCHK(hipEventRecord(b->ev_render, c->s_main));
 	std::lock_guard<std::mutex> lk2(c->mu);                   // (staging slot 2: the batch read-back's)
 	return copy_image_d2h(c, 2, rgba, b->d_render, (size_t)r.out_stride / opt->out_h, 0, (size_t)opt->out_w * 4, opt->out_h, c->s_main);
+}
+
+// ---- the map view with layers (smh_vision_hip.h, "map view: layers"; k_render_map_layers) ----
+static int check_render_layers(const smhv_render_layers *ly, const char *what) {
+	if (!ly) return fail(SMHV_E_INVALID, "%s: null layers", what);
+	if (ly->size != sizeof(smhv_render_layers)) return fail(SMHV_E_INVALID, "%s: smhv_render_layers.size %u != %zu", what, ly->size, sizeof(smhv_render_layers));
+	if (ly->flags & ~SMHV_LAYER_MINIMAP_BOUNDS) return fail(SMHV_E_INVALID, "%s: unknown layer flags 0x%x", what, ly->flags);
+	if (ly->map_source > (uint32_t)SMHV_VIEW_CROPPED_BRQ) return fail(SMHV_E_INVALID, "%s: unknown map source %u", what, ly->map_source);
+	if (ly->n_prims > SMHV_RENDER_MAX_PRIMS) return fail(SMHV_E_INVALID, "%s: %u prims (at most %u)", what, ly->n_prims, SMHV_RENDER_MAX_PRIMS);
+	if (ly->n_prims && !ly->prims) return fail(SMHV_E_INVALID, "%s: %u prims and a null pointer", what, ly->n_prims);
+	for (uint32_t i = 0; i < ly->n_prims; ++i) {
+		const smhv_render_prim &p = ly->prims[i];
+		if ((p.kind & ~(0xFFu | SMHV_PRIM_FOREGROUND | SMHV_PRIM_SHIFT1)) || (p.kind & 0xFFu) > SMHV_PRIM_RECT)
+			return fail(SMHV_E_INVALID, "%s: prim %u has the unknown kind 0x%x", what, i, p.kind);
+		if (p.rgba[3] != 255u) return fail(SMHV_E_INVALID, "%s: prim %u has alpha %u (255 only)", what, i, p.rgba[3]);
+	}
+	return SMHV_OK;
+}
+
+// The prims of a call on their way to the device: the list is split in paint order -- those below the marker lines, then the
+// foreground ones, each part in list order -- into the batch's pinned staging and copied on `s`.  Waits (host) for the previous
+// call's copy to have read the staging.  Fills y->prims, n_below, n_fg.
+static int render_upload_prims(smhv_batch *b, const smhv_render_layers *ly, RenderLayersRun *y, hipStream_t s) {
+	if (ly->n_prims == 0u) return SMHV_OK;
+	const size_t cap = sizeof(smhv_render_prim) * (size_t)SMHV_RENDER_MAX_PRIMS;
+	if (!b->h_prims) HIPCHK(hipHostMalloc((void **)&b->h_prims, cap));
+	if (!b->d_prims) HIPCHK(hipMalloc((void **)&b->d_prims, cap));
+	if (!b->ev_prims) HIPCHK(hipEventCreateWithFlags(&b->ev_prims, hipEventDisableTiming));
+	else HIPCHK(wait_event(b->ev_prims));
+	uint32_t k = 0;
+	for (uint32_t pass = 0; pass < 2u; ++pass) {
+		for (uint32_t i = 0; i < ly->n_prims; ++i)
+			if (((ly->prims[i].kind & SMHV_PRIM_FOREGROUND) != 0u) == (pass == 1u)) b->h_prims[k++] = ly->prims[i];
+		if (pass == 0u) y->n_below = k;
+	}
+	y->n_fg = k - y->n_below;
+	y->prims = b->d_prims;
+	HIPCHK(hipMemcpyAsync(b->d_prims, b->h_prims, sizeof(smhv_render_prim) * (size_t)k, hipMemcpyHostToDevice, s));
+	HIPCHK(hipEventRecord(b->ev_prims, s));
+	return SMHV_OK;
+}
+
+extern "C" SMHV_API int smhv_batch_render_layers(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_render_options *opt,
+                                                 const smhv_render_layers *layers, void *stream) {
+	if (!b) return fail(SMHV_E_INVALID, "batch_render_layers: null batch");
+	CTX_OPEN(b->ctx);
+	int rc = check_render_options(opt, hm, "batch_render_layers");
+	if (rc) return rc;
+	rc = check_render_layers(layers, "batch_render_layers");
+	if (rc) return rc;
+	if (n == 0u || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_render_layers: frames [%u, %u + %u) of a batch of %u", first, first, n, b->max_frames);
+	if (!b->ui_written) return fail(SMHV_E_STATE, "batch_render_layers: no run of this batch has produced a ui_map (SMHV_STAGE_UI_MAP)");
+	const Geom &g = b->g;
+	RenderLayersRun y{};
+	y.flags = layers->flags;
+	y.src_mode = SMH_RND_SRC_UI; y.src_w = g.rw; y.src_h = g.rh;
+	switch ((int)layers->map_source) {
+	case SMHV_VIEW_NONE: break;
+	case SMHV_VIEW_OCR_INPUT:
+	case SMHV_VIEW_FIND_SCALES_INPUT: {
+		const bool ocr = layers->map_source == (uint32_t)SMHV_VIEW_OCR_INPUT;
+		if (!(ocr ? b->ocr_written : b->scales_written))
+			return fail(SMHV_E_STATE, "batch_render_layers: no run of this batch has produced the %s image", ocr ? "OCR input (SMHV_STAGE_OCR)" : "scales input (SMHV_STAGE_SCALES with anchors)");
+		y.src_mode = SMH_RND_SRC_GRAY; y.src = (ocr ? b->d_ocr : b->d_scales) + (size_t)first * g.ocr_stride;
+		y.src_pitch = g.ocr_pitch; y.src_stride = g.ocr_stride; y.src_xoff = g.q_xoff; y.src_w = g.qw; y.src_h = g.qh;
+		break;
+	}
+	case SMHV_VIEW_LSD_INPUT:
+		if (!b->mask_written) return fail(SMHV_E_STATE, "batch_render_layers: no run of this batch has produced the marker mask (SMHV_STAGE_MARKERS)");
+		y.src_mode = SMH_RND_SRC_GRAY; y.src = b->d_mask + (size_t)first * g.mask_stride;
+		y.src_pitch = g.mask_pitch; y.src_stride = g.mask_stride; y.src_xoff = g.m_xoff;
+		break;
+	default:                                                   // SMHV_VIEW_LSD_PREPROCESS, SMHV_VIEW_CROPPED_BRQ: the colour ui_map
+		if (b->ui_gray) return fail(SMHV_E_STATE, "batch_render_layers: the batch's ui_map is grayscale, map source %u needs the colour one", layers->map_source);
+		if (layers->map_source == (uint32_t)SMHV_VIEW_CROPPED_BRQ) {
+			y.src_mode = SMH_RND_SRC_CROPPED; y.src_w = g.rw / 2u; y.src_h = g.rh / 2u;
+			if (y.src_w == 0u || y.src_h == 0u) return fail(SMHV_E_STATE, "batch_render_layers: the map has no bottom right quarter");
+		} else y.src_mode = SMH_RND_SRC_PREPROCESS;
+		break;
+	}
+	HIPCHK(hipSetDevice(b->ctx->device));
+	const bool use_hm = (opt->flags & SMHV_RENDER_HEIGHTMAP) != 0u;
+	RenderRun r;
+	rc = render_prepare(b, first, n, b->d_results + first, use_hm ? hm : nullptr, opt, &r);
+	if (rc) return rc;
+	hipStream_t s = (hipStream_t)stream;
+	rc = render_upload_prims(b, layers, &y, s);
+	if (rc) return rc;
+	render_bind(b, use_hm ? hm : nullptr);
+	for (uint32_t done = 0; done < n;) {                       // at most 65,535 frames per launch (the grid's third dimension)
+		const uint32_t k = std::min(n - done, 65535u);
+		RenderRun part = r;
+		part.ui += (size_t)done * g.ui_stride; part.out += (size_t)done * r.out_stride; part.aux += done; part.res += done;
+		RenderLayersRun yp = y;
+		if (yp.src) yp.src += (size_t)done * y.src_stride;
+		HIPCHK(launch_render_map_layers(g, part, yp, k, s));
+		done += k;
+	}
+	HIPCHK(hipEventRecord(b->ev_render, s));
+	return SMHV_OK;
+}
+
+extern "C" SMHV_API int smhv_render_map_layers(smhv_ctx *c, const smhv_heightmap *hm, const smhv_render_options *opt, const smhv_render_layers *layers,
+                                               const smhv_line *lines, uint32_t n_lines, uint8_t *rgba) {
+	int rc = require_open(c, "render_map_layers");
+	if (rc) return rc;
+	CTX_OPEN(c);
+	if (!rgba || (n_lines && !lines)) return fail(SMHV_E_INVALID, "render_map_layers: null argument");
+	if (n_lines > SMHV_RENDER_MAX_LINES) return fail(SMHV_E_INVALID, "render_map_layers: %u lines (at most %u)", n_lines, SMHV_RENDER_MAX_LINES);
+	rc = check_render_options(opt, hm, "render_map_layers");
+	if (rc) return rc;
+	rc = check_render_layers(layers, "render_map_layers");
+	if (rc) return rc;
+	HIPCHK(hipSetDevice(c->device));
+	smhv_batch *b = c->fb;
+	const Geom &g = b->g;
+	const bool use_hm = (opt->flags & SMHV_RENDER_HEIGHTMAP) != 0u;
+	std::lock_guard<std::mutex> lk(c->fire_mu);
+	RenderRun r;
+	rc = render_prepare(b, 0, 1, b->d_results + 3, use_hm ? hm : nullptr, opt, &r);
+	if (rc) return rc;
+	RenderLayersRun y{};
+	y.flags = layers->flags;
+	y.src_mode = SMH_RND_SRC_UI; y.src_w = g.rw; y.src_h = g.rh;
+	uint8_t *d_view = nullptr;
+	if (layers->map_source != (uint32_t)SMHV_VIEW_NONE) {
+		// U = smhv_get_debug_view's image of this moment: drawn by its kernel into device memory and sampled there
+		const int which = (int)layers->map_source;
+		const bool brq = which == SMHV_VIEW_OCR_INPUT || which == SMHV_VIEW_FIND_SCALES_INPUT || which == SMHV_VIEW_CROPPED_BRQ;
+		y.src_w = brq ? g.qw : g.rw; y.src_h = brq ? g.qh : g.rh;
+		HIPCHK(hipMalloc((void **)&d_view, (size_t)y.src_w * y.src_h * 4u));
+		Buffers bf = make_buffers(b, c->frame_ptr, 0);
+		hipError_t e = launch_debug_view(g, bf, 0, which, c->isolated ? 1 : 0, d_view, c->s_main);
+		if (e != hipSuccess) { (void)hipFree(d_view); return fail(SMHV_E_HIP, "render_map_layers: debug view: %s", hipGetErrorString(e)); }
+		y.src_mode = SMH_RND_SRC_RGBA; y.src = d_view; y.src_pitch = (uint64_t)y.src_w * 4u;
+	}
+	const auto run = [&]() -> int {
+		const size_t line_bytes = sizeof(smhv_line) * (size_t)SMHV_RENDER_MAX_LINES;
+		if (c->fire_cap < line_bytes) {
+			if (c->d_fire) (void)hipFree(c->d_fire);
+			if (c->h_fire) (void)hipHostFree(c->h_fire);
+			c->d_fire = c->h_fire = nullptr; c->fire_cap = 0;
+			HIPCHK(hipMalloc((void **)&c->d_fire, line_bytes));
+			HIPCHK(hipHostMalloc((void **)&c->h_fire, line_bytes));
+			c->fire_cap = line_bytes;
+		}
+		if (n_lines && (opt->flags & SMHV_RENDER_MARKERS)) {
+			memcpy(c->h_fire, lines, sizeof(smhv_line) * (size_t)n_lines);
+			HIPCHK(hipMemcpyAsync(c->d_fire, c->h_fire, sizeof(smhv_line) * (size_t)n_lines, hipMemcpyHostToDevice, c->s_main));
+			r.lines = (const smhv_line *)c->d_fire; r.n_lines = n_lines;
+		} else
+			r.flags &= ~SMHV_RENDER_MARKERS;                  // (no explicit lines: none are drawn, whatever the spare record holds)
+		int rc2 = render_upload_prims(b, layers, &y, c->s_main);
+		if (rc2) return rc2;
+		HIPCHK(launch_render_map_layers(g, r, y, 1, c->s_main));
+		HIPCHK(hipEventRecord(b->ev_render, c->s_main));
+		std::lock_guard<std::mutex> lk2(c->mu);               // (staging slot 2: the batch read-back's)
+		return copy_image_d2h(c, 2, rgba, b->d_render, (size_t)r.out_stride / opt->out_h, 0, (size_t)opt->out_w * 4, opt->out_h, c->s_main);
+	};
+	rc = run();
+	if (d_view) {
+		if (rc) (void)hipStreamSynchronize(c->s_main);         // (whatever was enqueued has left the view before it goes)
+		(void)hipFree(d_view);
+	}
+	return rc;
 }
 
 extern "C" SMHV_API int smhv_debug_render_form(uint32_t form) {

@@ -3,6 +3,8 @@ render call.  MapViewport is the app's own (src/ui/map.rs:14-126): calc letter-b
 the same object feeds the firing solutions (firing_viewport), so the numbers and the picture use one viewport."""
 import ctypes as C
 
+import numpy as np
+
 from . import _lib as L
 
 
@@ -59,3 +61,85 @@ def render_options(viewport, out_w, out_h, heightmap=False, markers=False, fit_t
 
 
 RenderOptions = L.RenderOptions
+
+# ---- layers (smhv_batch_render_layers / smhv_render_map_layers): what the window shows beside the map view ----------------
+CUSTOM_MARKER_COLOR = (255, 0, 255, 255)                          # [1, 0, 1] (src/ui/draw.rs), also the scale bars' (debug.rs:317)
+MEASURE_MARKER_COLOR = (255, 0, 0, 255)                           # [1, 0, 0]
+_f32 = np.float32
+
+
+def prim(x0, y0, x1, y1, rgba, kind):
+    """One smhv_render_prim as a tuple (x0, y0, x1, y1, (r, g, b, a), kind): map-ROI coordinates as C floats' values."""
+    return (float(_f32(x0)), float(_f32(y0)), float(_f32(x1)), float(_f32(y1)), tuple(int(v) for v in rgba), int(kind))
+
+
+def _long_enough(a, b, threshold):
+    """is_line_long_enough (draw.rs:34-36) in f32: sum((a - b)^2) >= threshold^2."""
+    d0, d1 = _f32(a[0]) - _f32(b[0]), _f32(a[1]) - _f32(b[1])
+    t = _f32(threshold)
+    return bool(_f32(d0 * d0) + _f32(d1 * d1) >= t * t)
+
+
+def ctl_marker_prims(custom, drag=None, measure=None, drag_threshold=6.0):
+    """draw::render (draw.rs:135-198) as prims painted BELOW the detected markers: every custom marker ((x0, y0), (x1, y1)) in
+    magenta; `drag` = (start, mouse) in magenta and `measure` = (start, mouse) in red, each only when it is at least
+    `drag_threshold` long (imgui's mouse_drag_threshold, 6 by default).  Map-ROI coordinates."""
+    out = [prim(p0[0], p0[1], p1[0], p1[1], CUSTOM_MARKER_COLOR, L.PRIM_LINE) for p0, p1 in custom]
+    for pair, color in ((drag, CUSTOM_MARKER_COLOR), (measure, MEASURE_MARKER_COLOR)):
+        if pair is not None and _long_enough(pair[0], pair[1], drag_threshold):
+            out.append(prim(pair[0][0], pair[0][1], pair[1][0], pair[1][1], color, L.PRIM_LINE))
+    return out
+
+
+def _color_byte(v):
+    v = _f32(v)
+    v = _f32(0.0) if not v > 0 else (_f32(1.0) if v > 1 else v)   # clamp01 (a NaN is 0)
+    return int(np.uint8(v * _f32(255.0) + _f32(0.5)))
+
+
+def ocr_box_prims(boxes, brq_w, brq_h):
+    """The Debug menu's OCR overlay (debug.rs:290-303): boxes = [(left, top, right, bottom, confidence)] in the bottom right
+    quadrant's pixels, moved by (brq_w, brq_h) into map-ROI coordinates as src/vision/mod.rs:154-157 does; 1 px outlines above
+    everything, coloured [1 - c/100, c/100, 0]."""
+    out = []
+    for left, top, right, bottom, conf in boxes:
+        f = _f32(conf) / _f32(100.0)
+        color = (_color_byte(_f32(1.0) - f), _color_byte(f), 0, 255)
+        out.append(prim(int(left) + int(brq_w), int(top) + int(brq_h), int(right) + int(brq_w), int(bottom) + int(brq_h), color,
+                        L.PRIM_RECT | L.PRIM_FOREGROUND))
+    return out
+
+
+def scale_bar_prims(bars, brq_w, brq_h):
+    """The Debug menu's scale overlay (debug.rs:306-320): bars = [(left, y, right, found)] as calc_meters_to_px_ratio(...,
+    want_bars=True) returns them, moved by (brq_w, brq_h) (mod.rs:205-210); 2 px magenta lines above everything.  Bars that
+    were not found are skipped."""
+    return [prim(int(left) + int(brq_w), int(y) + int(brq_h), int(right) + int(brq_w), int(y) + int(brq_h), CUSTOM_MARKER_COLOR,
+                 L.PRIM_LINE | L.PRIM_FOREGROUND) for left, y, right, found in bars if found]
+
+
+class RenderLayers:
+    """What a render call with layers draws beside the map view: prims (tuples of prim(), or an iterable of them from the
+    builders above), the records' minimap bounds, and a debug view (a VIEW_* of _lib) as the map quad's texture."""
+
+    def __init__(self, prims=(), minimap_bounds=False, map_source=0):
+        self.prims = list(prims)
+        self.minimap_bounds = bool(minimap_bounds)
+        self.map_source = int(map_source)
+
+    def struct(self):
+        """-> (smhv_render_layers, the array it points to: keep it alive for the call)."""
+        n = len(self.prims)
+        arr = (L.RenderPrim * max(n, 1))()
+        for i, (x0, y0, x1, y1, rgba, kind) in enumerate(self.prims):
+            arr[i].x0, arr[i].y0, arr[i].x1, arr[i].y1 = x0, y0, x1, y1
+            for k in range(4):
+                arr[i].rgba[k] = rgba[k]
+            arr[i].kind = kind
+        ly = L.RenderLayersStruct()
+        ly.size = C.sizeof(L.RenderLayersStruct)
+        ly.flags = L.LAYER_MINIMAP_BOUNDS if self.minimap_bounds else 0
+        ly.map_source = self.map_source
+        ly.n_prims = n
+        ly.prims = C.cast(arr, C.POINTER(L.RenderPrim)) if n else None
+        return ly, arr
