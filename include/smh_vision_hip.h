@@ -577,7 +577,8 @@ SMHV_API int smhv_heightmap_overlay(smhv_ctx *ctx, const smhv_heightmap *hm, con
  *      ax = cx - P0.x, ay = cy - P0.y; t = ax*dx + ay*dy; c = ax*dy - ay*dx.  Painted iff 0 <= t && t <= len2 && c*c <= len2
  *      (the centre within 1.0 of the segment, butt ends; no square root).  f = (float)(i + 1) / (float)n; r = (uint8_t)((1.0f -
  *      f) * 255.0f + 0.5f), g = (uint8_t)(f * 255.0f + 0.5f), b = 0, alpha 255.  Later lines paint over earlier ones.  This is
- *      a HARD-EDGED stroke in the place of imgui's anti-aliased one.  Text labels are not drawn (the numbers are smhv_firing's).
+ *      a HARD-EDGED stroke in the place of imgui's anti-aliased one.  Text labels are not drawn by this call: they are a pass of their own
+ *      over its image, smhv_batch_render_labels / smhv_render_map_labeled ("map view: labels").
  * Two identities follow: with out = (w, h), quad = {0, 0, w, h}, scale 1, top left 0 and no flags the image is the ui_map; with
  * SMHV_RENDER_HEIGHTMAP added it is SMHV_STAGE_HEIGHTMAP_OVERLAY's image of the same heightmap, byte for byte. */
 #define SMHV_RENDER_HEIGHTMAP 1u       /* smhv_render_options.flags: draw the heightmap overlay (needs hm) */
@@ -651,7 +652,8 @@ SMHV_API int smhv_render_map(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv
  *      a.y + 1.0f <= cy && cy < b.y - 1.0f): a HARD-EDGED 1 px frame in the place of imgui's stroke of the rectangle [a + 0.5,
  *      b - 0.5] with thickness 1.  A rectangle narrower or flatter than 2 is filled; a degenerate or NaN one paints nothing.
  *      SMHV_LAYER_MINIMAP_BOUNDS: when rec.has_minimap, a RECT with corners ((float)left, (float)top), ((float)right, (float)bottom)
- *      with SMHV_PRIM_SHIFT1 (debug.rs:326-329), colour (0, 255, 0); without a rectangle nothing.  The reference's text is not drawn.
+ *      with SMHV_PRIM_SHIFT1 (debug.rs:326-329), colour (0, 255, 0); without a rectangle nothing.  The reference's text is not drawn here (its
+ *      "Minimap bounds" caption; the marker labels are: "map view: labels").
  * Two identities: with n_prims = 0, flags = 0 and map_source = SMHV_VIEW_NONE the image is smhv_batch_render's / smhv_render_map's,
  * byte for byte; with the identity viewport at the view's size and nothing else the image is the view (smhv_get_debug_view's on the
  * per-call path).
@@ -691,6 +693,95 @@ SMHV_API int smhv_batch_render_layers(smhv_batch *b, uint32_t first, uint32_t n,
 /* smhv_render_map with layers: host memory through the context's pinned staging, synchronous.  Errors as smhv_render_map and as above. */
 SMHV_API int smhv_render_map_layers(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *opt, const smhv_render_layers *layers,
                                     const smhv_line *lines, uint32_t n_lines, uint8_t *rgba);
+
+/* ---- map view: labels -- range, mils, bearings and altitude as text beside every marker line ------------------------------------
+ * markers::draw (src/ui/markers.rs:93-211) prints the firing solution of a line as text that runs along the line and hangs below
+ * its midpoint.  The calls below draw that text, as a pass of their own over a finished image of the map view, and hand out the
+ * strings and their placement.  imgui's anti-aliased TTF text (Inter Bold, 20 px, src/ui/fonts/mod.rs:61) is not bit-reproducible,
+ * so the library pins ONE hard-edged restatement, as the stroke rule does.  Every f32 operation is one operation, left to right,
+ * unfused.
+ * Font.  A 5 x 7 bitmap font drawn for this project (csrc/smh_font5x7.h: 7 row bytes per glyph, top row first, bit 4 = the leftmost
+ *   column); nothing of the reference's TTF files is used.  A glyph sits in a 6 x 9 cell: the advance is 6 font units, the line
+ *   height 9, the glyph occupies columns 0-4 and rows 1-7.  Exactly 27 glyphs: 0-9, m i l a t, R A N G E !, < - >, space, the
+ *   plus-minus sign and the degree sign.  Strings are Latin-1 bytes (plus-minus 0xB1, degree 0xB0).  S = window pixels per font
+ *   unit = smhv_label_options.scale, 1 .. 4, 0 means 2 (a glyph of 10 x 14 px, close to the reference's size).
+ * Which lines, in which order (= slot order).  First the `extra` lines of the call in list order (custom markers, the drag, the
+ *   measuring line: draw.rs:135-198), each with its own RGB.  Then, with SMHV_LABEL_DETECTED, the detected lines in order: in a
+ *   batch rec.lines[0 .. n_lines), per call the explicit `lines` (at most SMHV_MAX_LINES); their colour is the map view's ramp,
+ *   f = (i + 1) / n, the same bytes.  Later labels paint over earlier ones and all labels paint over everything already in the
+ *   image.  THIS DEVIATES from the reference, where a later marker's stroke and the foreground draw list lie above an earlier
+ *   marker's text: here the text always wins.
+ * Numbers.  Every labelled line gets the firing solutions' device function (see "firing solutions": the same code
+ *   smhv_firing_solutions runs, so picture and numbers cannot disagree; SMHV_STAGE_FIRING need not have run) with the render
+ *   call's viewport_scale / viewport_top_left, SMHV_RENDER_BOUNDS_OFFSET as SMHV_FIRING_BOUNDS_OFFSET, the heightmap passed to the
+ *   call (NULL: none), and the frame's minimap rectangle and m/px: in a batch the record's, per call the context's rectangle and
+ *   smhv_label_options.mpx (NULL: none).  The record's-meters input of a detected line of a batch is rec.meters[i]; of every other
+ *   line it is sqrt((double)(x0-x1)*(double)(x0-x1) + (double)(y0-y1)*(double)(y0-y1)) * mpx (Marker::new, ui/mod.rs:131-140), valid
+ *   only when the frame has m/px.
+ * No label (the slot stays, with n_runs = 0, mid = dir = 0): source == SMHV_FIRING_NONE; one of the four translated coordinates is
+ *   not finite; len2 == 0; !(meters < 999999.5).
+ * Strings (a release build's: the debug_assertions rows are not printed).  {:.0} of an f64 is rint() (ties to even) printed as an
+ *   unsigned decimal; bearings are whole numbers already; A = |alt_delta as i32| with Rust's cast (truncating, saturating; the
+ *   lower saturation gives 2147483648); mil(d) = "RANGE!" when mils[d] is NaN, else rint(mils[d]).  d = P0 - P1, the translated
+ *   ends, in f32 (markers.rs:98).  "+-" and "deg" below stand for the bytes 0xB1 and 0xB0.
+ *   Source SCALES, four rows: "{m}m"; "{mil(0)} mil" or "RANGE!"; then, if d.x >= 0, "-> {bearing[1]}deg" and "<- {bearing[0]}deg",
+ *     otherwise "-> {bearing[0]}deg" and "<- {bearing[1]}deg" (d.x >= 0 is -pi/2 <= angle <= pi/2 in signs, markers.rs:202).
+ *   Source HEIGHTMAP: the rows "{m}m" and "+-{A}m alt", a left block "<- {mil(a)} mil" (or "<- RANGE!"), "{bearing[a]}deg" and a
+ *     right block "{mil(b)} mil ->" (or "RANGE! ->"), "{bearing[b]}deg"; a = 0, b = 1 when d.x > 0 || (d.x == 0 && d.y < 0) (-pi/2 <=
+ *     angle < pi/2 in signs, markers.rs:131), otherwise a = 1, b = 0.  Run order: the two rows, the left block, the right block.
+ * Layout, in HALF font units (all integers); row k is w_k = 6 * chars wide; a run is (x2, y2, text).
+ *   SCALES: W2 = max(w_0, w_1), W4 = max(w_0 .. w_3); x2_k = -W2 + (W4 - w_k), y2_k = 18 k (markers.rs:199-210 with its quirk: the
+ *     block is centred on the first two rows' width, each row in the width of all four).
+ *   HEIGHTMAP: the two rows x2_k = -w_k, y2 = 0, 18.  Wf, Wb = the blocks' widest rows, G = 5 (the reference's 10 px): left-block
+ *     rows, right-aligned, x2 = -(Wf + Wb + G) + 2 (Wf - w_k); right-block rows, left-aligned, x2 = -(Wf + Wb + G) + 2 (G + Wf); both
+ *     blocks at y2 = 36, 54 (markers.rs:179-187).
+ *   At most 6 runs of at most 16 characters.
+ * Placement.  M = ((P0.x + P1.x) / 2, (P0.y + P1.y) / 2); len = sqrtf(d.x*d.x + d.y*d.y), correctly rounded; s = d.x > 0 ? 1 : -1;
+ *   e = ((s*d.x) / len, (s*d.y) / len): text_angle (markers.rs:112-118, rotate.rs) without trigonometry -- along the line, never
+ *   upside down, below the midpoint.
+ * Pixel rule.  Pixel (X, Y), cx = X + 0.5f, cy = Y + 0.5f: ax = cx - M.x, ay = cy - M.y; u = (ax*e.x + ay*e.y) / (float)S;
+ *   v = (ay*e.x - ax*e.y) / (float)S.  For each run iu = floorf(u - (float)x2 * 0.5f), iv = floorf(v - (float)y2 * 0.5f); the run is
+ *   hit iff 0 <= iu < 6 * chars and 0 <= iv < 9; the pixel is painted iff the glyph of text[iu / 6] has its bit at column iu % 6
+ *   (< 5) and row iv - 1 (0 .. 6).  Colour = the label's RGB, alpha 255.  A closed frame gets nothing (its result has n_labels = 0). */
+#define SMHV_LABEL_DETECTED 1u        /* smhv_label_options.flags: label the detected lines too */
+#define SMHV_LABEL_MAX_EXTRA 64u
+typedef struct { smhv_line line; uint8_t rgba[4]; } smhv_label_line;          /* rgba[3] must be 255 */
+typedef struct {
+	uint32_t size;                       /* sizeof(smhv_label_options) */
+	uint32_t flags;                      /* SMHV_LABEL_* */
+	uint32_t scale;                      /* S: 1 .. 4, 0 = 2 */
+	uint32_t n_extra;                    /* <= SMHV_LABEL_MAX_EXTRA */
+	const smhv_label_line *extra;        /* host memory; copied before the call returns; the same list for every frame of the call */
+	const double *mpx;                   /* the per-call path's meters per pixel (NULL: none); a batch takes the record's */
+} smhv_label_options;
+typedef struct { int16_t x2, y2; uint8_t n, pad[3]; uint8_t text[16]; } smhv_label_run;      /* 24 bytes; text beyond n is 0 */
+typedef struct { smhv_firing firing; float mid[2], dir[2]; uint8_t rgba[4]; uint32_t n_runs; smhv_label_run run[6]; } smhv_label;   /* 216 bytes */
+typedef struct { uint32_t n_labels, reserved; smhv_label label[SMHV_LABEL_MAX_EXTRA + SMHV_MAX_LINES]; } smhv_label_result;
+/* A line without a label keeps its slot with n_runs = 0; slot order is extras first, then the detected lines; n_labels is the
+ * number of slots (slots beyond it are zero). */
+/* A glyph of the font: rows[0 .. 6], bit 4 = the leftmost column.  Host only.  SMHV_E_INVALID for a byte outside the 27. */
+SMHV_API int smhv_label_font(uint8_t ch, uint8_t rows[7]);
+/* Draws the labels onto the batch's render slab over frames [first, first + n), asynchronously on `stream`, behind whatever the
+ * batch's previous render enqueued (a device-side wait), and writes the batch's label slab: one smhv_label_result per frame,
+ * allocated by the first call.  ropt supplies the window and the viewport: out_w / out_h must be the most recent render's
+ * (SMHV_E_STATE for another size or before the first render); hm (NULL: none) feeds the numbers whatever ropt->flags says.
+ * SMHV_E_INVALID: what smhv_batch_render rejects in ropt, a wrong size, unknown flags, scale > 4, n_extra > SMHV_LABEL_MAX_EXTRA,
+ * n_extra != 0 with extra == NULL, an rgba[3] != 255, n == 0 or a range beyond the batch's capacity.  A failed call enqueues
+ * nothing.  The extras cross through pinned staging of the batch: a call with extras waits (host) until the previous call's copy
+ * of them has run.  Works on a plain batch after smhv_batch_run and on a pipeline slot's batch after smhv_pipeline_wait, for both
+ * searches.  The batch keeps a reference of hm as smhv_batch_render does. */
+SMHV_API int smhv_batch_render_labels(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_render_options *ropt,
+                                      const smhv_label_options *lopt, void *stream);
+/* The batch's label slab: read is a synchronising host copy, ptr the device address (SMHV_E_STATE before the first
+ * smhv_batch_render_labels): the strings and the placement without the pixels, for a caller that draws text itself. */
+SMHV_API int smhv_batch_read_labels(smhv_batch *b, uint32_t first, uint32_t n, smhv_label_result *out);
+SMHV_API int smhv_batch_labels_ptr(smhv_batch *b, void **d_labels);
+/* The per-call path: exactly smhv_render_map_layers's image (smhv_render_map's with layers == NULL), then the labels; the image is
+ * copied out once; *labels (optional) receives the slots.  With SMHV_LABEL_DETECTED the explicit `lines` are labelled
+ * (SMHV_E_INVALID for more than SMHV_MAX_LINES).  Errors as smhv_render_map_layers and as above. */
+SMHV_API int smhv_render_map_labeled(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_render_layers *layers,
+                                     const smhv_line *lines, uint32_t n_lines, const smhv_label_options *lopt, uint8_t *rgba,
+                                     smhv_label_result *labels);
 
 /* ---- remote-viewer feed: the web server's events of every processed frame ----------------------------------------------
  * The outward interface of a processed frame in the reference is the event stream of its web server (web/src/lib.rs:127-214),

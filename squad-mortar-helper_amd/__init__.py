@@ -12,6 +12,7 @@ from .ingest import IngestQueue, crc32_device  # noqa: F401
 from .heightmap import Heightmap  # noqa: F401
 from .render import MapViewport, RenderOptions, render_options  # noqa: F401
 from .render import RenderLayers, ctl_marker_prims, ocr_box_prims, prim, scale_bar_prims  # noqa: F401
+from .render import LabelOptions, label_lines  # noqa: F401
 from ._lib import LAYER_MINIMAP_BOUNDS, PRIM_FOREGROUND, PRIM_LINE, PRIM_RECT, PRIM_SHIFT1, RENDER_MAX_PRIMS  # noqa: F401
 from ._lib import RENDER_BOUNDS_OFFSET, RENDER_HEIGHTMAP, RENDER_MARKERS  # noqa: F401
 from .web import WebFeed, encode_fit, encode_heightmap, encode_markers, parse_interaction  # noqa: F401

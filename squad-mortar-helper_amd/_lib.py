@@ -98,6 +98,34 @@ class FiringResult(C.Structure):
     _fields_ = [("n_lines", C.c_uint32), ("reserved", C.c_uint32), ("line", Firing * MAX_LINES)]
 
 
+LABEL_DETECTED, LABEL_MAX_EXTRA, LABEL_SLOTS = 1, 64, 64 + MAX_LINES
+
+
+class LabelLine(C.Structure):
+    """smhv_label_line: an extra line to label, with its colour (20 bytes)."""
+    _fields_ = [("line", Line), ("rgba", C.c_uint8 * 4)]
+
+
+class LabelOptionsStruct(C.Structure):
+    """smhv_label_options: which lines get a label, and the text's scale."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("scale", C.c_uint32), ("n_extra", C.c_uint32), ("extra", C.POINTER(LabelLine)),
+                ("mpx", C.POINTER(C.c_double))]
+
+
+class LabelRun(C.Structure):
+    """smhv_label_run: one row of text, placed in half font units (24 bytes)."""
+    _fields_ = [("x2", C.c_int16), ("y2", C.c_int16), ("n", C.c_uint8), ("pad", C.c_uint8 * 3), ("text", C.c_uint8 * 16)]
+
+
+class Label(C.Structure):
+    """smhv_label: a slot -- the numbers, the placement, the colour and the runs of one line (216 bytes)."""
+    _fields_ = [("firing", Firing), ("mid", C.c_float * 2), ("dir", C.c_float * 2), ("rgba", C.c_uint8 * 4), ("n_runs", C.c_uint32), ("run", LabelRun * 6)]
+
+
+class LabelResult(C.Structure):
+    _fields_ = [("n_labels", C.c_uint32), ("reserved", C.c_uint32), ("label", Label * LABEL_SLOTS)]
+
+
 class FeedEntry(C.Structure):
     """smhv_feed_entry: a message of a feed's buffer (24 bytes)."""
     _fields_ = [("offset", C.c_uint64), ("length", C.c_uint32), ("frame", C.c_uint32), ("kind", C.c_uint32), ("crc", C.c_uint32)]
@@ -217,6 +245,12 @@ SIGNATURES = {
     "smhv_batch_render_layers": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(RenderLayersStruct), C.c_void_p]),
     "smhv_render_map_layers": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(RenderLayersStruct), C.c_void_p, C.c_uint32, C.c_void_p]),
     "smhv_render_map": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.c_void_p, C.c_uint32, C.c_void_p]),
+    "smhv_label_font": (C.c_int, [C.c_uint8, C.POINTER(C.c_uint8)]),
+    "smhv_batch_render_labels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(LabelOptionsStruct), C.c_void_p]),
+    "smhv_batch_read_labels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(LabelResult)]),
+    "smhv_batch_labels_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smhv_render_map_labeled": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(RenderLayersStruct), C.c_void_p, C.c_uint32,
+                                          C.POINTER(LabelOptionsStruct), C.c_void_p, C.POINTER(LabelResult)]),
     "smhv_feed_create": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
     "smhv_feed_destroy": (None, [C.c_void_p]),
     "smhv_feed_reset": (C.c_int, [C.c_void_p]),

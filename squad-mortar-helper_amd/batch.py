@@ -206,6 +206,28 @@ class FrameBatch:
         L.check(self._lib.smhv_batch_render_ptr(self._b, C.byref(d), C.byref(st)))
         return d.value or 0, int(st.value)
 
+    def render_labels(self, options, labels, first=0, n=None, heightmap=None, stream=None):
+        """Draw the marker labels onto the images of the most recent render over frames [first, first + n) on `stream`
+        (smhv_batch_render_labels) and write the label slab.  options: the RenderOptions of that render (the window and the
+        viewport); labels: a LabelOptions; heightmap: what the numbers take their range and altitude from.  Asynchronous."""
+        n = self.max_frames - first if n is None else n
+        lo, keep = labels.struct()
+        L.check(self._lib.smhv_batch_render_labels(self._b, first, n, heightmap._hm if heightmap is not None else None, C.byref(options), C.byref(lo), stream))
+        del keep
+
+    def read_labels(self, first=0, n=None):
+        """Synchronising host copy of the label slab -> a ctypes array of n LabelResult."""
+        n = self.max_frames - first if n is None else n
+        out = (L.LabelResult * n)()
+        L.check(self._lib.smhv_batch_read_labels(self._b, first, n, out))
+        return out
+
+    def labels_ptr(self):
+        """Device address of the label slab (one smhv_label_result per frame)."""
+        d = C.c_void_p()
+        L.check(self._lib.smhv_batch_labels_ptr(self._b, C.byref(d)))
+        return d.value or 0
+
     def feed(self, feed, first=0, n=None, snapshot=False, stream=0):
         """The web server's events of frames [first, first + n) into `feed` (a WebFeed) on `stream` (smhv_batch_feed):
         UpdateState, Map when the ui_map's CRC-32 differs from the one the feed last sent, Markers -- or, with snapshot, what a

@@ -215,6 +215,28 @@ struct RenderLayersRun {
 	uint32_t flags;                      // SMHV_LAYER_*
 	uint32_t pad;
 };
+// smhv_batch_render_labels / smhv_render_map_labeled (k_label_plan, k_label_draw: smh_labels.hip): the marker labels of n frames.
+// Launch arguments, taken by value at the launch.
+#define SMH_LBL_SLOTS (SMHV_LABEL_MAX_EXTRA + SMHV_MAX_LINES)
+struct LabelCull { float mx, my, rad; uint32_t live; };   // per slot, for k_label_draw's cull: the midpoint, the circle that holds every painted pixel, n_runs != 0
+struct LabelRun {
+	FiringRun fr;                        // the heightmap and the viewport, as the firing solutions take them (`out` is not used)
+	const FrameAux *aux;                 // per frame: open
+	const smhv_frame_result *res;        // per frame: the minimap rectangle; batch: m/px, meters and the detected lines too
+	const smhv_label_line *extra;        // device memory: the call's extra lines
+	const smhv_line *lines;              // per call: the explicit detected lines (null: the record's)
+	smhv_label_result *out;              // the label slab, at the first frame of the call
+	LabelCull *cull;                     // SMH_LBL_SLOTS entries per frame, at the first frame of the call
+	uint8_t *img;                        // the render slab, at the first frame of the call
+	uint64_t img_stride;                 // out_w * out_h * 4
+	double mpx;                          // per call: the frame's meters per pixel (valid iff has_mpx)
+	uint32_t out_w, out_h;
+	uint32_t n_extra, n_lines;           // of `extra`, of `lines`
+	uint32_t detected;                   // SMHV_LABEL_DETECTED
+	uint32_t scale;                      // S, 1 .. 4
+	uint32_t per_call;                   // 1: `lines`, `mpx` / has_mpx are the call's and res is one record for the rectangle alone
+	uint32_t has_mpx;
+};
 // ---- the mask as the streaming passes leave it for the line search (round 6) -------------------------------------------------
 // A marker mask is 1-4 % non-empty, and what the search keeps in LDS is its non-empty 32 x 8 px tiles.  Finding them in the
 // row-major bit rows meant walking the bounding box of the set bits: (tile rows x tile columns) x 16 strided dword loads, ~68 KB
@@ -439,6 +461,8 @@ hipError_t launch_render_map_layers(const Geom &g, const RenderRun &r, const Ren
 // the 16-bit form of a heightmap's colour table: lut16 = SMH_HM_LUT_ENTRIES halfwords, *vr = the lowest value with red in its colour
 hipError_t launch_heightmap_lut16(const uint32_t *lut, uint16_t *lut16, uint32_t *vr, hipStream_t s);
 #define SMH_HM_LUT_WORDS (SMH_HM_LUT_ENTRIES + 4u + SMH_HM_LUT_ENTRIES / 2u)   // 32-bit table, {max, min, vr, -}, 16-bit table
+// the marker labels (smh_labels.hip): k_label_plan over n frames, then k_label_draw over their images
+hipError_t launch_labels(const LabelRun &r, uint32_t n, hipStream_t s);
 void render_set_form(uint32_t form);
 uint32_t render_rule(const Geom &g, const RenderRun &r, uint32_t *texels, float *ratio);
 float render_switch_ratio();

@@ -245,6 +245,13 @@ struct smhv_batch {
 	bool ui_gray = false, mask_written = false, ocr_written = false, scales_written = false;
 	smhv_render_prim *h_prims = nullptr, *d_prims = nullptr;
 	hipEvent_t ev_prims = nullptr;
+	// smhv_batch_render_labels: the label slab and the cull entries of its slots (allocated by the first call), the extras' way to
+	// the device (pinned staging, a device copy, the event of the most recent copy) and the heightmap the last call read
+	smhv_label_result *d_labels = nullptr;
+	LabelCull *d_label_cull = nullptr;
+	smhv_label_line *h_label_extra = nullptr, *d_label_extra = nullptr;
+	hipEvent_t ev_label_extra = nullptr;
+	smhv_heightmap *label_hm = nullptr;
 };
 
 // a device copy of a heightmap (smhv_heightmap_create); batches and pipelines that have it bound hold references of their own
@@ -635,11 +642,14 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	if (b->ctx) (void)hipSetDevice(b->ctx->device);
 	(void)hipDeviceSynchronize();
 	void *ptrs[] = {b->d_ui, b->d_mask, b->d_bits, b->d_tiled, b->d_occ, b->d_ocr, b->d_scales, b->d_aux, b->d_results, b->d_anchors, b->d_bars, b->d_farm,
-	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run, b->d_overlay, b->d_render, b->d_prims};
+	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run, b->d_overlay, b->d_render, b->d_prims, b->d_labels,
+	                b->d_label_cull, b->d_label_extra};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	if (b->h_prims) (void)hipHostFree(b->h_prims);
 	if (b->ev_prims) (void)hipEventDestroy(b->ev_prims);
+	if (b->h_label_extra) (void)hipHostFree(b->h_label_extra);
+	if (b->ev_label_extra) (void)hipEventDestroy(b->ev_label_extra);
 	if (b->h_err) (void)hipHostFree(b->h_err);
 	for (auto &a : b->anchor_stage) {
 		if (a.h) (void)hipHostFree(a.h);
@@ -651,6 +661,7 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	}
 	hm_release(b->fire_hm);
 	hm_release(b->render_hm);
+	hm_release(b->label_hm);
 	if (b->ev_render) (void)hipEventDestroy(b->ev_render);
 	if (b->ev) {
 		for (int r = 0; r < smhv_batch::TIMING_RING; ++r)
@@ -3439,3 +3450,4 @@ extern "C" SMHV_API int smhv_debug_render_rule(uint32_t map_w, uint32_t map_h, f
 }
 
 #include "smh_feed.inc"
+#include "smh_labels.inc"

@@ -143,3 +143,45 @@ class RenderLayers:
         ly.n_prims = n
         ly.prims = C.cast(arr, C.POINTER(L.RenderPrim)) if n else None
         return ly, arr
+
+
+# ---- labels (smhv_batch_render_labels / smhv_render_map_labeled): the firing solution of a line as text beside it -------------
+def label_lines(custom, drag=None, measure=None, drag_threshold=6.0):
+    """The label side of ctl_marker_prims: the lines draw::render (draw.rs:135-198) hands to markers::draw, as ((x0, y0, x1, y1),
+    rgba) in its order -- every custom marker in magenta, `drag` in magenta and `measure` in red, each only when it is at least
+    `drag_threshold` long (is_line_long_enough).  Map-ROI coordinates."""
+    out = [((float(_f32(p0[0])), float(_f32(p0[1])), float(_f32(p1[0])), float(_f32(p1[1]))), CUSTOM_MARKER_COLOR) for p0, p1 in custom]
+    for pair, color in ((drag, CUSTOM_MARKER_COLOR), (measure, MEASURE_MARKER_COLOR)):
+        if pair is not None and _long_enough(pair[0], pair[1], drag_threshold):
+            out.append(((float(_f32(pair[0][0])), float(_f32(pair[0][1])), float(_f32(pair[1][0])), float(_f32(pair[1][1]))), color))
+    return out
+
+
+class LabelOptions:
+    """What a label call draws: `extra` = [((x0, y0, x1, y1), rgba)] (label_lines()), detected = the detected lines too, scale =
+    window pixels per font unit (1 .. 4, 0 = 2), mpx = the per-call path's meters per pixel (a batch takes its records')."""
+
+    def __init__(self, extra=(), detected=True, scale=0, mpx=None):
+        self.extra = list(extra)
+        self.detected = bool(detected)
+        self.scale = int(scale)
+        self.mpx = mpx
+
+    def struct(self):
+        """-> (smhv_label_options, what it points to: keep it alive for the call)."""
+        n = len(self.extra)
+        arr = (L.LabelLine * max(n, 1))()
+        for i, (line, rgba) in enumerate(self.extra):
+            arr[i].line.x0, arr[i].line.y0, arr[i].line.x1, arr[i].line.y1 = line
+            for k in range(4):
+                arr[i].rgba[k] = rgba[k]
+        mpx = C.c_double(self.mpx) if self.mpx is not None else None
+        o = L.LabelOptionsStruct()
+        o.size = C.sizeof(L.LabelOptionsStruct)
+        o.flags = L.LABEL_DETECTED if self.detected else 0
+        o.scale = self.scale
+        o.n_extra = n
+        o.extra = C.cast(arr, C.POINTER(L.LabelLine)) if n else None
+        o.mpx = C.pointer(mpx) if mpx is not None else None
+        return o, (arr, mpx)
+

@@ -245,14 +245,26 @@ class HipVision:
         L.check(self._lib.smhv_heightmap_overlay(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(opt), out.ctypes.data))
         return out
 
-    def render_map(self, viewport, out_w, out_h, lines=None, heightmap=None, fit_to_minimap=True, background=(0, 0, 0, 255), options=None, layers=None):
+    def render_map(self, viewport, out_w, out_h, lines=None, heightmap=None, fit_to_minimap=True, background=(0, 0, 0, 255), options=None, layers=None,
+                   labels=None):
         """The app's map view of the current frame (smhv_render_map; src/ui/map.rs:209-273): the ui_map through `viewport` (a
         MapViewport) into a window of out_w x out_h, the heightmap's overlay when `heightmap` is given, and `lines` (float32
-        [n, 4] in map-ROI coordinates: detected and custom markers) -> uint8 [out_h, out_w, 4] RGBA."""
+        [n, 4] in map-ROI coordinates: detected and custom markers) -> uint8 [out_h, out_w, 4] RGBA.  labels: a LabelOptions
+        (smhv_render_map_labeled): the firing solutions as text beside the lines, drawn over the finished image; the call then
+        returns (image, LabelResult)."""
         from .render import render_options
         ln = np.ascontiguousarray(lines if lines is not None else np.zeros((0, 4)), np.float32).reshape(-1, 4)
         opt = options if options is not None else render_options(viewport, out_w, out_h, heightmap is not None, len(ln) > 0, fit_to_minimap, background)
         out = np.empty((max(int(opt.out_h), 1), max(int(opt.out_w), 1), 4), np.uint8)
+        if labels is not None:
+            lo, keep_labels = labels.struct()
+            ly, keep = layers.struct() if layers is not None else (None, None)
+            res = L.LabelResult()
+            L.check(self._lib.smhv_render_map_labeled(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(opt),
+                                                      C.byref(ly) if ly is not None else None, ln.ctypes.data if len(ln) else None, len(ln), C.byref(lo),
+                                                      out.ctypes.data, C.byref(res)))
+            del keep, keep_labels
+            return out, res
         if layers is not None:                                    # smhv_render_map_layers: prims, the minimap bounds, a debug view as the map
             ly, keep = layers.struct()
             L.check(self._lib.smhv_render_map_layers(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(opt), C.byref(ly),
