@@ -228,7 +228,12 @@ SMHV_API int smhv_batch_layout_get(smhv_batch *b, smhv_batch_layout *out);
 /* Runs the selected stages over n resident frames (d_frames: n * frame_w*frame_h*4 bytes of BGRA8 in
  * device memory) on `stream` (a hipStream_t, NULL = default stream).  Asynchronous and non-blocking: every kernel and
  * copy is enqueued on `stream` and the call returns; results are in device memory when the stream reaches this point.
- * anchors: host array of n smhv_anchors or NULL (copied into pinned staging before the call returns). */
+ * anchors: host array of n smhv_anchors or NULL (copied into pinned staging before the call returns).
+ * Alignment of d_frames (here and in smhv_pipeline_submit / smhv_node_run): a pixel, 4 bytes -- nothing more.  Frames are tightly
+ * packed, so with a width that is no multiple of 4 every row, and every frame after the first, starts 4, 8 or 12 bytes off a
+ * 16-byte boundary anyway; the kernels' 16-byte loads take any 4-byte aligned address and a base pointer at such an offset gives
+ * the same outputs, bit for bit (16-byte alignment and frame_w % 4 == 0 are merely the fastest case).  A pointer that is not
+ * 4-byte aligned is refused with SMHV_E_INVALID before anything is enqueued. */
 SMHV_API int smhv_batch_run(smhv_batch *b, const void *d_frames, uint32_t n, uint32_t stages, int grayscale, uint32_t max_gap,
                             const smhv_anchors *anchors, void *stream);
 /* device pointers of the batch outputs (valid for the life of the batch) */

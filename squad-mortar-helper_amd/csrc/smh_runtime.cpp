@@ -890,6 +890,7 @@ struct SvcPublish { SvcCtl *ctl; unsigned long long *ring; SvcSlot *slots; uint3
 static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint32_t stages, int grayscale, uint32_t max_gap,
                           const smhv_anchors *anchors, hipStream_t s, hipStream_t sl, const SvcPublish *svc = nullptr) {
 	if (!b || !d_frames || n == 0 || n > b->max_frames) return fail(SMHV_E_INVALID, "bad arguments (n=%u, capacity %u)", n, b ? b->max_frames : 0);
+	if ((uintptr_t)d_frames & 3u) return fail(SMHV_E_INVALID, "d_frames is not aligned to a pixel (4 bytes)");
 	CTX_OPEN(b->ctx);
 	if ((stages & (SMHV_STAGE_ALL | SMHV_STAGE_MINIMAP)) == 0) return fail(SMHV_E_INVALID, "no stage selected");
 	if ((stages & SMHV_STAGE_FIRING) && !(stages & SMHV_STAGE_MARKERS)) return fail(SMHV_E_INVALID, "SMHV_STAGE_FIRING needs SMHV_STAGE_MARKERS");
@@ -1734,6 +1735,7 @@ static int mode_control(smhv_pipeline *p, uint32_t n, uint32_t stages, uint32_t 
 extern "C" SMHV_API int smhv_pipeline_submit(smhv_pipeline *p, const void *d_frames, uint32_t n, uint32_t stages, int grayscale, uint32_t max_gap,
                                              const smhv_anchors *anchors, void *after_stream, uint32_t *slot_out) {
 	if (!p) return fail(SMHV_E_INVALID, "null pipeline");
+	if ((uintptr_t)d_frames & 3u) return fail(SMHV_E_INVALID, "d_frames is not aligned to a pixel (4 bytes)");   // (before the submission is counted)
 	CTX_OPEN(p->ctx);
 	HIPCHK(hipSetDevice(p->ctx->device));
 	const uint32_t slot = (uint32_t)(p->submitted % p->depth);

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as o
+from tile_mask_check import check_tile_mask
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -472,34 +473,12 @@ def test_tile_major_mask_of_the_streaming_passes(vision, size):
         for stages, anc in ((smh.STAGE_ALL, anchors), (smh.STAGE_MARKERS, None)):
             fb.run(d.data_ptr(), n, stages=stages, anchors=anc, stream=s)
             for f in sorted(want_mask):
-                tiled, occ, bits, xoff = fb.tile_mask(f)
-                wcols = bits.shape[1]
-                trows = (rh + 7) // 8
                 # whole tile rows per band where that is free or pays (band_rows_for, smh_stream.hip): few frames always (bands of 8 / 16 / 32
                 # rows), full-height bands when the ROI is at most 900 rows tall or 56-row bands need no more bands than the kernel's own
                 cap = 58 if stages == smh.STAGE_ALL else 62
                 expect_tiles = n == 1 or rh <= 900 or -(-rh // 56) == -(-rh // cap)
-                assert (tiled is not None) == expect_tiles, (size, n, stages, f)
-                assert bits.shape == (rh, wcols)
-                # the bit rows are the oracle's mask (bit x + xoff of row y = pixel x)
-                px = np.zeros((rh, wcols * 32), np.uint8)
-                px[:, xoff:xoff + rw] = want_mask[f] != 0
-                want_bits = np.packbits(px.reshape(rh, wcols, 32), axis=2, bitorder="little").view(np.uint32).reshape(rh, wcols)
-                assert np.array_equal(bits, want_bits), (size, n, stages, f)
-                if tiled is None:
-                    continue
-                assert tiled.shape == (trows, wcols, 8)
-                # occupancy == non-empty tiles of those rows; the tiles' words == the rows' words
-                padded = np.zeros((trows * 8, wcols), np.uint32)
-                padded[:rh] = bits
-                by_tile = padded.reshape(trows, 8, wcols).transpose(0, 2, 1)            # [ty, wx, r]
-                nonempty = by_tile.any(axis=2)
-                got_occ = np.unpackbits(occ, axis=1, bitorder="little")[:, :wcols].astype(bool)
-                assert np.array_equal(got_occ, nonempty), (size, n, stages, f, int(nonempty.sum()), int(got_occ.sum()))
-                tail = rh - (trows - 1) * 8                                               # rows of the last tile row inside the image
-                a, b_ = tiled[nonempty], by_tile[nonempty]
-                last = np.repeat(np.arange(trows)[:, None], wcols, axis=1)[nonempty] == trows - 1
-                assert np.array_equal(a[~last], b_[~last]) and np.array_equal(a[last][:, :tail], b_[last][:, :tail]), (size, n, stages, f)
+                # the bit rows are the oracle's mask; occupancy == non-empty tiles of those rows; the tiles' words == the rows' words
+                check_tile_mask(fb, f, want_mask[f], expect_tiles, (size, n, stages, f))
             if n > 1 and fb.tile_mask(n - 1)[1] is not None:
                 assert not fb.tile_mask(n - 1)[1].any()                                   # no marker pixel: every occupancy byte written, all zero
         fb.close()
@@ -641,23 +620,7 @@ def _full_height_bands(vision, W, H, n, forced):
         assert np.array_equal(fb.read_image(smh._lib.VIEW_LSD_INPUT, i), mask_ref), (size, i)
         assert np.array_equal(fb.read_image(smh._lib.VIEW_OCR_INPUT, i), ref["ocr"]), (size, i)
         assert np.array_equal(fb.read_image(smh._lib.VIEW_FIND_SCALES_INPUT, i)[per[i][0]:], ref["scales"][per[i][0]:]), (size, i)
-        tiled, occ, bits, xoff = fb.tile_mask(i)
-        assert (tiled is not None) == bool(tiles.value), (size, i)
-        wcols = bits.shape[1]
-        px = np.zeros((rh, wcols * 32), np.uint8)
-        px[:, xoff:xoff + rw] = mask_ref != 0
-        assert np.array_equal(bits, np.packbits(px.reshape(rh, wcols, 32), axis=2, bitorder="little").view(np.uint32).reshape(rh, wcols)), (size, i)
-        if tiled is not None:
-            trows = (rh + 7) // 8
-            padded = np.zeros((trows * 8, wcols), np.uint32)
-            padded[:rh] = bits
-            by_tile = padded.reshape(trows, 8, wcols).transpose(0, 2, 1)
-            nonempty = by_tile.any(axis=2)
-            assert np.array_equal(np.unpackbits(occ, axis=1, bitorder="little")[:, :wcols].astype(bool), nonempty), (size, i)
-            tail = rh - (trows - 1) * 8
-            a, b_ = tiled[nonempty], by_tile[nonempty]
-            last = np.repeat(np.arange(trows)[:, None], wcols, axis=1)[nonempty] == trows - 1
-            assert np.array_equal(a[~last], b_[~last]) and np.array_equal(a[last][:, :tail], b_[last][:, :tail]), (size, i)
+        check_tile_mask(fb, i, mask_ref, tiles.value, (size, i))
     fb.close()
 
 
