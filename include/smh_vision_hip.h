@@ -795,7 +795,9 @@ SMHV_API int smhv_render_map_labeled(smhv_ctx *ctx, const smhv_heightmap *hm, co
  * producer side of that protocol on the device: it hashes every frame's ui_map where it lies, applies the "changed since the
  * last texture" rule in frame order (the stored CRC lives in device memory and carries over from call to call) and writes the
  * byte-exact messages into one compact buffer, so what crosses to the host is proportional to what changed.  Transport
- * (sockets, HTTP) is the caller's; the debug view that can replace the map (map.rs:210) is not covered: the feed sends the ui_map.
+ * (sockets, HTTP) is the caller's.  The reference shows and sends debug_view.unwrap_or(map) (map.rs:210): with a debug view selected
+ * that view is what is hashed and what goes out as the Map.  smhv_batch_feed_view / smhv_feed_frame_view take the view as
+ * map_source; "the map" below is then that view, at its own width and height.
  * Messages, all little endian, each starting with its u16 id (the macro at lib.rs:74-126 numbers the variants from 1):
  *   UpdateState (state.rs:81-88, lib.rs:154-176): 03 00, f64 metres per pixel (0.0 for None: !has_mpx), then 01 and the record's
  *     minimap[4] = left, right, top, bottom as u32 when has_minimap, else 00.  27 or 11 bytes.
@@ -822,7 +824,8 @@ SMHV_API int smhv_render_map_labeled(smhv_ctx *ctx, const smhv_heightmap *hm, co
                                    something; the feed's stored CRC is neither used nor changed */
 typedef struct smhv_feed smhv_feed;
 typedef struct { uint64_t offset; uint32_t length, frame, kind, crc; } smhv_feed_entry;   /* a message: bytes [offset, offset + length) of the buffer,
-                                   frame = its index in the batch, kind = SMHV_WEB_*, crc = CRC-32 of that frame's ui_map */
+                                   frame = its index in the batch, kind = SMHV_WEB_*, crc = CRC-32 of the Map payload of that frame for
+                                   the call's source (the ui_map, or the debug view given as map_source) */
 typedef struct { uint32_t n_entries, frames_done, n_maps, has_last_crc, last_crc, reserved; uint64_t bytes_used; } smhv_feed_header;   /* bytes_used: the end
                                    of the last message; has_last_crc / last_crc: the stored CRC after the call */
 /* capacity_bytes: the message buffer; max_frames: the most frames one call covers (1 .. 65535) */
@@ -838,6 +841,18 @@ SMHV_API int smhv_feed_reset(smhv_feed *feed);
  * capacity or beyond the feed's max_frames, unknown flags, a batch on another device; SMHV_E_STATE: no run of the batch has
  * produced a ui_map.  A failed call enqueues nothing. */
 SMHV_API int smhv_batch_feed(smhv_batch *b, smhv_feed *feed, uint32_t first, uint32_t n, uint32_t flags, void *stream);
+/* The same with a debug view as the Map (map.rs:210).  map_source = SMHV_VIEW_NONE is smhv_batch_feed, byte for byte; otherwise one
+ * of the five SMHV_VIEW_*: the Map message is 01 00, the VIEW's width and height as u32 and its RGBA bytes -- exactly the bytes
+ * "Map sources" under "map view: layers" pins for a batch ((L, L, L, 255) from the ocr, scales or mask plane; the colour ui_map with
+ * every non-marker pixel (0, 0, 0, 255); the colour ui_map's bottom right quarter, alpha 255), generated from the slabs where they
+ * lie: nothing the size of a batch is materialised.  The "changed since the last texture" rule runs over those bytes.  A feed has ONE
+ * stored CRC whatever the source, as the reference has one texture CRC: a call with another source compares against it, so
+ * switching the source normally sends a Map and switching back sends one again.  UpdateState, Markers, closed and non-OK frames,
+ * SMHV_FEED_SNAPSHOT, the layout, the capacity cut, frames_done and the chaining are unchanged.  SMHV_E_INVALID: an unknown
+ * map_source, or capacity_bytes below one frame's worst case computed with the SOURCE's width and height (brq_w x brq_h = w/2 x h/2
+ * for the OCR input, the scales input and the cropped quarter); SMHV_E_STATE: smhv_batch_render_layers' conditions for the source.
+ * A failed call enqueues nothing and changes nothing. */
+SMHV_API int smhv_batch_feed_view(smhv_batch *b, smhv_feed *feed, uint32_t first, uint32_t n, uint32_t flags, uint32_t map_source, void *stream);
 /* Waits for the feed's last call and copies the header, then n_entries entries (entries may be NULL) and bytes_used bytes (bytes
  * may be NULL) -- nothing else crosses.  SMHV_E_INVALID when max_entries or cap is too small (the header is filled in then). */
 SMHV_API int smhv_feed_read(smhv_feed *feed, smhv_feed_header *header, smhv_feed_entry *entries, uint32_t max_entries, uint8_t *bytes, uint64_t cap);
@@ -849,6 +864,11 @@ SMHV_API int smhv_feed_ptrs(smhv_feed *feed, void **d_header, void **d_entries, 
  * crop_to_map, SMHV_E_STATE when the map is closed. */
 SMHV_API int smhv_feed_frame(smhv_ctx *ctx, smhv_feed *feed, const smhv_line *lines, uint32_t n_lines, const double *mpx, const uint32_t minimap[4],
                              uint32_t flags);
+/* The same with a debug view as the Map: the payload is exactly what smhv_get_debug_view(ctx, map_source, ...) returns at that
+ * moment (the view is drawn into device memory of the feed and hashed there); SMHV_VIEW_NONE is smhv_feed_frame.  Errors as
+ * smhv_feed_frame, the capacity measured with the view's size; SMHV_E_INVALID for an unknown map_source. */
+SMHV_API int smhv_feed_frame_view(smhv_ctx *ctx, smhv_feed *feed, const smhv_line *lines, uint32_t n_lines, const double *mpx, const uint32_t minimap[4],
+                                  uint32_t flags, uint32_t map_source);
 /* The rest of the protocol, host only (no device needed).  Encoders: *len <- the message's length; the message is written when
  * out != NULL and cap >= *len (out == NULL asks for the length), SMHV_E_INVALID when cap is too small.
  *   Markers (lib.rs:142-152): 02 00, custom as a byte, n as u32, n x 4 f32.

@@ -103,6 +103,10 @@ SMHV_API int smhv_debug_render_rule(uint32_t map_w, uint32_t map_h, float sw, fl
  * launch some 2048 workgroups, at most 8: one for a handful of frames, eight for a batch of hundreds), 1 .. 64 = that many.  All
  * give the same CRC; the tests force several so that a batch of a few frames runs the form a large one takes. */
 SMHV_API int smhv_debug_feed_rows(uint32_t rows);
+/* process-wide: how the feed hashes a view made from a one-byte plane (smhv_batch_feed_view with the OCR, scales or LSD input):
+ * 0 = the launcher's rule (one LDS lookup per source byte where a plane row has at most 64 16-byte groups, k_view_crc_gray1),
+ * 4 = always the general kernel's four lookups per message dword.  Both give the same CRC. */
+SMHV_API int smhv_debug_feed_gray_form(uint32_t form);
 /* benchmark driver: a NATIVE capture loop for the ingest queue (the reference's capture thread is native code, src/capture.rs) --
  * n times: smhv_ingest_acquire, stamp the 24-bit value (*counter)++ into pixel (0, 0) of the staging buffer (whose other
  * pixels keep what they last held; (0, 0) lies outside every region the path reads, so every frame hashes differently and

@@ -264,6 +264,9 @@ SIGNATURES = {
     "smhv_web_event_fit": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "smhv_web_interaction_parse": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "smhv_debug_feed_rows": (C.c_int, [C.c_uint32]),
+    "smhv_debug_feed_gray_form": (C.c_int, [C.c_uint32]),
+    "smhv_batch_feed_view": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "smhv_feed_frame_view": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32]),
     "smhv_debug_render_form": (C.c_int, [C.c_uint32]),
     "smhv_debug_render_rule": (C.c_int, [C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

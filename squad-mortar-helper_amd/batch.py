@@ -228,12 +228,17 @@ class FrameBatch:
         L.check(self._lib.smhv_batch_labels_ptr(self._b, C.byref(d)))
         return d.value or 0
 
-    def feed(self, feed, first=0, n=None, snapshot=False, stream=0):
+    def feed(self, feed, first=0, n=None, snapshot=False, stream=0, map_source=L.VIEW_NONE):
         """The web server's events of frames [first, first + n) into `feed` (a WebFeed) on `stream` (smhv_batch_feed):
         UpdateState, Map when the ui_map's CRC-32 differs from the one the feed last sent, Markers -- or, with snapshot, what a
-        client that has just connected gets.  Asynchronous; feed.read() waits for it."""
+        client that has just connected gets.  map_source: a VIEW_* of _lib -- that debug view is hashed and sent as the Map in
+        the ui_map's place (smhv_batch_feed_view).  Asynchronous; feed.read() waits for it."""
         n = self.max_frames - first if n is None else n
-        L.check(self._lib.smhv_batch_feed(self._b, feed._f, first, n, L.FEED_SNAPSHOT if snapshot else 0, C.c_void_p(stream)))
+        flags = L.FEED_SNAPSHOT if snapshot else 0
+        if map_source == L.VIEW_NONE:
+            L.check(self._lib.smhv_batch_feed(self._b, feed._f, first, n, flags, C.c_void_p(stream)))
+        else:
+            L.check(self._lib.smhv_batch_feed_view(self._b, feed._f, first, n, flags, int(map_source), C.c_void_p(stream)))
 
     def read_image(self, which, frame):
         x, y, w, h = self.roi

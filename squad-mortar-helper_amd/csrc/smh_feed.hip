@@ -5,7 +5,9 @@
 //   k_feed_plan   one workgroup: the "changed since the last texture" rule in frame order, message sizes and offsets, the
 //                 capacity cut, header, entries, the new stored CRC, and the bytes of the small messages
 //   k_feed_maps   the Map payloads: pitched rows -> tight, 16-byte aligned payloads, for the frames the plan gave a Map entry
-// and k_feed_tables, which a feed runs once per map geometry (the powers of x the CRC needs).
+// and k_feed_tables, which a feed runs once per map geometry (the powers of x the CRC needs).  With a debug view as the Map
+// (smhv_batch_feed_view) the first and the third are k_view_crc / k_view_crc_gray1 and k_feed_view_maps further down: the same
+// structure over a message generated from its source; these four stay as they are.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -292,8 +294,203 @@ __global__ void __launch_bounds__(FEED_COPY_BS) k_feed_maps(FeedRun r) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// A debug view as the Map (smhv_batch_feed_view): the message no longer lies in memory -- its RGBA bytes are generated from a plane
+// of one byte per pixel (SMH_RND_SRC_GRAY: the ocr, scales or mask slab), from the colour ui slab through the marker predicate
+// (SMH_RND_SRC_PREPROCESS) or from the slab's bottom right quarter (SMH_RND_SRC_CROPPED), exactly the bytes k_render_map_layers
+// samples for that source.  The kernels below are k_map_crc and k_feed_maps over a FeedRun whose ui / ui_pitch / ui_stride / w / h /
+// xoff / quads describe the SOURCE: for the colour sources the ui slab (CROPPED: advanced by rh / 2 rows and by the whole 16-byte
+// groups of m_xoff + rw / 2 pixels, xoff the residual of at most 3 pixels, w x h the quarter's), for a plane its rows, xoff the
+// bytes in front of a row's first pixel and `quads` its 16-byte groups of SIXTEEN pixels.  k_feed_plan takes the same FeedRun as it is.
+// ------------------------------------------------------------------------------------------------
+template <uint32_t SRC>
+static __device__ __forceinline__ uint32_t view_px(uint32_t p) {      // a colour source's message dword from the slab's
+	if (SRC == SMH_RND_SRC_CROPPED) return p | 0xFF000000u;
+	return is_marker(p & 255u, (p >> 8) & 255u, (p >> 16) & 255u) ? (p | 0xFF000000u) : 0xFF000000u;
+}
+static __device__ __forceinline__ uint32_t view_gray(uint32_t l) { return l * 0x00010101u | 0xFF000000u; }
+
+// k_feed_tables with `ppg` message dwords per 16-byte source group (16 for a plane)
+__global__ void __launch_bounds__(256) k_feed_view_tables(uint32_t *tab, uint32_t w, uint32_t h, uint32_t xoff, uint32_t quads, uint32_t ppg) {
+	const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+	if (t < quads) {
+		const uint32_t last = min(ppg * t + (ppg - 1u) - xoff, w - 1u);   // (xoff < ppg)
+		tab[t] = xpow(32ull * (w - 1u - last));
+	} else if (t < quads + h)
+		tab[t] = xpow(32ull * w * (uint64_t)(t - quads));
+}
+
+// k_map_crc over a generated message: the same bands, Horner step, alignments and atomicXor; a group's dwords are made from what
+// was loaded before they are folded.  A plane's group yields sixteen dwords, so there the LDS lookups decide, not the loads.
+template <uint32_t SRC>
+__global__ void __launch_bounds__(FEED_CRC_BS) k_view_crc(FeedRun r) {
+	constexpr uint32_t PPG = SRC == SMH_RND_SRC_GRAY ? 16u : 4u;
+	__shared__ uint32_t tab[4][256], mrow[4][256], wsum[FEED_CRC_BS / 64u];
+	const uint32_t f = blockIdx.y, tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+	if (!r.res[f].map_open || r.res[f].status != SMHV_FRAME_OK) return;
+	{
+		uint32_t c = tid;
+		for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? SMH_CRC_POLY : 0u);
+		tab[0][tid] = c;
+		const uint32_t xrow = r.tab[r.quads + 1u];                               // x^(32 w)
+#pragma unroll
+		for (uint32_t k = 0; k < 4u; ++k) mrow[k][tid] = gf2_mulmod(tid << (8u * k), xrow);
+	}
+	__syncthreads();
+	{
+		uint32_t c = tab[0][tid];
+		for (int k = 1; k < 4; ++k) { c = (c >> 8) ^ tab[0][c & 255u]; tab[k][tid] = c; }
+	}
+	__syncthreads();
+	const uint32_t K = (r.quads + 63u) >> 6;
+	const uint32_t c0 = min(lane * K, r.quads), c1 = min(c0 + K, r.quads);
+	const uint32_t y0 = min((blockIdx.x * (FEED_CRC_BS / 64u) + wv) * r.rows_per_wave, r.h), y1 = min(y0 + r.rows_per_wave, r.h);
+	const uint8_t *frame = r.ui + (size_t)f * r.ui_stride;
+	const int32_t xoff = (int32_t)r.xoff, w = (int32_t)r.w;
+	uint32_t acc = 0;
+	for (uint32_t y = y0; y < y1; ++y) {
+		const uint4 *row = (const uint4 *)(frame + (size_t)y * r.ui_pitch);      // (16-byte aligned: pitch and base are multiples of 16)
+		uint32_t v = 0;
+		for (uint32_t cb = c0; cb < c1; cb += 4u) {
+			uint4 q[4];
+#pragma unroll
+			for (uint32_t u = 0; u < 4u; ++u) q[u] = row[min(cb + u, c1 - 1u)];
+#pragma unroll
+			for (uint32_t u = 0; u < 4u; ++u) {
+				if (cb + u >= c1) break;
+				const uint32_t d[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+				const int32_t j0 = (int32_t)(PPG * (cb + u)) - xoff;                // message dword of the group's first pixel
+#pragma unroll
+				for (uint32_t i = 0; i < PPG; ++i) {
+					if (j0 + (int32_t)i < 0 || j0 + (int32_t)i >= w) continue;
+					const uint32_t m = SRC == SMH_RND_SRC_GRAY ? view_gray((d[i >> 2] >> (8u * (i & 3u))) & 255u) : view_px<SRC>(d[i & 3u]);
+					const uint32_t c = v ^ m;
+					v = tab[3][c & 255u] ^ tab[2][(c >> 8) & 255u] ^ tab[1][(c >> 16) & 255u] ^ tab[0][c >> 24];
+				}
+			}
+		}
+		acc = mrow[0][acc & 255u] ^ mrow[1][(acc >> 8) & 255u] ^ mrow[2][(acc >> 16) & 255u] ^ mrow[3][acc >> 24] ^ v;
+	}
+	if (c0 < c1 && y0 < y1) acc = gf2_mulmod(acc, r.tab[c1 - 1u]); else acc = 0u;
+	acc = wave_xor32_dpp(acc);
+	if (lane == 0u) wsum[wv] = y0 < y1 ? gf2_mulmod(acc, r.tab[r.quads + (r.h - y1)]) : 0u;
+	__syncthreads();
+	if (tid == 0u) {
+		uint32_t x = 0;
+		for (uint32_t k = 0; k < FEED_CRC_BS / 64u; ++k) x ^= wsum[k];
+		atomicXor(r.raw + f, x);
+	}
+}
+
+// The plane's CRC with ONE lookup per source byte, for rows of at most 64 groups (a lane has one group per row).  A grey dword takes
+// 256 values and a lane starts every row from remainder 0, so its remainder over the n dwords of its group is XOR_i G[n - i][L_i],
+// G[p][L] = R(grey(L)) x^(32 (p - 1)): sixteen independent lookups and an xor tree in the place of 64 dependent ones.  A thread
+// builds column `tid` of G with the slice-by-4 step on a zero dword (G[p + 1] = G[p] x^32).  16 KB of LDS more.
+__global__ void __launch_bounds__(FEED_CRC_BS) k_view_crc_gray1(FeedRun r) {
+	__shared__ uint32_t tab[4][256], mrow[4][256], G[17][256], wsum[FEED_CRC_BS / 64u];
+	const uint32_t f = blockIdx.y, tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+	if (!r.res[f].map_open || r.res[f].status != SMHV_FRAME_OK) return;
+	{
+		uint32_t c = tid;
+		for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? SMH_CRC_POLY : 0u);
+		tab[0][tid] = c;
+		const uint32_t xrow = r.tab[r.quads + 1u];
+#pragma unroll
+		for (uint32_t k = 0; k < 4u; ++k) mrow[k][tid] = gf2_mulmod(tid << (8u * k), xrow);
+	}
+	__syncthreads();
+	{
+		uint32_t c = tab[0][tid];
+		for (int k = 1; k < 4; ++k) { c = (c >> 8) ^ tab[0][c & 255u]; tab[k][tid] = c; }
+	}
+	__syncthreads();
+	{
+		uint32_t c = view_gray(tid);
+		G[0][tid] = 0u;                                                          // (p = 0: a dword that is not the message's)
+		for (uint32_t p = 1; p <= 16u; ++p) {
+			c = tab[3][c & 255u] ^ tab[2][(c >> 8) & 255u] ^ tab[1][(c >> 16) & 255u] ^ tab[0][c >> 24];
+			G[p][tid] = c;
+		}
+	}
+	__syncthreads();
+	const bool live = lane < r.quads;                                            // (quads <= 64: the launcher's condition)
+	const uint32_t y0 = min((blockIdx.x * (FEED_CRC_BS / 64u) + wv) * r.rows_per_wave, r.h), y1 = min(y0 + r.rows_per_wave, r.h);
+	const uint8_t *frame = r.ui + (size_t)f * r.ui_stride + 16u * (live ? lane : 0u);
+	const int32_t j0 = (int32_t)(16u * lane) - (int32_t)r.xoff;                   // message dword of the group's first pixel
+	const int32_t pend = min(16, (int32_t)r.w - j0);                              // dwords from it to the group's last message dword
+	uint32_t pos[16];                                                            // G's row of source byte i; 0 where the byte is not the message's
+#pragma unroll
+	for (int32_t i = 0; i < 16; ++i) pos[i] = (live && j0 + i >= 0 && i < pend) ? (uint32_t)(pend - i) : 0u;
+	uint32_t acc = 0;
+	for (uint32_t y = y0; y < y1; ++y) {
+		const uint4 q = *(const uint4 *)(frame + (size_t)y * r.ui_pitch);
+		const uint32_t d[4] = {q.x, q.y, q.z, q.w};
+		uint32_t v = 0;
+#pragma unroll
+		for (uint32_t i = 0; i < 16u; ++i) v ^= G[pos[i]][(d[i >> 2] >> (8u * (i & 3u))) & 255u];
+		acc = mrow[0][acc & 255u] ^ mrow[1][(acc >> 8) & 255u] ^ mrow[2][(acc >> 16) & 255u] ^ mrow[3][acc >> 24] ^ v;
+	}
+	if (live && y0 < y1) acc = gf2_mulmod(acc, r.tab[lane]); else acc = 0u;
+	acc = wave_xor32_dpp(acc);
+	if (lane == 0u) wsum[wv] = y0 < y1 ? gf2_mulmod(acc, r.tab[r.quads + (r.h - y1)]) : 0u;
+	__syncthreads();
+	if (tid == 0u) {
+		uint32_t x = 0;
+		for (uint32_t k = 0; k < FEED_CRC_BS / 64u; ++k) x ^= wsum[k];
+		atomicXor(r.raw + f, x);
+	}
+}
+
+// k_feed_maps for a view: destination driven as it is -- a lane owns four pixels of the payload, finds them in (row, column),
+// makes their dwords from the source (a plane: four byte loads) and stores them as one aligned 16-byte store.
+template <uint32_t SRC>
+__global__ void __launch_bounds__(FEED_COPY_BS) k_feed_view_maps(FeedRun r) {
+	const uint32_t n_maps = r.header->n_maps;
+	if (!n_maps) return;
+	const uint32_t dwords = r.w * r.h;
+	const uint32_t groups = (dwords + 3u) >> 2, per_item = FEED_COPY_BS * FEED_COPY_GROUPS;
+	const uint32_t items_per_map = (groups + per_item - 1u) / per_item;
+	const uint64_t items = (uint64_t)n_maps * items_per_map;
+	const uint32_t pitch_px = SRC == SMH_RND_SRC_GRAY ? (uint32_t)r.ui_pitch : (uint32_t)(r.ui_pitch >> 2);
+	for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
+		const uint32_t m = (uint32_t)(item / items_per_map), ib = (uint32_t)(item - (uint64_t)m * items_per_map);
+		const FeedMap fm = r.maps[m];
+		const uint8_t *src8 = r.ui + (size_t)fm.frame * r.ui_stride + r.xoff;
+		const uint32_t *src32 = (const uint32_t *)(r.ui + (size_t)fm.frame * r.ui_stride) + r.xoff;
+		uint8_t *dst = r.bytes + fm.dst;
+		uint32_t d[FEED_COPY_GROUPS][4];
+#pragma unroll
+		for (uint32_t u = 0; u < FEED_COPY_GROUPS; ++u) {
+			const uint32_t g = ib * per_item + u * FEED_COPY_BS + threadIdx.x;
+			uint32_t q = min(4u * g, dwords - 1u), row = q / r.w, col = q - row * r.w;
+#pragma unroll
+			for (uint32_t k = 0; k < 4u; ++k) {
+				const size_t at = (size_t)row * pitch_px + col;                              // (clamped to the view's last pixel: always inside the frame)
+				d[u][k] = SRC == SMH_RND_SRC_GRAY ? (uint32_t)src8[at] : src32[at];
+				if (q + 1u < dwords) { ++q; if (++col == r.w) { col = 0u; ++row; } }
+			}
+		}
+#pragma unroll
+		for (uint32_t u = 0; u < FEED_COPY_GROUPS; ++u) {
+			const uint32_t g = ib * per_item + u * FEED_COPY_BS + threadIdx.x;
+			if (g >= groups) continue;
+			uint32_t o[4];
+#pragma unroll
+			for (uint32_t k = 0; k < 4u; ++k) o[k] = SRC == SMH_RND_SRC_GRAY ? view_gray(d[u][k]) : view_px<SRC>(d[u][k]);
+			if (4u * g + 4u <= dwords) *(uint4 *)(dst + 16ull * g) = make_uint4(o[0], o[1], o[2], o[3]);
+			else
+				for (uint32_t k = 0; 4u * g + k < dwords; ++k) *(uint32_t *)(dst + 16ull * g + 4u * k) = o[k];
+		}
+	}
+}
+
+// ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
+hipError_t launch_feed_view_tables(uint32_t *d_tab, uint32_t w, uint32_t h, uint32_t xoff, uint32_t quads, uint32_t ppg, hipStream_t s) {
+	hipLaunchKernelGGL(k_feed_view_tables, dim3((quads + h + 255u) / 256u), dim3(256), 0, s, d_tab, w, h, xoff, quads, ppg);
+	return hipGetLastError();
+}
+
 hipError_t launch_feed_tables(uint32_t *d_tab, uint32_t w, uint32_t h, uint32_t xoff, uint32_t quads, hipStream_t s) {
 	hipLaunchKernelGGL(k_feed_tables, dim3((quads + h + 255u) / 256u), dim3(256), 0, s, d_tab, w, h, xoff, quads);
 	return hipGetLastError();
@@ -314,6 +511,45 @@ hipError_t launch_feed(const FeedRun &r, hipStream_t s) {
 	if (e != hipSuccess) return e;
 	const uint32_t band = (FEED_CRC_BS / 64u) * r.rows_per_wave;
 	hipLaunchKernelGGL(k_map_crc, dim3((r.h + band - 1u) / band, r.n), dim3(FEED_CRC_BS), 0, s, r);
+	hipLaunchKernelGGL(k_feed_plan, dim3(1), dim3(FEED_PLAN_BS), 0, s, r);
+	hipLaunchKernelGGL(k_feed_maps, dim3(2048), dim3(FEED_COPY_BS), 0, s, r);
+	return hipGetLastError();
+}
+
+// a plane's CRC: 0 = the rule (one lookup per source byte where a row has at most 64 groups), 4 = four per message dword always
+static std::atomic<uint32_t> g_feed_gray_form{0};       // smhv_debug_feed_gray_form
+void feed_set_gray_form(uint32_t form) { g_feed_gray_form.store(form, std::memory_order_relaxed); }
+
+hipError_t launch_feed_view(const FeedRun &r, uint32_t src_mode, hipStream_t s) {
+	hipError_t e = hipMemsetAsync(r.raw, 0, sizeof(uint32_t) * r.n, s);
+	if (e != hipSuccess) return e;
+	const uint32_t band = (FEED_CRC_BS / 64u) * r.rows_per_wave;
+	const dim3 grid((r.h + band - 1u) / band, r.n), bs(FEED_CRC_BS);
+	switch (src_mode) {
+	case SMH_RND_SRC_GRAY:
+		if (r.quads <= 64u && g_feed_gray_form.load(std::memory_order_relaxed) != 4u) hipLaunchKernelGGL(k_view_crc_gray1, grid, bs, 0, s, r);
+		else hipLaunchKernelGGL(k_view_crc<SMH_RND_SRC_GRAY>, grid, bs, 0, s, r);
+		break;
+	case SMH_RND_SRC_PREPROCESS: hipLaunchKernelGGL(k_view_crc<SMH_RND_SRC_PREPROCESS>, grid, bs, 0, s, r); break;
+	case SMH_RND_SRC_CROPPED: hipLaunchKernelGGL(k_view_crc<SMH_RND_SRC_CROPPED>, grid, bs, 0, s, r); break;
+	default: return hipErrorInvalidValue;
+	}
+	hipLaunchKernelGGL(k_feed_plan, dim3(1), dim3(FEED_PLAN_BS), 0, s, r);
+	switch (src_mode) {
+	case SMH_RND_SRC_GRAY: hipLaunchKernelGGL(k_feed_view_maps<SMH_RND_SRC_GRAY>, dim3(2048), dim3(FEED_COPY_BS), 0, s, r); break;
+	case SMH_RND_SRC_PREPROCESS: hipLaunchKernelGGL(k_feed_view_maps<SMH_RND_SRC_PREPROCESS>, dim3(2048), dim3(FEED_COPY_BS), 0, s, r); break;
+	default: hipLaunchKernelGGL(k_feed_view_maps<SMH_RND_SRC_CROPPED>, dim3(2048), dim3(FEED_COPY_BS), 0, s, r); break;
+	}
+	return hipGetLastError();
+}
+
+// The per-call path's view: one tight RGBA8 image.  `crc` describes it as rows of 1024 dwords behind a lead-in of zero dwords (leading
+// zeros do not change the remainder), `r` as what it is -- the plan's and the copy's dimensions.
+hipError_t launch_feed_image(const FeedRun &crc, const FeedRun &r, hipStream_t s) {
+	hipError_t e = hipMemsetAsync(r.raw, 0, sizeof(uint32_t) * r.n, s);
+	if (e != hipSuccess) return e;
+	const uint32_t band = (FEED_CRC_BS / 64u) * crc.rows_per_wave;
+	hipLaunchKernelGGL(k_map_crc, dim3((crc.h + band - 1u) / band, crc.n), dim3(FEED_CRC_BS), 0, s, crc);
 	hipLaunchKernelGGL(k_feed_plan, dim3(1), dim3(FEED_PLAN_BS), 0, s, r);
 	hipLaunchKernelGGL(k_feed_maps, dim3(2048), dim3(FEED_COPY_BS), 0, s, r);
 	return hipGetLastError();

@@ -524,5 +524,15 @@ hipError_t launch_feed_tables(uint32_t *d_tab, uint32_t w, uint32_t h, uint32_t 
 uint32_t feed_rows_per_wave(uint32_t h, uint32_t n);
 void feed_set_rows(uint32_t rows);   // diagnostic: rows per wave of every k_map_crc launch (0 = the rule)
 hipError_t launch_feed(const FeedRun &r, hipStream_t s);   // CRC, plan, compacting copy
+// A debug view as the Map (smhv_batch_feed_view / smhv_feed_frame_view).  launch_feed_view: the same three steps over a message
+// GENERATED from the source the FeedRun describes (src_mode = SMH_RND_SRC_GRAY / PREPROCESS / CROPPED; smh_feed.hip says what
+// ui, ui_pitch, ui_stride, w, h, xoff and quads mean for each); its tables come from launch_feed_view_tables with ppg = 16 message
+// dwords per 16-byte group for a plane, 4 for the colour sources (= launch_feed_tables).  launch_feed_image: one tight RGBA8
+// image (the per-call path's materialised view) -- `crc` describes it to k_map_crc, `r` to the plan and the copy.
+#define SMH_FEED_IMAGE_ROW 1024u         // dwords per row of launch_feed_image's description of a tight image
+hipError_t launch_feed_view_tables(uint32_t *d_tab, uint32_t w, uint32_t h, uint32_t xoff, uint32_t quads, uint32_t ppg, hipStream_t s);
+hipError_t launch_feed_view(const FeedRun &r, uint32_t src_mode, hipStream_t s);
+hipError_t launch_feed_image(const FeedRun &crc, const FeedRun &r, hipStream_t s);
+void feed_set_gray_form(uint32_t form);   // diagnostic: 0 = the rule, 4 = a plane's CRC with four lookups per message dword always
 
 }  // namespace smh

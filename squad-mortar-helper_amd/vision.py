@@ -275,14 +275,19 @@ class HipVision:
                                           len(ln), out.ctypes.data))
         return out
 
-    def feed_frame(self, feed, lines, mpx=None, minimap=None, snapshot=False):
+    def feed_frame(self, feed, lines, mpx=None, minimap=None, snapshot=False, map_source=L.VIEW_NONE):
         """The web server's events of the current frame into `feed` (a WebFeed; smhv_feed_frame): the ui_map crop_to_map left on
         the device, `lines` (float32 [n, 4], n <= 32: the detected markers), mpx (None: none) and minimap = (left, right, top,
-        bottom) or None.  feed.read() hands the messages out."""
+        bottom) or None.  map_source: a VIEW_* of _lib -- the Map is get_debug_view's image of this moment in the ui_map's place
+        (smhv_feed_frame_view).  feed.read() hands the messages out."""
         ln = np.ascontiguousarray(lines if lines is not None else np.zeros((0, 4)), np.float32).reshape(-1, 4)
         m = C.byref(C.c_double(float(mpx))) if mpx is not None else None
         mm = (C.c_uint32 * 4)(*[int(v) for v in minimap]) if minimap is not None else None
-        L.check(self._lib.smhv_feed_frame(self._ctx, feed._f, ln.ctypes.data if len(ln) else None, len(ln), m, mm, L.FEED_SNAPSHOT if snapshot else 0))
+        flags = L.FEED_SNAPSHOT if snapshot else 0
+        if map_source == L.VIEW_NONE:
+            L.check(self._lib.smhv_feed_frame(self._ctx, feed._f, ln.ctypes.data if len(ln) else None, len(ln), m, mm, flags))
+        else:
+            L.check(self._lib.smhv_feed_frame_view(self._ctx, feed._f, ln.ctypes.data if len(ln) else None, len(ln), m, mm, flags, int(map_source)))
 
     def debug_marker_table(self):
         bits = np.empty((1 << 24) // 32, np.uint32)

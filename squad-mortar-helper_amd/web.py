@@ -1,5 +1,7 @@
 """The remote-viewer feed (smhv_feed_* / smhv_batch_feed / smhv_feed_frame): the reference web server's events of every processed
-frame (web/src/lib.rs:127-214), written on the device, and the host-only rest of its protocol.  Transport is the caller's: a
+frame (web/src/lib.rs:127-214), written on the device, and the host-only rest of its protocol.  FrameBatch.feed and
+HipVision.feed_frame take map_source = a VIEW_* of _lib: that debug view is hashed and sent as the Map in the ui_map's place
+(smhv_batch_feed_view / smhv_feed_frame_view; src/ui/map.rs:210).  Transport is the caller's: a
 message from WebFeed.read() or an encoder is what the reference hands its websocket as one binary frame."""
 import ctypes as C
 
