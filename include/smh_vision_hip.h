@@ -657,8 +657,8 @@ SMHV_API int smhv_render_map(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv
  *      a.y + 1.0f <= cy && cy < b.y - 1.0f): a HARD-EDGED 1 px frame in the place of imgui's stroke of the rectangle [a + 0.5,
  *      b - 0.5] with thickness 1.  A rectangle narrower or flatter than 2 is filled; a degenerate or NaN one paints nothing.
  *      SMHV_LAYER_MINIMAP_BOUNDS: when rec.has_minimap, a RECT with corners ((float)left, (float)top), ((float)right, (float)bottom)
- *      with SMHV_PRIM_SHIFT1 (debug.rs:326-329), colour (0, 255, 0); without a rectangle nothing.  The reference's text is not drawn here (its
- *      "Minimap bounds" caption; the marker labels are: "map view: labels").
+ *      with SMHV_PRIM_SHIFT1 (debug.rs:326-329), colour (0, 255, 0); without a rectangle nothing.  The reference's text is not drawn here (the
+ *      marker labels are "map view: labels", the Debug menu's text is "map view: debug text and the vision debugger").
  * Two identities: with n_prims = 0, flags = 0 and map_source = SMHV_VIEW_NONE the image is smhv_batch_render's / smhv_render_map's,
  * byte for byte; with the identity viewport at the view's size and nothing else the image is the view (smhv_get_debug_view's on the
  * per-call path).
@@ -787,6 +787,114 @@ SMHV_API int smhv_batch_labels_ptr(smhv_batch *b, void **d_labels);
 SMHV_API int smhv_render_map_labeled(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_render_layers *layers,
                                      const smhv_line *lines, uint32_t n_lines, const smhv_label_options *lopt, uint8_t *rgba,
                                      smhv_label_result *labels);
+
+/* ---- map view: debug text and the vision debugger ---------------------------------------------------------------------------
+ * What is left of the reference's window: the vision debugger (src/ui/debug.rs:350-475: RGB, HSV, Luma8, ocr_monochromaticy,
+ * ocr_brightness and the three tests of debug_is_map_marker_color per fireteam, for the pixel under the cursor, printed in a small
+ * window beside it), the text of the Debug menu's overlays (debug.rs:286-345: "{:.2}%\n{:?}" under every OCR box, "{}m" at every
+ * scale bar, the red caption when a frame has no minimap rectangle).  The numbers come from k_probe, the picture is a pass of its
+ * own over a finished image of the map view, as the labels are.  imgui's text and windows are not bit-reproducible: the library
+ * pins ONE hard-edged restatement.  Every f32 operation is one operation, left to right, unfused.  W, H = out_w, out_h; sw, sh,
+ * tx, ty = the render call's viewport (a scale of 0 means 1); S = smhv_debug_options.scale, 1 .. 4, 0 means 2, one value per call.
+ * Font.  csrc/smh_font5x7_ascii.h: 97 glyphs in the label font's format and 6 x 9 cell -- the printable ASCII bytes 0x20 .. 0x7E,
+ *   the degree sign 0xB0 and the plus-minus sign 0xB1; the label font's 27 glyphs have the same rows.  Drawn for this project.
+ * Text runs.  A run = a position (x, y), rgba (alpha 255), flags, n <= SMHV_TEXT_MAX_BYTES text bytes; '\n' starts a new line at the
+ *   run's x; a run has 1 + (number of '\n') lines, at most SMHV_TEXT_MAX_LINES (n == 0: one empty line).  The anchor P: with
+ *   SMHV_TEXT_MAP_COORDS (x * sw + tx, y * sh + ty), otherwise (x, y) in window pixels.  Pixel (X, Y): cx = X + 0.5f, cy = Y + 0.5f;
+ *   u = (cx - P.x) / (float)S, v = (cy - P.y) / (float)S; iu = floorf(u), iv = floorf(v).  Painted iff iu >= 0, iv >= 0, line = iv / 9 is
+ *   less than the run's number of lines, iu / 6 is less than that line's number of characters, and the glyph of character iu / 6 of
+ *   that line has its bit at column iu % 6 (< 5) and row iv % 9 - 1 (0 .. 6).  A run whose anchor is not finite paints nothing.
+ *   Colour = the run's RGB, alpha 255.  The same list for every frame of a call.
+ * Probe (debug.rs:357-385).  A window position (mx, my), the same for every frame of the call -> one smhv_probe per frame and
+ *   position.  Every field is 0 (valid = 0) when the frame's map is closed or mx == FLT_MAX && my == FLT_MAX.  ix = (mx - tx) / sw,
+ *   iy = (my - ty) / sh (MapViewport::inverse_xy); invalid if ix < 0 || iy < 0 (a NaN passes, as in the reference); px = ix as u32,
+ *   py = iy as u32 (truncating, saturating, NaN -> 0); invalid if px >= w || py >= h (get_pixel_checked).  An invalid probe is all 0.
+ *   rgb = the ui_map's pixel (px, py) as the batch or context holds it (after a grayscale run: the gray bytes).
+ *   h, s, v = util/src/image.rs:159-187 in f32: r = R / 255.0f (g, b likewise); mx = max, mn = min, d = mx - mn; hue = 0 if mx == mn,
+ *     else 60 * ((g - b) / d) if mx == r, else 60 * (((b - r) / d) + 2) if mx == g, else 60 * (((r - g) / d) + 4); hue < 0: hue + 360;
+ *     h = hue as u16, s = ((100 * d) / mx) as u8 (NaN -> 0), v = (100 * mx) as u8 -- the operations of the marker predicate.
+ *   luma = image 0.23.14's luma8: ((0.2126f * R + 0.7152f * G) + 0.0722f * B) as u8.  mono = the sum over all nine (a, b) of
+ *     |p[a] - p[b]| (ocr_monochromaticy), brightness = the minimum channel (ocr_brightness).
+ *   team_bits: bit 3 * team + k, team 0 = Alpha, 1 = Bravo, 2 = Charlie, (mh, ms, mv) that team's colour (smh_consts.h):
+ *     k = 0: |mh - h| <= HUE_TOLERANCE; k = 1: s >= MIN_SAT && (|ms - s| <= SAT_TOLERANCE || |s - (ms - PLAYER_DIR_ARC_SAT)| <=
+ *     SAT_TOLERANCE); k = 2: |mv - v| <= VIB_TOLERANCE.  "Some team has all three bits" is the predicate the pipeline runs.
+ *   Text: smhv_probe_text writes the reference's string, eight lines joined by '\n': "RGB [r, g, b]", "HSV [h, s, v]", "Luma8 l",
+ *     "OCRPixelSimilarity mono", "OCRBrightness brightness", "AlphaMarker [b0, b1, b2]", "BravoMarker [..]", "CharlieMarker [..]"
+ *     with true / false for the bits.  The device builds the same bytes when it draws.
+ * The debugger's picture (SMHV_DEBUG_DRAW_PROBES), for every valid probe, in list order.  C = the widest of the eight lines in
+ *   characters; Wd = (float)(6 * S * C + 16), Hd = (float)(34 + 72 * S) (padding 8, swatch 10, 8, eight lines, 8).  THIS DEVIATES
+ *   from the reference: the window is sized to its text in the place of imgui's wrapped 200 px window, and its background is
+ *   opaque.  wp = (mx + 15.0f, my + 15.0f); if wp.x + Wd > (float)W || wp.y + Hd > (float)H then wp = ((mx - Wd) - 5.0f, (my - Hd) -
+ *   5.0f) (debug.rs:415-420).  A fill of [a, b) paints pixel centres with a.x <= cx && cx < b.x && a.y <= cy && cy < b.y.  Painted in
+ *   this order, later over earlier: (1) the fill [wp, (wp.x + Wd, wp.y + Hd)) in (15, 15, 15) (theme.rs:24, opaque); (2) the text
+ *   as one run at (wp.x + 8.0f, wp.y + 26.0f) in (255, 255, 255); (3) the swatch, the fill [(wp.x + 8.0f, wp.y + 8.0f), ((wp.x + Wd) -
+ *   8.0f, wp.y + 18.0f)) in rgb; (4) the pixel frame (debug.rs:444-463): pw = floorf(sw), ph = floorf(sh), ax = mx, ay = my; if pw > 1
+ *   then ax = ax - fmodf(ax, pw); if ph > 1 then ay = ay - fmodf(ay, ph); corners (ax - pw, ay - ph) and (ax + ph, ay + ph) -- the
+ *   reference's ph in both coordinates of the second corner is kept -- drawn by the SMHV_PRIM_RECT rule of "map view: layers" on
+ *   these window coordinates, in (0, 0, 0) when ((float)r * 0.299f + (float)g * 0.587f) + (float)b * 0.114f > 186.0f, else (255, 255, 255).
+ * The caption (SMHV_DEBUG_MINIMAP_CAPTION, debug.rs:335-343): a frame whose record has has_minimap == 0 (per call: the context's
+ *   frame without a rectangle) gets "No minimap bounds detected or we don't need to detect them" in (255, 0, 0) as a window run at
+ *   (10.0f, ((float)H - 10.0f) - (float)(9 * S)).
+ * Paint order of the pass: the runs in list order, the caption, the probes; later over earlier, and everything over all that is
+ *   already in the image -- THIS DEVIATES from the reference as the labels do: text always wins over strokes drawn before.  A frame
+ *   whose map is closed gets nothing at all.  The reference's draw_fps (host wall times) and imgui's chrome are not drawn. */
+#define SMHV_TEXT_MAX_RUNS 64u
+#define SMHV_TEXT_MAX_BYTES 64u
+#define SMHV_TEXT_MAX_LINES 8u
+#define SMHV_TEXT_MAP_COORDS 1u       /* smhv_text_run.flags: (x, y) are map-ROI coordinates, through the viewport */
+#define SMHV_MAX_PROBES 16u
+#define SMHV_DEBUG_DRAW_PROBES 1u     /* smhv_debug_options.flags: the debugger's picture for every valid probe */
+#define SMHV_DEBUG_MINIMAP_CAPTION 2u /*   ... the red caption on frames without a minimap rectangle */
+typedef struct { float x, y; uint8_t rgba[4]; uint32_t flags; uint32_t n; uint8_t text[SMHV_TEXT_MAX_BYTES]; } smhv_text_run;   /* 84 bytes */
+typedef struct { float x, y; } smhv_probe_point;                      /* window pixels */
+typedef struct {
+	uint32_t valid, px, py;
+	uint8_t rgb[3], luma;
+	uint16_t h; uint8_t s, v;
+	uint16_t mono; uint8_t brightness, reserved0;
+	uint32_t team_bits;                /* bit 3 * team + k */
+	uint32_t reserved1;
+} smhv_probe;                          /* 32 bytes */
+typedef struct {
+	uint32_t size;                     /* sizeof(smhv_debug_options) */
+	uint32_t flags;                    /* SMHV_DEBUG_* */
+	uint32_t scale;                    /* S: 1 .. 4, 0 = 2 */
+	uint32_t n_runs;                   /* <= SMHV_TEXT_MAX_RUNS */
+	const smhv_text_run *runs;         /* host memory; copied before the call returns; the same list for every frame of the call */
+	uint32_t n_probes, reserved;       /* <= SMHV_MAX_PROBES */
+	const smhv_probe_point *probes;    /* host memory, likewise */
+} smhv_debug_options;
+/* A glyph of the text font: rows[0 .. 6], bit 4 = the leftmost column.  Host only.  SMHV_E_INVALID for a byte outside the 97. */
+SMHV_API int smhv_text_font(uint8_t ch, uint8_t rows[7]);
+/* The debugger's string of a probe, NUL-terminated (at most 200 bytes with the NUL).  Host only.  SMHV_E_INVALID when cap is too small. */
+SMHV_API int smhv_probe_text(const smhv_probe *p, char *out, size_t cap);
+/* The numbers without any pixels: probes frames [first, first + n) at n_points <= SMHV_MAX_PROBES window positions through ropt's
+ * viewport (nothing else of ropt is used but its size field), asynchronously on `stream`, into the batch's probe slab:
+ * SMHV_MAX_PROBES smhv_probe per frame (allocated by the first call; entries beyond n_points are zeroed).  Needs a ui_map in the
+ * batch (SMHV_E_STATE), no render.  SMHV_E_INVALID: null or wrongly sized ropt, n == 0 or a range beyond the capacity, n_points >
+ * SMHV_MAX_PROBES, n_points != 0 with points == NULL.  The points cross through pinned staging of the batch under the rule the prims
+ * follow.  A failed call enqueues nothing. */
+SMHV_API int smhv_batch_probe(smhv_batch *b, uint32_t first, uint32_t n, const smhv_render_options *ropt, const smhv_probe_point *points,
+                              uint32_t n_points, void *stream);
+/* read: synchronising host copy of SMHV_MAX_PROBES * n entries; ptr: the device address (SMHV_E_STATE before the first probe) */
+SMHV_API int smhv_batch_read_probes(smhv_batch *b, uint32_t first, uint32_t n, smhv_probe *out);
+SMHV_API int smhv_batch_probes_ptr(smhv_batch *b, void **d_probes);
+/* The pass over the batch's render slab, frames [first, first + n), asynchronously on `stream`, behind whatever the batch's
+ * previous render, label or debug call enqueued; writes the probe slab too (dopt's probes).  ropt: the window (the most recent
+ * render's: SMHV_E_STATE for another size or before the first render) and the viewport.  SMHV_E_INVALID: what smhv_batch_render
+ * rejects in ropt (no heightmap is needed), a wrong size, unknown flags, scale > 4, n_runs > SMHV_TEXT_MAX_RUNS, n_probes >
+ * SMHV_MAX_PROBES, a null list with a non-zero count, a run with n > SMHV_TEXT_MAX_BYTES, more than SMHV_TEXT_MAX_LINES lines, a byte
+ * that has no glyph and is not '\n', rgba[3] != 255 or an unknown flag.  A failed call enqueues nothing.  Works on a plain batch and
+ * on a pipeline slot's batch.  The first call that draws allocates the batch's item lists and string pool (about 12.5 KB per frame of
+ * the batch's capacity); smhv_batch_probe allocates the probe slab alone. */
+SMHV_API int smhv_batch_render_debug(smhv_batch *b, uint32_t first, uint32_t n, const smhv_render_options *ropt, const smhv_debug_options *dopt,
+                                     void *stream);
+/* The per-call path: exactly smhv_render_map_labeled's image (lopt == NULL: smhv_render_map_layers's, or smhv_render_map's with
+ * layers == NULL too; `labels` is then not written), then this pass; one copy out.  probes (optional) receives SMHV_MAX_PROBES
+ * entries.  With no runs, no probes and no flags the image is that call's, byte for byte.  Errors as those calls and as above. */
+SMHV_API int smhv_render_map_debug(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_render_layers *layers,
+                                   const smhv_line *lines, uint32_t n_lines, const smhv_label_options *lopt, const smhv_debug_options *dopt,
+                                   uint8_t *rgba, smhv_label_result *labels, smhv_probe *probes);
 
 /* ---- remote-viewer feed: the web server's events of every processed frame ----------------------------------------------
  * The outward interface of a processed frame in the reference is the event stream of its web server (web/src/lib.rs:127-214),

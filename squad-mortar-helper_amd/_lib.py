@@ -126,6 +126,34 @@ class LabelResult(C.Structure):
     _fields_ = [("n_labels", C.c_uint32), ("reserved", C.c_uint32), ("label", Label * LABEL_SLOTS)]
 
 
+TEXT_MAX_RUNS, TEXT_MAX_BYTES, TEXT_MAX_LINES, TEXT_MAP_COORDS = 64, 64, 8, 1
+MAX_PROBES = 16
+DEBUG_DRAW_PROBES, DEBUG_MINIMAP_CAPTION = 1, 2   # smhv_debug_options.flags
+
+
+class TextRun(C.Structure):
+    """smhv_text_run: a run of debug text, its anchor and colour (84 bytes)."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("rgba", C.c_uint8 * 4), ("flags", C.c_uint32), ("n", C.c_uint32), ("text", C.c_uint8 * TEXT_MAX_BYTES)]
+
+
+class ProbePoint(C.Structure):
+    """smhv_probe_point: a window position of the vision debugger."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float)]
+
+
+class Probe(C.Structure):
+    """smhv_probe: what the vision debugger prints about the pixel under a window position (32 bytes)."""
+    _fields_ = [("valid", C.c_uint32), ("px", C.c_uint32), ("py", C.c_uint32), ("rgb", C.c_uint8 * 3), ("luma", C.c_uint8), ("h", C.c_uint16),
+                ("s", C.c_uint8), ("v", C.c_uint8), ("mono", C.c_uint16), ("brightness", C.c_uint8), ("reserved0", C.c_uint8),
+                ("team_bits", C.c_uint32), ("reserved1", C.c_uint32)]
+
+
+class DebugOptionsStruct(C.Structure):
+    """smhv_debug_options: the text runs, the probes and the switches of a debug pass."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("scale", C.c_uint32), ("n_runs", C.c_uint32), ("runs", C.POINTER(TextRun)),
+                ("n_probes", C.c_uint32), ("reserved", C.c_uint32), ("probes", C.POINTER(ProbePoint))]
+
+
 class FeedEntry(C.Structure):
     """smhv_feed_entry: a message of a feed's buffer (24 bytes)."""
     _fields_ = [("offset", C.c_uint64), ("length", C.c_uint32), ("frame", C.c_uint32), ("kind", C.c_uint32), ("crc", C.c_uint32)]
@@ -251,6 +279,14 @@ SIGNATURES = {
     "smhv_batch_labels_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "smhv_render_map_labeled": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(RenderLayersStruct), C.c_void_p, C.c_uint32,
                                           C.POINTER(LabelOptionsStruct), C.c_void_p, C.POINTER(LabelResult)]),
+    "smhv_text_font": (C.c_int, [C.c_uint8, C.POINTER(C.c_uint8)]),
+    "smhv_probe_text": (C.c_int, [C.POINTER(Probe), C.c_char_p, C.c_size_t]),
+    "smhv_batch_probe": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RenderOptions), C.POINTER(ProbePoint), C.c_uint32, C.c_void_p]),
+    "smhv_batch_read_probes": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Probe)]),
+    "smhv_batch_probes_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smhv_batch_render_debug": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RenderOptions), C.POINTER(DebugOptionsStruct), C.c_void_p]),
+    "smhv_render_map_debug": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(RenderLayersStruct), C.c_void_p, C.c_uint32,
+                                        C.POINTER(LabelOptionsStruct), C.POINTER(DebugOptionsStruct), C.c_void_p, C.POINTER(LabelResult), C.POINTER(Probe)]),
     "smhv_feed_create": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
     "smhv_feed_destroy": (None, [C.c_void_p]),
     "smhv_feed_reset": (C.c_int, [C.c_void_p]),

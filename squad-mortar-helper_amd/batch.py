@@ -228,6 +228,37 @@ class FrameBatch:
         L.check(self._lib.smhv_batch_labels_ptr(self._b, C.byref(d)))
         return d.value or 0
 
+    def probe(self, options, points, first=0, n=None, stream=None):
+        """The vision debugger's numbers of frames [first, first + n) at `points` = [(mx, my)] window positions (at most
+        MAX_PROBES) through the viewport of `options` (a RenderOptions), on `stream` (smhv_batch_probe): no pixels.  Asynchronous;
+        read_probes() waits for it."""
+        from .render import probe_points
+        n = self.max_frames - first if n is None else n
+        pts = probe_points([(float(x), float(y)) for x, y in points])
+        L.check(self._lib.smhv_batch_probe(self._b, first, n, C.byref(options), pts if len(points) else None, len(points), stream))
+
+    def read_probes(self, first=0, n=None):
+        """Synchronising host copy of the probe slab -> a ctypes array of n * MAX_PROBES Probe (frame f's at [f * MAX_PROBES])."""
+        n = self.max_frames - first if n is None else n
+        out = (L.Probe * (n * L.MAX_PROBES))()
+        L.check(self._lib.smhv_batch_read_probes(self._b, first, n, out))
+        return out
+
+    def probes_ptr(self):
+        """Device address of the probe slab (MAX_PROBES smhv_probe per frame)."""
+        d = C.c_void_p()
+        L.check(self._lib.smhv_batch_probes_ptr(self._b, C.byref(d)))
+        return d.value or 0
+
+    def render_debug(self, options, debug, first=0, n=None, stream=None):
+        """Draw the debug text and the vision debugger onto the images of the most recent render over frames [first, first + n) on
+        `stream` (smhv_batch_render_debug), behind the render and the labels, and write the probe slab.  options: the
+        RenderOptions of that render; debug: a DebugOptions.  Asynchronous."""
+        n = self.max_frames - first if n is None else n
+        do, keep = debug.struct()
+        L.check(self._lib.smhv_batch_render_debug(self._b, first, n, C.byref(options), C.byref(do), stream))
+        del keep
+
     def feed(self, feed, first=0, n=None, snapshot=False, stream=0, map_source=L.VIEW_NONE):
         """The web server's events of frames [first, first + n) into `feed` (a WebFeed) on `stream` (smhv_batch_feed):
         UpdateState, Map when the ui_map's CRC-32 differs from the one the feed last sent, Markers -- or, with snapshot, what a

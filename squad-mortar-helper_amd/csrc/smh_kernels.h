@@ -237,6 +237,40 @@ struct LabelRun {
 	uint32_t per_call;                   // 1: `lines`, `mpx` / has_mpx are the call's and res is one record for the rectangle alone
 	uint32_t has_mpx;
 };
+// smhv_batch_probe / smhv_batch_render_debug / smhv_render_map_debug (k_probe, k_debug_plan, k_debug_draw: smh_debugtext.hip): the
+// vision debugger's numbers and the debug text of n frames.  Launch arguments, taken by value at the launch.
+#define SMH_DBG_ITEMS (SMHV_TEXT_MAX_RUNS + 1u + 4u * SMHV_MAX_PROBES)   // a frame's item list: the runs, the caption, four per probe
+#define SMH_DBG_TEXT 200u                // bytes of a probe's string in the plan's pool (197 at most, were every field at its type's limit)
+#define SMH_DBG_NONE 0u                  // DebugItem::kind: nothing (an empty bounding box)
+#define SMH_DBG_TEXT_ITEM 1u             //   a text run at anchor (ax, ay)
+#define SMH_DBG_FILL 2u                  //   a fill of [a, b)
+#define SMH_DBG_FRAME 3u                 //   the SMHV_PRIM_RECT rule on corners a, b
+struct DebugItem {                       // 72 bytes; a fixed place in the frame's list per run, caption and probe part: paint order
+	const uint8_t *text;                 // the run's bytes (the call's run list, the plan's pool or the caption)
+	float ax, ay, bx, by;
+	int32_t x0, y0, x1, y1;              // window bounding box, half-open, clamped to the window: a superset of what the rule paints
+	uint32_t color;                      // RGBA8 as a little-endian word, alpha 255
+	uint32_t kind;
+	uint32_t n_lines, pad;
+	uint8_t off[8], len[8];              // text: where each line starts in `text` and how many characters it has
+};
+struct DebugRun {
+	const uint8_t *ui;                   // the ui slab, at the first frame of the call
+	const FrameAux *aux;                 // per frame: open
+	const smhv_frame_result *res;        // per frame: has_minimap
+	const smhv_text_run *runs;           // device memory: the call's runs
+	const smhv_probe_point *points;      // device memory: the call's probe points
+	smhv_probe *probes;                  // the probe slab, at the first frame of the call: SMHV_MAX_PROBES per frame
+	DebugItem *items;                    // SMH_DBG_ITEMS per frame, at the first frame of the call
+	uint8_t *pool;                       // SMHV_MAX_PROBES * SMH_DBG_TEXT bytes per frame: the probes' strings
+	uint8_t *img;                        // the render slab, at the first frame of the call (null: the probe alone)
+	uint64_t img_stride;                 // out_w * out_h * 4
+	uint32_t out_w, out_h;
+	uint32_t n_runs, n_points;
+	uint32_t flags;                      // SMHV_DEBUG_*
+	uint32_t scale;                      // S, 1 .. 4
+	float sw, sh, tx, ty;                // the viewport
+};
 // ---- the mask as the streaming passes leave it for the line search (round 6) -------------------------------------------------
 // A marker mask is 1-4 % non-empty, and what the search keeps in LDS is its non-empty 32 x 8 px tiles.  Finding them in the
 // row-major bit rows meant walking the bounding box of the set bits: (tile rows x tile columns) x 16 strided dword loads, ~68 KB
@@ -463,6 +497,8 @@ hipError_t launch_heightmap_lut16(const uint32_t *lut, uint16_t *lut16, uint32_t
 #define SMH_HM_LUT_WORDS (SMH_HM_LUT_ENTRIES + 4u + SMH_HM_LUT_ENTRIES / 2u)   // 32-bit table, {max, min, vr, -}, 16-bit table
 // the marker labels (smh_labels.hip): k_label_plan over n frames, then k_label_draw over their images
 hipError_t launch_labels(const LabelRun &r, uint32_t n, hipStream_t s);
+// the vision debugger and the debug text (smh_debugtext.hip): k_probe over n frames; with r.img also k_debug_plan and k_debug_draw
+hipError_t launch_debug_text(const Geom &g, const DebugRun &r, uint32_t n, hipStream_t s);
 void render_set_form(uint32_t form);
 uint32_t render_rule(const Geom &g, const RenderRun &r, uint32_t *texels, float *ratio);
 float render_switch_ratio();

@@ -126,26 +126,31 @@ extern "C" SMHV_API int smhv_batch_labels_ptr(smhv_batch *b, void **d_labels) {
 }
 
 // The per-call path.  The image is smhv_render_map's / smhv_render_map_layers's: their enqueueing is restated here (those entry
-// points copy the image out themselves, and this one copies it once, after the labels), launch for launch.
-extern "C" SMHV_API int smhv_render_map_labeled(smhv_ctx *c, const smhv_heightmap *hm, const smhv_render_options *opt, const smhv_render_layers *layers,
-                                                const smhv_line *lines, uint32_t n_lines, const smhv_label_options *lopt, uint8_t *rgba,
-                                                smhv_label_result *labels) {
-	int rc = require_open(c, "render_map_labeled");
+// points copy the image out themselves, and this one copies it once, after the labels), launch for launch.  smhv_render_map_debug
+// (smh_debugtext.inc) is the same call with the debug pass behind the labels: dopt != NULL, checked by its caller, and lopt may
+// then be NULL (no labels).
+static int debug_prepare(smhv_batch *b, const smhv_render_options *ropt, const smhv_debug_options *dopt, bool draw, hipStream_t s, DebugRun *r);
+static int render_map_text(smhv_ctx *c, const smhv_heightmap *hm, const smhv_render_options *opt, const smhv_render_layers *layers, const smhv_line *lines,
+                           uint32_t n_lines, const smhv_label_options *lopt, const smhv_debug_options *dopt, uint8_t *rgba, smhv_label_result *labels,
+                           smhv_probe *probes, const char *what) {
+	int rc = require_open(c, what);
 	if (rc) return rc;
 	CTX_OPEN(c);
-	if (!rgba || (n_lines && !lines)) return fail(SMHV_E_INVALID, "render_map_labeled: null argument");
-	if (n_lines > SMHV_RENDER_MAX_LINES) return fail(SMHV_E_INVALID, "render_map_labeled: %u lines (at most %u)", n_lines, SMHV_RENDER_MAX_LINES);
-	rc = check_render_options(opt, hm, "render_map_labeled");
+	if (!rgba || (n_lines && !lines)) return fail(SMHV_E_INVALID, "%s: null argument", what);
+	if (n_lines > SMHV_RENDER_MAX_LINES) return fail(SMHV_E_INVALID, "%s: %u lines (at most %u)", what, n_lines, SMHV_RENDER_MAX_LINES);
+	rc = check_render_options(opt, hm, what);
 	if (rc) return rc;
 	if (layers) {
-		rc = check_render_layers(layers, "render_map_labeled");
+		rc = check_render_layers(layers, what);
 		if (rc) return rc;
 	}
-	rc = check_label_options(lopt, "render_map_labeled");
-	if (rc) return rc;
-	if ((lopt->flags & SMHV_LABEL_DETECTED) && n_lines > SMHV_MAX_LINES)
-		return fail(SMHV_E_INVALID, "render_map_labeled: %u detected lines to label (at most %u)", n_lines, (unsigned)SMHV_MAX_LINES);
-	if (hm && hm->ctx->device != c->device) return fail(SMHV_E_INVALID, "render_map_labeled: the heightmap lives on device %d, the context on %d", hm->ctx->device, c->device);
+	if (lopt || !dopt) {
+		rc = check_label_options(lopt, what);
+		if (rc) return rc;
+	}
+	if (lopt && (lopt->flags & SMHV_LABEL_DETECTED) && n_lines > SMHV_MAX_LINES)
+		return fail(SMHV_E_INVALID, "%s: %u detected lines to label (at most %u)", what, n_lines, (unsigned)SMHV_MAX_LINES);
+	if (hm && hm->ctx->device != c->device) return fail(SMHV_E_INVALID, "%s: the heightmap lives on device %d, the context on %d", what, hm->ctx->device, c->device);
 	HIPCHK(hipSetDevice(c->device));
 	smhv_batch *b = c->fb;
 	const Geom &g = b->g;
@@ -166,7 +171,7 @@ extern "C" SMHV_API int smhv_render_map_labeled(smhv_ctx *c, const smhv_heightma
 			HIPCHK(hipMalloc((void **)&d_view, (size_t)y.src_w * y.src_h * 4u));
 			Buffers bf = make_buffers(b, c->frame_ptr, 0);
 			hipError_t e = launch_debug_view(g, bf, 0, which, c->isolated ? 1 : 0, d_view, c->s_main);
-			if (e != hipSuccess) { (void)hipFree(d_view); return fail(SMHV_E_HIP, "render_map_labeled: debug view: %s", hipGetErrorString(e)); }
+			if (e != hipSuccess) { (void)hipFree(d_view); return fail(SMHV_E_HIP, "%s: debug view: %s", what, hipGetErrorString(e)); }
 			y.src_mode = SMH_RND_SRC_RGBA; y.src = d_view; y.src_pitch = (uint64_t)y.src_w * 4u;
 		}
 	}
@@ -180,7 +185,7 @@ extern "C" SMHV_API int smhv_render_map_labeled(smhv_ctx *c, const smhv_heightma
 			HIPCHK(hipHostMalloc((void **)&c->h_fire, line_bytes));
 			c->fire_cap = line_bytes;
 		}
-		const bool label_lines = n_lines && (lopt->flags & SMHV_LABEL_DETECTED);
+		const bool label_lines = lopt && n_lines && (lopt->flags & SMHV_LABEL_DETECTED);
 		if (n_lines && ((opt->flags & SMHV_RENDER_MARKERS) || label_lines)) {
 			memcpy(c->h_fire, lines, sizeof(smhv_line) * (size_t)n_lines);
 			HIPCHK(hipMemcpyAsync(c->d_fire, c->h_fire, sizeof(smhv_line) * (size_t)n_lines, hipMemcpyHostToDevice, c->s_main));
@@ -193,25 +198,43 @@ extern "C" SMHV_API int smhv_render_map_labeled(smhv_ctx *c, const smhv_heightma
 			HIPCHK(launch_render_map_layers(g, r, y, 1, c->s_main));
 		} else
 			HIPCHK(launch_render_map(g, r, 1, c->s_main));
-		LabelRun lr;
-		int rc2 = labels_prepare(b, hm, opt, lopt, c->s_main, &lr);
-		if (rc2) return rc2;
-		lr.aux = b->d_aux;
-		lr.res = b->d_results + 3;
-		lr.per_call = 1u;
-		lr.lines = label_lines ? (const smhv_line *)c->d_fire : nullptr;
-		lr.n_lines = label_lines ? n_lines : 0u;
-		lr.has_mpx = lopt->mpx ? 1u : 0u;
-		lr.mpx = lopt->mpx ? *lopt->mpx : 0.0;
-		lr.out = b->d_labels;
-		lr.cull = b->d_label_cull;
-		lr.img = b->d_render;
-		HIPCHK(launch_labels(lr, 1, c->s_main));
+		if (lopt) {
+			LabelRun lr;
+			int rc2 = labels_prepare(b, hm, opt, lopt, c->s_main, &lr);
+			if (rc2) return rc2;
+			lr.aux = b->d_aux;
+			lr.res = b->d_results + 3;
+			lr.per_call = 1u;
+			lr.lines = label_lines ? (const smhv_line *)c->d_fire : nullptr;
+			lr.n_lines = label_lines ? n_lines : 0u;
+			lr.has_mpx = lopt->mpx ? 1u : 0u;
+			lr.mpx = lopt->mpx ? *lopt->mpx : 0.0;
+			lr.out = b->d_labels;
+			lr.cull = b->d_label_cull;
+			lr.img = b->d_render;
+			HIPCHK(launch_labels(lr, 1, c->s_main));
+		}
+		if (dopt) {
+			DebugRun dr;
+			int rc2 = debug_prepare(b, opt, dopt, true, c->s_main, &dr);
+			if (rc2) return rc2;
+			dr.ui = b->d_ui;
+			dr.aux = b->d_aux;
+			dr.res = b->d_results + 3;
+			dr.probes = b->d_probes;
+			dr.items = b->d_dbg_items;
+			dr.pool = b->d_dbg_pool;
+			dr.img = b->d_render;
+			HIPCHK(launch_debug_text(g, dr, 1, c->s_main));
+			HIPCHK(hipEventRecord(b->ev_dbg, c->s_main));
+			b->probed = true;
+		}
 		HIPCHK(hipEventRecord(b->ev_render, c->s_main));
 		std::lock_guard<std::mutex> lk2(c->mu);                  // (staging slot 2: the batch read-back's)
 		int rc3 = copy_image_d2h(c, 2, rgba, b->d_render, (size_t)r.out_stride / opt->out_h, 0, (size_t)opt->out_w * 4, opt->out_h, c->s_main);
 		if (rc3) return rc3;
-		if (labels) HIPCHK(hipMemcpy(labels, b->d_labels, sizeof(smhv_label_result), hipMemcpyDeviceToHost));   // (the stream has run dry)
+		if (labels && lopt) HIPCHK(hipMemcpy(labels, b->d_labels, sizeof(smhv_label_result), hipMemcpyDeviceToHost));   // (the stream has run dry)
+		if (probes && dopt) HIPCHK(hipMemcpy(probes, b->d_probes, sizeof(smhv_probe) * SMHV_MAX_PROBES, hipMemcpyDeviceToHost));
 		return SMHV_OK;
 	};
 	rc = run();
@@ -220,4 +243,10 @@ extern "C" SMHV_API int smhv_render_map_labeled(smhv_ctx *c, const smhv_heightma
 		(void)hipFree(d_view);
 	}
 	return rc;
+}
+
+extern "C" SMHV_API int smhv_render_map_labeled(smhv_ctx *c, const smhv_heightmap *hm, const smhv_render_options *opt, const smhv_render_layers *layers,
+                                                const smhv_line *lines, uint32_t n_lines, const smhv_label_options *lopt, uint8_t *rgba,
+                                                smhv_label_result *labels) {
+	return render_map_text(c, hm, opt, layers, lines, n_lines, lopt, nullptr, rgba, labels, nullptr, "render_map_labeled");
 }

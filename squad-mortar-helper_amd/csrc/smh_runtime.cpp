@@ -252,6 +252,14 @@ struct smhv_batch {
 	smhv_label_line *h_label_extra = nullptr, *d_label_extra = nullptr;
 	hipEvent_t ev_label_extra = nullptr;
 	smhv_heightmap *label_hm = nullptr;
+	// smhv_batch_probe / smhv_batch_render_debug: the probe slab, the item lists and the string pool of the draw (allocated by the
+	// first call), the runs' and points' way to the device (one pinned block, one device block: the runs, then the points), the
+	// event of the most recent copy and the event behind the most recent call's kernels (they read the device block)
+	smhv_probe *d_probes = nullptr;
+	DebugItem *d_dbg_items = nullptr;
+	uint8_t *d_dbg_pool = nullptr, *h_dbg_stage = nullptr, *d_dbg_stage = nullptr;
+	hipEvent_t ev_dbg_stage = nullptr, ev_dbg = nullptr;
+	bool probed = false;
 };
 
 // a device copy of a heightmap (smhv_heightmap_create); batches and pipelines that have it bound hold references of their own
@@ -643,13 +651,16 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	(void)hipDeviceSynchronize();
 	void *ptrs[] = {b->d_ui, b->d_mask, b->d_bits, b->d_tiled, b->d_occ, b->d_ocr, b->d_scales, b->d_aux, b->d_results, b->d_anchors, b->d_bars, b->d_farm,
 	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run, b->d_overlay, b->d_render, b->d_prims, b->d_labels,
-	                b->d_label_cull, b->d_label_extra};
+	                b->d_label_cull, b->d_label_extra, b->d_probes, b->d_dbg_items, b->d_dbg_pool, b->d_dbg_stage};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	if (b->h_prims) (void)hipHostFree(b->h_prims);
 	if (b->ev_prims) (void)hipEventDestroy(b->ev_prims);
 	if (b->h_label_extra) (void)hipHostFree(b->h_label_extra);
 	if (b->ev_label_extra) (void)hipEventDestroy(b->ev_label_extra);
+	if (b->h_dbg_stage) (void)hipHostFree(b->h_dbg_stage);
+	if (b->ev_dbg_stage) (void)hipEventDestroy(b->ev_dbg_stage);
+	if (b->ev_dbg) (void)hipEventDestroy(b->ev_dbg);
 	if (b->h_err) (void)hipHostFree(b->h_err);
 	for (auto &a : b->anchor_stage) {
 		if (a.h) (void)hipHostFree(a.h);
@@ -3453,3 +3464,4 @@ extern "C" SMHV_API int smhv_debug_render_rule(uint32_t map_w, uint32_t map_h, f
 
 #include "smh_feed.inc"
 #include "smh_labels.inc"
+#include "smh_debugtext.inc"

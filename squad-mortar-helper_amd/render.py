@@ -185,3 +185,116 @@ class LabelOptions:
         o.mpx = C.pointer(mpx) if mpx is not None else None
         return o, (arr, mpx)
 
+
+# ---- debug text and the vision debugger (smhv_batch_probe / smhv_batch_render_debug / smhv_render_map_debug) ------------------------
+def text_run(x, y, text, rgba=(255, 255, 255, 255), map_coords=False):
+    """One smhv_text_run as a tuple (x, y, (r, g, b, a), flags, bytes): `text` a str (encoded as Latin-1) or bytes, '\\n' starts a
+    new line at the run's x; map_coords: (x, y) are map-ROI coordinates and go through the viewport, otherwise window pixels."""
+    data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    return (float(_f32(x)), float(_f32(y)), tuple(int(v) for v in rgba), L.TEXT_MAP_COORDS if map_coords else 0, data)
+
+
+def _font_has(byte):
+    return 0x20 <= byte <= 0x7E or byte in (0xB0, 0xB1)
+
+
+def rust_debug_str(text):
+    """Rust's {:?} of a str -- quotes around it, a backslash before '"' and a backslash, \\t \\r \\n as two characters, \\u{..} for
+    what char::escape_debug escapes -- restricted to what the text font can print: None when a character that {:?} leaves as
+    it is has no glyph (anything outside ASCII but the degree and plus-minus signs)."""
+    out = ['"']
+    for ch in text:
+        o = ord(ch)
+        if ch in '"\\':
+            out.append("\\" + ch)
+        elif ch == "\t":
+            out.append("\\t")
+        elif ch == "\r":
+            out.append("\\r")
+        elif ch == "\n":
+            out.append("\\n")
+        elif o == 0:
+            out.append("\\0")
+        elif o < 0x20 or 0x7F <= o < 0xA0:
+            out.append("\\u{%x}" % o)                               # a control character: escape_debug's \u{..}
+        elif o < 0x100 and _font_has(o):
+            out.append(ch)
+        else:
+            return None
+    out.append('"')
+    return "".join(out)
+
+
+def ocr_text_runs(boxes, brq_w, brq_h):
+    """The text of the Debug menu's OCR overlay (debug.rs:300-301), beside ocr_box_prims: boxes = [(left, top, right, bottom,
+    confidence, text)] in the bottom right quadrant's pixels; "{:.2}%\\n{:?}" at (left, bottom) moved by (brq_w, brq_h), in the box's
+    colour.  ("%.2f" is Rust's {:.2}: both round the exact binary value.)  A run the font cannot print or that is longer than a
+    run may be is skipped."""
+    out = []
+    for left, top, right, bottom, conf, text in boxes:
+        f = _f32(conf) / _f32(100.0)
+        color = (_color_byte(_f32(1.0) - f), _color_byte(f), 0, 255)
+        dbg = rust_debug_str(text)
+        if dbg is None:
+            continue
+        s = "%.2f%%\n" % float(_f32(conf)) + dbg                   # (the confidence is an f32, vision-ocr/src/lib.rs:111)
+        if len(s) > L.TEXT_MAX_BYTES:
+            continue
+        out.append(text_run(int(left) + int(brq_w), int(bottom) + int(brq_h), s, color, map_coords=True))
+    return out
+
+
+def scale_text_runs(bars, brq_w, brq_h):
+    """The text of the Debug menu's scale overlay (debug.rs:315), beside scale_bar_prims: bars = [(meters, left, y, right,
+    found)]; "{meters}m" at the bar's p0 = (left, y) moved by (brq_w, brq_h), magenta.  Bars that were not found are skipped."""
+    return [text_run(int(left) + int(brq_w), int(y) + int(brq_h), "%dm" % int(meters), CUSTOM_MARKER_COLOR, map_coords=True)
+            for meters, left, y, right, found in bars if found]
+
+
+def probe_points(points):
+    """[(mx, my)] -> a ctypes array of smhv_probe_point (one entry at least, so it can always be passed)."""
+    pts = (L.ProbePoint * max(len(points), 1))()
+    for i, (x, y) in enumerate(points):
+        pts[i].x, pts[i].y = x, y
+    return pts
+
+
+class DebugOptions:
+    """What a debug pass draws: runs = [text_run()], probes = [(mx, my)] window positions of the vision debugger, draw_probes =
+    the debugger's picture for every valid probe, minimap_caption = the red caption on frames without a minimap rectangle,
+    scale = window pixels per font unit (1 .. 4, 0 = 2)."""
+
+    def __init__(self, runs=(), probes=(), draw_probes=False, minimap_caption=False, scale=0):
+        self.runs = list(runs)
+        self.probes = [(float(_f32(x)), float(_f32(y))) for x, y in probes]
+        self.draw_probes = bool(draw_probes)
+        self.minimap_caption = bool(minimap_caption)
+        self.scale = int(scale)
+
+    def struct(self):
+        """-> (smhv_debug_options, what it points to: keep it alive for the call)."""
+        n, m = len(self.runs), len(self.probes)
+        arr = (L.TextRun * max(n, 1))()
+        for i, (x, y, rgba, flags, data) in enumerate(self.runs):
+            arr[i].x, arr[i].y, arr[i].flags, arr[i].n = x, y, flags, len(data)
+            for k in range(4):
+                arr[i].rgba[k] = rgba[k]
+            for k, b in enumerate(data[:L.TEXT_MAX_BYTES]):
+                arr[i].text[k] = b
+        pts = probe_points(self.probes)
+        o = L.DebugOptionsStruct()
+        o.size = C.sizeof(L.DebugOptionsStruct)
+        o.flags = (L.DEBUG_DRAW_PROBES if self.draw_probes else 0) | (L.DEBUG_MINIMAP_CAPTION if self.minimap_caption else 0)
+        o.scale = self.scale
+        o.n_runs = n
+        o.runs = C.cast(arr, C.POINTER(L.TextRun)) if n else None
+        o.n_probes = m
+        o.probes = C.cast(pts, C.POINTER(L.ProbePoint)) if m else None
+        return o, (arr, pts)
+
+
+def probe_text(probe):
+    """The string the vision debugger prints for a Probe (smhv_probe_text; needs no device)."""
+    buf = C.create_string_buffer(256)
+    L.check(L.load().smhv_probe_text(C.byref(probe), buf, 256))
+    return buf.value.decode("latin-1")

@@ -246,16 +246,29 @@ class HipVision:
         return out
 
     def render_map(self, viewport, out_w, out_h, lines=None, heightmap=None, fit_to_minimap=True, background=(0, 0, 0, 255), options=None, layers=None,
-                   labels=None):
+                   labels=None, debug=None):
         """The app's map view of the current frame (smhv_render_map; src/ui/map.rs:209-273): the ui_map through `viewport` (a
         MapViewport) into a window of out_w x out_h, the heightmap's overlay when `heightmap` is given, and `lines` (float32
         [n, 4] in map-ROI coordinates: detected and custom markers) -> uint8 [out_h, out_w, 4] RGBA.  labels: a LabelOptions
         (smhv_render_map_labeled): the firing solutions as text beside the lines, drawn over the finished image; the call then
-        returns (image, LabelResult)."""
+        returns (image, LabelResult).  debug: a DebugOptions (smhv_render_map_debug): the debug text and the vision debugger,
+        drawn last; the call then returns (image, LabelResult or None, a ctypes array of MAX_PROBES Probe)."""
         from .render import render_options
         ln = np.ascontiguousarray(lines if lines is not None else np.zeros((0, 4)), np.float32).reshape(-1, 4)
         opt = options if options is not None else render_options(viewport, out_w, out_h, heightmap is not None, len(ln) > 0, fit_to_minimap, background)
         out = np.empty((max(int(opt.out_h), 1), max(int(opt.out_w), 1), 4), np.uint8)
+        if debug is not None:
+            do, keep_debug = debug.struct()
+            lo, keep_labels = labels.struct() if labels is not None else (None, None)
+            ly, keep = layers.struct() if layers is not None else (None, None)
+            res = L.LabelResult() if lo is not None else None
+            probes = (L.Probe * L.MAX_PROBES)()
+            L.check(self._lib.smhv_render_map_debug(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(opt),
+                                                    C.byref(ly) if ly is not None else None, ln.ctypes.data if len(ln) else None, len(ln),
+                                                    C.byref(lo) if lo is not None else None, C.byref(do), out.ctypes.data,
+                                                    C.byref(res) if res is not None else None, probes))
+            del keep, keep_labels, keep_debug
+            return out, res, probes
         if labels is not None:
             lo, keep_labels = labels.struct()
             ly, keep = layers.struct() if layers is not None else (None, None)
@@ -274,6 +287,14 @@ class HipVision:
         L.check(self._lib.smhv_render_map(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(opt), ln.ctypes.data if len(ln) else None,
                                           len(ln), out.ctypes.data))
         return out
+
+    def probe(self, viewport, points, out_w=1, out_h=1):
+        """The vision debugger's numbers of the current frame at `points` = [(mx, my)] window positions through `viewport` (a
+        MapViewport) -> a ctypes array of MAX_PROBES Probe.  The per-call path has no probe-only entry point: this is
+        smhv_render_map_debug with nothing to draw, so a render of out_w x out_h (1 x 1 by default) is enqueued and copied out with
+        the numbers; a caller that probes many frames uses FrameBatch.probe."""
+        from .render import DebugOptions
+        return self.render_map(viewport, out_w, out_h, debug=DebugOptions(probes=points))[2]
 
     def feed_frame(self, feed, lines, mpx=None, minimap=None, snapshot=False, map_source=L.VIEW_NONE):
         """The web server's events of the current frame into `feed` (a WebFeed; smhv_feed_frame): the ui_map crop_to_map left on
