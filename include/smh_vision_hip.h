@@ -236,7 +236,16 @@ SMHV_API int smhv_batch_layout_get(smhv_batch *b, smhv_batch_layout *out);
  * 4-byte aligned is refused with SMHV_E_INVALID before anything is enqueued. */
 SMHV_API int smhv_batch_run(smhv_batch *b, const void *d_frames, uint32_t n, uint32_t stages, int grayscale, uint32_t max_gap,
                             const smhv_anchors *anchors, void *stream);
-/* device pointers of the batch outputs (valid for the life of the batch) */
+/* device pointers of the batch outputs (valid for the life of the batch); any of them may be NULL.
+ * d_mask, the marker mask one byte per pixel, is the one slab the runs do not write by themselves: it is an exact function of the
+ * bit-packed rows (byte x of a row = 0xFF where bit x + bits_xoff is set), nothing on the device reads it, and the library makes it
+ * from the bit rows when one of ITS readers wants it (smhv_batch_read_image, smhv_batch_render_layers / smhv_batch_feed_view with the
+ * mask as the map).  A call with a non-NULL d_mask tells the library that the caller reads the slab itself: the call waits for the
+ * device, brings the bytes of every run so far up to date, and switches the batch for good -- every later run (smhv_batch_run, or a
+ * pipeline's submission into this batch) writes its frames' bytes with one more small kernel on its own stream right behind its
+ * streaming pass (in a frame-granular pipeline ahead of the publication, so inside the submission's completion).  So the rule for
+ * every pointer here stays "a run's results are in memory when its stream gets there"; a caller that never asks for d_mask never
+ * pays for it (19 % of the streaming pass's written bytes at 1080p). */
 SMHV_API int smhv_batch_device_ptrs(smhv_batch *b, void **d_results, void **d_ui, void **d_mask, void **d_ocr, void **d_scales, void **d_bits);
 /* The marker mask a third time, as the streaming passes leave it for the line search (and for any host kernel that wants the
  * marker pixels without scanning a 1-4 % full image): TILE-MAJOR, 32 x 8 px tiles of the bit-packed rows -- tile (ty, wx) = rows

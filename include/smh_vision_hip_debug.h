@@ -107,6 +107,15 @@ SMHV_API int smhv_debug_feed_rows(uint32_t rows);
  * 0 = the launcher's rule (one LDS lookup per source byte where a plane row has at most 64 16-byte groups, k_view_crc_gray1),
  * 4 = always the general kernel's four lookups per message dword.  Both give the same CRC. */
 SMHV_API int smhv_debug_feed_gray_form(uint32_t form);
+/* host state only: how the batch stands with its marker mask as bytes (d_mask; smhv_batch_device_ptrs in smh_vision_hip.h).
+ * *stale_frames <- frames [0, stale_frames) whose bytes are owed: runs since the last expansion wrote their bit rows, and the next
+ * reader of the byte form (or of this count's cause, a call that asks for d_mask) has them expanded; 0 = the bytes are current or
+ * their expansion is enqueued.  *eager <- 1 once a caller has asked smhv_batch_device_ptrs for d_mask: every run expands its own
+ * frames behind its pass and nothing is ever owed.  Either pointer may be NULL. */
+SMHV_API int smhv_debug_batch_mask_state(smhv_batch *b, uint32_t *stale_frames, int *eager);
+/* measuring: k_mask_expand alone -- the byte mask of frames [0, n) from their bit rows as they stand, on `stream`; changes no state
+ * (the bytes it writes are the ones any expansion writes).  tools/mask_on_demand_cost.py times it. */
+SMHV_API int smhv_debug_mask_expand(smhv_batch *b, uint32_t n, void *stream);
 /* benchmark driver: a NATIVE capture loop for the ingest queue (the reference's capture thread is native code, src/capture.rs) --
  * n times: smhv_ingest_acquire, stamp the 24-bit value (*counter)++ into pixel (0, 0) of the staging buffer (whose other
  * pixels keep what they last held; (0, 0) lies outside every region the path reads, so every frame hashes differently and

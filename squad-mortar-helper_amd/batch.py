@@ -4,6 +4,7 @@ torch is used only as plumbing (device memory for the frame batch, the current H
 torch.distributed); every kernel is in libsmh_vision_hip.so.
 """
 import ctypes as C
+from collections.abc import Mapping
 
 import numpy as np
 
@@ -38,6 +39,27 @@ def results_to_dicts(recs):
             status=int(r.status), error=(None if r.status == L.FRAME_OK else "line search gave the frame up (SMHV_FRAME_LSD_STUCK)" if r.status == L.FRAME_LSD_STUCK
                                          else "status %d" % r.status)))
     return out
+
+
+_PTR_KEYS = ("results", "ui", "mask", "ocr", "scales", "bits")
+
+
+class _DevicePtrs(Mapping):
+    """FrameBatch.device_ptrs(): read-only; the "mask" entry asks the library for d_mask the first time it is read."""
+
+    def __init__(self, batch, ptrs):
+        self._batch, self._ptrs = batch, ptrs
+
+    def __getitem__(self, key):
+        if key == "mask" and self._ptrs["mask"] is None:
+            self._ptrs["mask"] = self._batch._mask_ptr()
+        return self._ptrs[key]
+
+    def __iter__(self):
+        return iter(_PTR_KEYS)
+
+    def __len__(self):
+        return len(_PTR_KEYS)
 
 
 class FrameBatch:
@@ -105,9 +127,25 @@ class FrameBatch:
         return out
 
     def device_ptrs(self):
+        """Mapping of the output slabs' device addresses ("results", "ui", "mask", "ocr", "scales", "bits").  "mask" is fetched when it
+        is first read: asking the library for d_mask makes the batch write the byte mask behind every run from then on
+        (smhv_batch_device_ptrs), which a caller that reads the other slabs only never pays."""
         p = [C.c_void_p() for _ in range(6)]
-        L.check(self._lib.smhv_batch_device_ptrs(self._b, *[C.byref(x) for x in p]))
-        return dict(zip(("results", "ui", "mask", "ocr", "scales", "bits"), [x.value for x in p]))
+        args = [C.byref(x) for x in p]
+        args[2] = None
+        L.check(self._lib.smhv_batch_device_ptrs(self._b, *args))
+        return _DevicePtrs(self, dict(zip(_PTR_KEYS, [x.value for x in p])))
+
+    def _mask_ptr(self):
+        m = C.c_void_p()
+        L.check(self._lib.smhv_batch_device_ptrs(self._b, None, None, C.byref(m), None, None, None))
+        return m.value
+
+    def mask_state(self):
+        """(frames whose byte mask is owed, whether every run writes it): smhv_debug_batch_mask_state."""
+        stale, eager = C.c_uint32(0), C.c_int(0)
+        L.check(self._lib.smhv_debug_batch_mask_state(self._b, C.byref(stale), C.byref(eager)))
+        return int(stale.value), bool(eager.value)
 
     def tile_mask(self, frame=0):
         """The marker mask of one frame as the streaming passes leave it for the line search: (tiled uint32[tile_rows, word_columns, 8],

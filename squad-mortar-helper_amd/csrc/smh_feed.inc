@@ -195,6 +195,10 @@ extern "C" SMHV_API int smhv_batch_feed_view(smhv_batch *b, smhv_feed *f, uint32
 	rc = feed_batch_source(b, first, map_source, true, &v);
 	if (rc) return rc;
 	HIPCHK(hipSetDevice(b->ctx->device));
+	if (map_source == (uint32_t)SMHV_VIEW_LSD_INPUT) {         // the mask as bytes is made when it is read (smh_runtime.cpp)
+		rc = batch_materialize_mask(b, (hipStream_t)stream);
+		if (rc) return rc;
+	}
 	return feed_enqueue(f, v, b->d_results + first, first, n, flags, (hipStream_t)stream);
 }
 

@@ -425,7 +425,10 @@ hipError_t svc_probe_host_atomics(SvcHost *h, SvcHost *d_h, bool *ok);   // pipe
 hipError_t launch_svc_publish(SvcCtl *ctl, unsigned long long *ring, SvcSlot *slots, uint32_t slot, const Buffers &b, uint32_t n, uint32_t seq, uint32_t ring_log2, hipStream_t s);
 hipError_t launch_lsd_service(const Geom &g, const SvcParams &p, uint32_t workgroups, uint32_t waves, uint32_t lds_bytes, hipStream_t s);
 
-enum : uint32_t { MAP_UI = 1u, MAP_MASK = 2u, MAP_PRIO = 0x100u, MAP_BAND_MAJOR = 0x200u };   // MAP_BAND_MAJOR: the order of the work items (launch_map_brq_pass)
+enum : uint32_t { MAP_UI = 1u, MAP_MASK = 2u, MAP_BYTES = 4u, MAP_PRIO = 0x100u, MAP_BAND_MAJOR = 0x200u };   // MAP_BAND_MAJOR: the order of the work items (launch_map_brq_pass)
+// MAP_BYTES (k_map_pass only): the pass also writes the mask one byte per pixel (Buffers::mask) -- the per-call path, whose mask goes
+// straight to the host.  Batch runs leave it out: their passes write the bit rows (and the tile-major mask), and the byte form is
+// made from the bit rows when a reader asks for it (launch_mask_expand; smh_runtime.cpp, batch_materialize_mask).
 enum : uint32_t { BRQ_OCR = 1u, BRQ_SCALES = 2u };
 
 hipError_t launch_button(const Geom &g, const Buffers &b, uint32_t n, int force_open, hipStream_t s);
@@ -505,6 +508,9 @@ float render_switch_ratio();
 // which: SMHV_VIEW_*; isolated: LSDPreprocess shows the marker-isolated crop (after isolate_map_markers)
 hipError_t launch_debug_view(const Geom &g, const Buffers &b, uint32_t frame, int which, int isolated, uint8_t *d_rgba, hipStream_t s);
 hipError_t launch_marker_table(uint32_t *d_bits, hipStream_t s);
+// the marker mask one byte per pixel (Buffers::mask) of frames [0, n) from their bit rows (Buffers::bits): byte x of a row = 0xFF where bit x of the
+// row is set, the padded row width (mask_pitch bytes) for rows 0 .. rh - 1
+hipError_t launch_mask_expand(const Geom &g, const uint32_t *d_bits, uint8_t *d_mask, uint32_t n, hipStream_t s);
 hipError_t launch_pack_rows(const void *d_src, uint32_t src_pitch_bytes, void *d_dst, uint32_t row_bytes, uint32_t rows, hipStream_t s);   // pitched rows -> a tight buffer (dword granularity)
 hipError_t launch_side_probe(uint32_t *d_out, uint32_t workgroups, uint32_t spin, hipStream_t s);   // a 21 KB-LDS / 280-VGPR kernel that does nothing (co-residency probe)
 hipError_t launch_build_sector_table(unsigned long long *d_tab, uint32_t T, hipStream_t s);

@@ -6,6 +6,7 @@
 //   k_hm_minmax / k_hm_color  heightmap overlay colours                       (src/ui/heightmaps.rs:169-207)
 //   k_hm_lut / k_hm_overlay   the overlay drawn over the ui_map               (src/ui/map.rs:250-256, heightmaps.rs:794-826)
 //   k_debug_view   DebugView images                                           (vision-cpu/src/lib.rs:451-460)
+//   k_mask_expand  the marker mask one byte per pixel from the bit rows, when a reader asks for it
 //   k_marker_table exhaustive colour-predicate table (test support)
 //   k_crc32        CRC-32 of a frame in HBM for the capture hand-off          (src/capture.rs:44-47)
 //
@@ -428,6 +429,33 @@ hipError_t launch_pack_rows(const void *d_src, uint32_t src_pitch_bytes, void *d
 	if ((src_pitch_bytes | row_bytes) & 3u) return hipErrorInvalidValue;
 	const uint32_t row_w = row_bytes / 4u;
 	hipLaunchKernelGGL(k_pack_rows, dim3((row_w + 255u) / 256u, rows), dim3(256), 0, s, (const uint32_t *)d_src, src_pitch_bytes / 4u, (uint32_t *)d_dst, row_w, rows);
+	return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_mask_expand: the marker mask one byte per pixel (Buffers::mask) from the bit-packed rows the streaming passes write -- made
+// when a reader of the byte form asks for it (smh_runtime.cpp, batch_materialize_mask), not by every pass.  Both forms pad a row
+// to the same 128 columns (mask_pitch = 32 bits_pitch_w bytes), neither has a gap between rows or frames, and byte x of a padded row
+// is 0xFF where bit x of the row is set: byte j of the slab is bit j of the bit slab.  A thread takes 16 bits (one halfword: a wave
+// reads 128 contiguous bytes) and stores their 16 bytes at once (a wave writes 1 KB, contiguous); `groups` = 16-byte groups of the
+// frames expanded, so nothing beyond their rows is touched.  Memory-bound: 1 byte read per 8 written.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_mask_expand(const uint16_t *__restrict__ bits, uint4 *__restrict__ mask, uint64_t groups) {
+	const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (i >= groups) return;
+	const uint32_t v = bits[i];
+	uint4 o;
+	o.x = (((v & 15u) * 0x00204081u) & 0x01010101u) * 0xFFu;           // nibble -> four bytes of 0x00 / 0xFF (k_map_pass)
+	o.y = ((((v >> 4) & 15u) * 0x00204081u) & 0x01010101u) * 0xFFu;
+	o.z = ((((v >> 8) & 15u) * 0x00204081u) & 0x01010101u) * 0xFFu;
+	o.w = ((((v >> 12) & 15u) * 0x00204081u) & 0x01010101u) * 0xFFu;
+	mask[i] = o;
+}
+hipError_t launch_mask_expand(const Geom &g, const uint32_t *d_bits, uint8_t *d_mask, uint32_t n, hipStream_t s) {
+	if (g.mask_pitch != (uint64_t)g.bits_pitch_w * 32u || (g.mask_stride & 15u)) return hipErrorInvalidValue;   // (compute_geom: whole groups of 16 quads)
+	const uint64_t groups = g.mask_stride / 16u * n, blocks = (groups + 255u) / 256u;
+	if (blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(k_mask_expand, dim3((uint32_t)blocks), dim3(256), 0, s, (const uint16_t *)d_bits, (uint4 *)d_mask, groups);
 	return hipGetLastError();
 }
 

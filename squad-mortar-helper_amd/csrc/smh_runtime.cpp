@@ -243,6 +243,14 @@ struct smhv_batch {
 	// smhv_batch_render_layers: what the runs of this batch have left in its slabs (a map source has to be there), and the prims'
 	// way to the device: pinned staging, a device copy, and the event of the most recent copy (the staging is free once it has run)
 	bool ui_gray = false, mask_written = false, ocr_written = false, scales_written = false;
+	// The marker mask one byte per pixel (d_mask) is made from the bit rows when somebody reads it (batch_materialize_mask): the runs'
+	// passes write the bit rows only.  mask_stale: frames [0, mask_stale) may have bit rows newer than their bytes (the largest n of
+	// the runs since the last expansion); ev_mask: behind the last expansion, for a reader on another stream; mask_eager: a caller
+	// holds d_mask itself (smhv_batch_device_ptrs), so every run expands its own frames behind its pass.  Under mask_mu.
+	std::mutex mask_mu;
+	uint32_t mask_stale = 0;
+	bool mask_eager = false;
+	hipEvent_t ev_mask = nullptr;
 	smhv_render_prim *h_prims = nullptr, *d_prims = nullptr;
 	hipEvent_t ev_prims = nullptr;
 	// smhv_batch_render_labels: the label slab and the cull entries of its slots (allocated by the first call), the extras' way to
@@ -630,6 +638,7 @@ extern "C" SMHV_API int smhv_batch_create(smhv_ctx *c, uint32_t W, uint32_t H, u
 		hipError_t e = hipHostMalloc((void **)&b->h_err, sizeof(BatchError), hipHostMallocMapped | hipHostMallocCoherent);
 		if (e == hipSuccess) { memset(b->h_err, 0, sizeof(BatchError)); e = hipHostGetDevicePointer((void **)&b->d_err, b->h_err, 0); }
 		if (e == hipSuccess) e = hipEventCreateWithFlags(&b->ev_map_done, hipEventDisableTiming);
+		if (e == hipSuccess) e = hipEventCreateWithFlags(&b->ev_mask, hipEventDisableTiming);
 		// Only for frame sizes that need them: a process has few hardware queues, and every extra stream makes it more
 		// likely that two independent branches share one (measured: 10 % off the pipelined 1080p throughput).
 		if (max_frames > 1 && !lsd_rows_only(b->g)) {
@@ -683,6 +692,7 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
 	if (b->ev_join) (void)hipEventDestroy(b->ev_join);
 	if (b->ev_map_done) (void)hipEventDestroy(b->ev_map_done);
+	if (b->ev_mask) (void)hipEventDestroy(b->ev_mask);
 	for (auto e : b->ev_probe) if (e) (void)hipEventDestroy(e);
 	if (b->lsd_fork.s1) (void)hipStreamDestroy(b->lsd_fork.s1);
 	if (b->lsd_fork.s2) (void)hipStreamDestroy(b->lsd_fork.s2);
@@ -896,6 +906,21 @@ static int check_overlay_stages(uint32_t stages, const smhv_heightmap *hm) {
 	return SMHV_OK;
 }
 
+// The marker mask as bytes, on demand.  Every reader of d_mask calls this first, with the stream its own work is ordered on behind
+// the run (the ordering it relies on for the run's other outputs holds for the bit rows the expansion reads).  Something stale:
+// k_mask_expand over [0, mask_stale) on `stream`, the event behind it.  Nothing stale: `stream` waits for the event, so a second
+// reader on another stream cannot overtake the first one's expansion.  Frames a run skipped (a closed map) keep their older bit
+// rows and get the older mask the pass would have left; hipMemset zeroed both forms at creation.
+static int batch_materialize_mask(smhv_batch *b, hipStream_t stream) {
+	std::lock_guard<std::mutex> lk(b->mask_mu);
+	if (b->mask_stale) {
+		HIPCHK(launch_mask_expand(b->g, b->d_bits, b->d_mask, std::min(b->mask_stale, b->max_frames), stream));
+		HIPCHK(hipEventRecord(b->ev_mask, stream));
+		b->mask_stale = 0;
+	} else HIPCHK(hipStreamWaitEvent(stream, b->ev_mask, 0));  // (no-op before the first expansion)
+	return SMHV_OK;
+}
+
 struct SvcPublish { SvcCtl *ctl; unsigned long long *ring; SvcSlot *slots; uint32_t slot, seq, ring_log2; const uint32_t *cull_tab; bool have_cull; hipStream_t s_pro; hipEvent_t ev_pro;
                     bool *published; };   // <- set once k_svc_publish has been enqueued (from then on the device WILL complete the submission)
 static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint32_t stages, int grayscale, uint32_t max_gap,
@@ -974,6 +999,13 @@ static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint3
 	STAGE_BEGIN(1, s);
 	if (mflags && qflags) HIPCHK(launch_map_brq_pass(g, bf, n, mflags, qflags, grayscale, 0, 1, s, &b->tune));
 	else if (mflags) HIPCHK(launch_map_pass(g, bf, n, mflags, grayscale, s, true, b->tune.map_overlapped != 0u));
+	if (mflags & MAP_MASK) {
+		// the mask as bytes: owed to whoever reads it (batch_materialize_mask) -- or, for a caller that holds d_mask itself, made
+		// here, behind the pass and ahead of everything a completion of this run is taken from (the publication included)
+		std::lock_guard<std::mutex> lk(b->mask_mu);
+		if (b->mask_eager) HIPCHK(launch_mask_expand(g, b->d_bits, b->d_mask, n, s));
+		else b->mask_stale = std::max(b->mask_stale, n);
+	}
 	STAGE_END(1, s);
 	if (mflags & MAP_UI) { b->ui_written = true; b->ui_gray = grayscale != 0; }   // (the pass that writes the ui slab is enqueued: smhv_batch_render)
 	if (mflags & MAP_MASK) b->mask_written = true;             // (... and the slabs smhv_batch_render_layers can take as the map)
@@ -1096,7 +1128,19 @@ extern "C" SMHV_API int smhv_batch_device_ptrs(smhv_batch *b, void **r, void **u
 	if (!b) return fail(SMHV_E_INVALID, "null batch");
 	if (r) *r = b->d_results;
 	if (ui) *ui = b->d_ui;
-	if (mask) *mask = b->d_mask;
+	if (mask) {
+		// A caller that holds d_mask reads it whenever it likes: the bytes of every run so far are made now (after everything enqueued
+		// on the device, and waited for), and from here on every run of this batch expands its own frames behind its pass
+		// (batch_run_impl), so "a run's results are in memory when its stream gets there" holds for this slab as for the others.
+		CTX_OPEN(b->ctx);
+		HIPCHK(hipSetDevice(b->ctx->device));
+		{ std::lock_guard<std::mutex> lk(b->mask_mu); b->mask_eager = true; }
+		HIPCHK(hipDeviceSynchronize());
+		int rc = batch_materialize_mask(b, b->ctx->s_main);
+		if (rc) return rc;
+		HIPCHK(wait_stream(b->ctx->s_main));
+		*mask = b->d_mask;
+	}
 	if (ocr) *ocr = b->d_ocr;
 	if (scales) *scales = b->d_scales;
 	if (bits) *bits = b->d_bits;
@@ -1166,6 +1210,8 @@ extern "C" SMHV_API int smhv_batch_read_image(smhv_batch *b, int which, uint32_t
 		break;
 	case SMHV_VIEW_LSD_INPUT: {
 		std::lock_guard<std::mutex> lk(b->ctx->mu);
+		int rc = batch_materialize_mask(b, b->ctx->s_main);         // (the runs are complete: the device was waited for above)
+		if (rc) return rc;
 		return copy_image_d2h(b->ctx, 2, out, b->d_mask + frame * g.mask_stride, g.mask_pitch, g.m_xoff, g.rw, g.rh, b->ctx->s_main);
 	}
 	case SMHV_VIEW_OCR_INPUT: {
@@ -2063,7 +2109,7 @@ extern "C" SMHV_API int smhv_crop_to_map(smhv_ctx *c, int grayscale, int *map_op
 	// that decide how the call returns.  On a frame whose map is closed the pass ran for nothing (~20 us of the GPU, nobody
 	// waits for it).
 	HIPCHK(launch_button(g, bf, 1, 0, s));
-	HIPCHK(launch_map_pass(g, bf, 1, MAP_UI | MAP_MASK, grayscale, s));
+	HIPCHK(launch_map_pass(g, bf, 1, MAP_UI | MAP_MASK | MAP_BYTES, grayscale, s));   // (MAP_BYTES: get_lsd_image and the debug views read this batch's d_mask as it stands)
 	b->ui_written = true; b->ui_gray = grayscale != 0;         // (enqueued)
 	HIPCHK(hipEventRecord(c->ev_map, s));
 	Buffers bm = make_buffers(b, c->frame_ptr, 3);             // the minimap's own record slot
@@ -2210,7 +2256,7 @@ extern "C" SMHV_API int smhv_mask_marker_lines(smhv_ctx *c) {
 	HIPCHK(hipSetDevice(c->device));
 	smhv_batch *b = c->fb;
 	Buffers bf = make_buffers(b, c->frame_ptr, 0);
-	HIPCHK(launch_map_pass(b->g, bf, 1, MAP_MASK, 1, c->s_markers));
+	HIPCHK(launch_map_pass(b->g, bf, 1, MAP_MASK | MAP_BYTES, 1, c->s_markers));
 	HIPCHK(wait_stream(c->s_markers));
 	c->mask_valid = true;
 	return SMHV_OK;
@@ -2847,6 +2893,22 @@ extern "C" SMHV_API int smhv_debug_band_rows(uint32_t frame_w, uint32_t frame_h,
 	return SMHV_OK;
 }
 
+extern "C" SMHV_API int smhv_debug_batch_mask_state(smhv_batch *b, uint32_t *stale_frames, int *eager) {
+	if (!b) return fail(SMHV_E_INVALID, "null batch");
+	std::lock_guard<std::mutex> lk(b->mask_mu);
+	if (stale_frames) *stale_frames = b->mask_stale;
+	if (eager) *eager = b->mask_eager ? 1 : 0;
+	return SMHV_OK;
+}
+
+extern "C" SMHV_API int smhv_debug_mask_expand(smhv_batch *b, uint32_t n, void *stream) {
+	if (!b || n == 0 || n > b->max_frames) return fail(SMHV_E_INVALID, "debug_mask_expand: bad arguments");
+	CTX_OPEN(b->ctx);
+	HIPCHK(hipSetDevice(b->ctx->device));
+	HIPCHK(launch_mask_expand(b->g, b->d_bits, b->d_mask, n, (hipStream_t)stream));
+	return SMHV_OK;
+}
+
 extern "C" SMHV_API int smhv_debug_ingest_feed(smhv_ingest *q, uint32_t n, uint32_t *counter) {
 	if (!q || !counter) return fail(SMHV_E_INVALID, "ingest_feed: null argument");
 	for (uint32_t i = 0; i < n; ++i) {
@@ -3358,6 +3420,10 @@ extern "C" SMHV_API int smhv_batch_render_layers(smhv_batch *b, uint32_t first, 
 	rc = render_prepare(b, first, n, b->d_results + first, use_hm ? hm : nullptr, opt, &r);
 	if (rc) return rc;
 	hipStream_t s = (hipStream_t)stream;
+	if (layers->map_source == (uint32_t)SMHV_VIEW_LSD_INPUT) {  // the mask as bytes is made when it is read
+		rc = batch_materialize_mask(b, s);
+		if (rc) return rc;
+	}
 	rc = render_upload_prims(b, layers, &y, s);
 	if (rc) return rc;
 	render_bind(b, use_hm ? hm : nullptr);

@@ -1,7 +1,8 @@
 // smh_stream.hip -- the HBM-bound streaming kernels of the vision hot path (gfx950, wave64).
 //   k_button      red "Close Deployment" pixel count -> map_open           (lib.rs:116-133)
 //   k_map_pass    one streaming pass over the map ROI: ui_map RGBA + marker colour predicate +
-//                 L1 radius-1 dilation -> u8 mask + bit-packed mask + bbox   (lib.rs:137-171,253-280,357-375)
+//                 L1 radius-1 dilation -> bit-packed mask + bbox (+ the u8 mask with MAP_BYTES: the per-call path; a batch's
+//                 is k_mask_expand's, smh_misc.hip)                        (lib.rs:137-171,253-280,357-375)
 //   k_brq_pass    bottom-right quadrant: ocr_preprocess + find_scales_preprocess (lib.rs:173-251)
 //
 // Build with -ffp-contract=off and correctly rounded f32 division: several results are truncated to integers
@@ -246,7 +247,9 @@ __global__ void __launch_bounds__(1024) k_map_pass(Geom g, Buffers b, uint32_t f
 #pragma unroll
 	for (int c = 0; c < 4; ++c) D[c] = ((vmask >> c) & 1u) ? (D[c] & rowmask) : 0ull;
 
-	// ---- outputs: u8 mask rows and bit-packed rows ----
+	// ---- outputs: bit-packed rows, and with MAP_BYTES (the per-call path, which hands the mask straight to the host) the u8 mask
+	// rows; a batch run leaves those to k_mask_expand (smh_misc.hip) ----
+	const bool do_bytes = (flags & MAP_BYTES) != 0;            // (uniform: a kernel argument)
 	const uint32_t quads_padded = (g.m_quads + 15u) & ~15u;
 	const uint64_t any = D[0] | D[1] | D[2] | D[3];
 	const uint64_t lanes_set = __ballot(any != 0ull);
@@ -269,7 +272,7 @@ __global__ void __launch_bounds__(1024) k_map_pass(Geom g, Buffers b, uint32_t f
 			const int bit = row - r0 + 1;
 			const uint32_t nib = (uint32_t)((D[0] >> bit) & 1ull) | ((uint32_t)((D[1] >> bit) & 1ull) << 1) |
 			                     ((uint32_t)((D[2] >> bit) & 1ull) << 2) | ((uint32_t)((D[3] >> bit) & 1ull) << 3);
-			*(uint32_t *)(mp + (size_t)row * g.mask_pitch) = ((nib * 0x00204081u) & 0x01010101u) * 0xFFu;
+			if (do_bytes) *(uint32_t *)(mp + (size_t)row * g.mask_pitch) = ((nib * 0x00204081u) & 0x01010101u) * 0xFFu;
 			// gather 8 lanes' nibbles into one dword of the bit-packed row (lane l supplies bits 4(l%8)..)
 			uint32_t v = nib;
 			v |= __shfl_down(v, 1) << 4;
@@ -855,21 +858,18 @@ __device__ SMH_MAP_ITEM_INLINE void map_brq_item(MapKernelArgsPtr ka, uint32_t f
 		}
 		if (q < quads_padded && !lanes_set) {
 			// no marker pixel in this wave's 256 columns of the band (most of a map): rows of zeros, nothing to extract or gather
-			uint8_t *mbase = b.mask + (size_t)f * g.mask_stride;
+			// (the mask as bytes is not written here: k_mask_expand makes it from the bit rows when somebody asks, smh_misc.hip)
 			uint32_t *bbase = b.bits + (size_t)f * g.bits_stride_w;
-			const uint32_t moff = q * 4u, boff = (q >> 3) * 4u;
+			const uint32_t boff = (q >> 3) * 4u;
 			const bool bit_lane = (lane & 7u) == 0;
-			for (int row = r0; row < r1; ++row) {
-				*(uint32_t *)(mbase + (size_t)row * g.mask_pitch + moff) = 0u;
-				if (bit_lane) *(uint32_t *)((uint8_t *)bbase + (size_t)row * g.bits_pitch_w * 4u + boff) = 0u;
-			}
+			if (bit_lane)
+				for (int row = r0; row < r1; ++row) *(uint32_t *)((uint8_t *)bbase + (size_t)row * g.bits_pitch_w * 4u + boff) = 0u;
 		} else if (q < quads_padded) {
-			// u8 mask rows and bit-packed rows.  The column masks are walked one 32-row half at a time (32-bit bit-field
+			// bit-packed rows.  The column masks are walked one 32-row half at a time (32-bit bit-field
 			// extracts on a uniform bit index); eight lanes' nibbles meet in one dword through three DPP row shifts
 			// (lane l supplies bits 4 (l % 8) ..): no LDS round trip, nothing to wait for.
-			uint8_t *mbase = b.mask + (size_t)f * g.mask_stride;
 			uint32_t *bbase = b.bits + (size_t)f * g.bits_stride_w;
-			const uint32_t moff = q * 4u, boff = (q >> 3) * 4u;
+			const uint32_t boff = (q >> 3) * 4u;
 			const bool bit_lane = (lane & 7u) == 0;
 			uint32_t *tp = nullptr;
 			uint32_t tpitch = 0;
@@ -881,7 +881,6 @@ __device__ SMH_MAP_ITEM_INLINE void map_brq_item(MapKernelArgsPtr ka, uint32_t f
 				for (int row = row_lo; row < row_hi; ++row) {
 					const uint32_t bit = (uint32_t)(row - base) & 31u;
 					const uint32_t nib = ((d0 >> bit) & 1u) | (((d1 >> bit) & 1u) << 1) | (((d2 >> bit) & 1u) << 2) | (((d3 >> bit) & 1u) << 3);
-					*(uint32_t *)(mbase + (size_t)row * g.mask_pitch + moff) = nib_to_bytes(nib);
 					uint32_t v = nib;
 					v |= SMH_DPP(v, 0x101) << 4;                    // row_shl:1 -- lane l reads lane l + 1 (0 beyond the 16-lane row)
 					v |= SMH_DPP(v, 0x102) << 8;
@@ -1016,9 +1015,12 @@ hipError_t launch_map_brq_pass(const Geom &g, const Buffers &b, uint32_t n, uint
 	// (the grid-stride form and the three-set form never write the tile-major mask -- see below -- and keep the 58-row bands they had)
 	const uint32_t cap0 = tune ? tune->map_grid_cap : 0u;
 	const uint32_t RB0 = band_rows_for(g.rh, n, MAPQ_RB_MAX, false);
-	const bool no_tiles = b.tiled == nullptr || (tune && tune->map_deep) || (cap0 && cap0 < ((g.rh + RB0 - 1) / RB0) * n);
-	const uint32_t RB = no_tiles ? RB0 : band_rows_for(g.rh, n, MAPQ_RB_MAX, true, tune && tune->map_overlapped);
-	const uint32_t nbands = (g.rh + RB - 1) / RB, items = nbands * n;
+	bool no_tiles = b.tiled == nullptr || (tune && tune->map_deep) || (cap0 && cap0 < ((g.rh + RB0 - 1) / RB0) * n);
+	uint32_t RB = no_tiles ? RB0 : band_rows_for(g.rh, n, MAPQ_RB_MAX, true, tune && tune->map_overlapped);
+	uint32_t nbands = (g.rh + RB - 1) / RB, items = nbands * n;
+	// the tile rows' shorter bands can be more bands: where the cap is below THAT count the grid-stride form runs after all, and it
+	// runs with the bands it has always had
+	if (!no_tiles && cap0 && cap0 < items) { no_tiles = true; RB = RB0; nbands = (g.rh + RB - 1) / RB; items = nbands * n; }
 	unsigned lds = (g.m_block / 64u) * 640u;                 // 64 x (pixel, verdict, id) per wave
 	if (tune && tune->map_lds_total > map_brq_lds_bytes(g)) lds = tune->map_lds_total - map_brq_static_lds();
 	if (lds > 65536u) {                                      // more than 64 KB of dynamic LDS has to be allowed per function (and per device)
@@ -1067,8 +1069,10 @@ hipError_t launch_map_brq_pass(const Geom &g, const Buffers &b, uint32_t n, uint
 // gives THIS access pattern (smhv_debug_pattern_copy; bench.py: roofline_isolated.pattern_copy_GBps).  Same decomposition as
 // k_map_brq_pass (one workgroup per (frame, band of MAPQ_RB_MAX rows), one thread per quad across the ROI width): every ROI
 // quad is read once with a 16-byte load out of the 1920-px-pitch frame (986 of 1920 pixels of a row at 1080p), 16 bytes go to
-// the ui_map row, 4 to the mask row, and inside the bottom-right quadrant 4 each to the ocr and scales rows: per 256 1080p
-// frames 0.83 GB read and 1.14 GB written (the pass reads 0.95 GB: two halo rows per band on top).  What is stored is a
+// the ui_map row, and inside the bottom-right quadrant 4 each to the ocr and scales rows: per 256 1080p frames 0.83 GB read and
+// 0.94 GB written (the pass reads 0.95 GB: two halo rows per band on top; like the pass it writes no mask bytes -- those 4 per quad,
+// 0.21 GB per 256 frames, were in both until the byte form became k_mask_expand's; the pass's bit rows and tile-major words, 1 bit
+// per pixel each, have no counterpart here).  What is stored is a
 // cheap function of what was loaded, so that no load can be dropped.  NR = rows a thread has in flight (the pass: three sets of
 // four = 12); the bench line quotes the best of 4 / 8 / 12.
 // ------------------------------------------------------------------------------------------------
@@ -1084,7 +1088,6 @@ __global__ void __launch_bounds__(1024) k_pattern_copy(Geom g, Buffers b, uint32
 	if (q >= g.m_quads) return;
 	const uint8_t *fp = b.frames + (size_t)f * g.frame_bytes + ((size_t)g.ry * g.W + g.m_ax) * 4 + (size_t)q * 16;
 	uint8_t *up = b.ui + (size_t)f * g.ui_stride + (size_t)q * 16;
-	uint8_t *mp = b.mask + (size_t)f * g.mask_stride + (size_t)q * 4;
 	const int qy0 = (int)(g.qy - g.ry);
 	const int qq = (int)q - (int)((g.q_ax - g.m_ax) >> 2);
 	const bool in_q = qq >= 0 && (uint32_t)qq < g.q_quads;
@@ -1101,7 +1104,6 @@ __global__ void __launch_bounds__(1024) k_pattern_copy(Geom g, Buffers b, uint32
 			if (row >= r1) break;
 			*(uint4 *)(up + (size_t)row * g.ui_pitch) = v[k];
 			const uint32_t m = v[k].x ^ v[k].y ^ v[k].z ^ v[k].w;
-			*(uint32_t *)(mp + (size_t)row * g.mask_pitch) = m;
 			const int qrow = row - qy0;
 			if (in_q && qrow >= 0 && qrow < (int)g.qh) {
 				*(uint32_t *)(op + (size_t)qrow * g.ocr_pitch) = ~m;
