@@ -19,7 +19,8 @@ def _as_u32(v):
     return np.clip(np.trunc(v), 0, 4294967295).astype(np.int64)
 
 
-def find_longest_line(img, px, py, max_gap):
+def ray_lengths(img, px, py, max_gap):
+    """All 3600 rays of one candidate: (x_end, y_end, len²) as float32 arrays, in ray order."""
     h, w = img.shape
     n = len(DX)
     xs, ys = f32(px), f32(py)
@@ -54,6 +55,12 @@ def find_longest_line(img, px, py, max_gap):
     xe = np.where(zero, x - DX, xs).astype(f32); ye = np.where(zero, y - DY, ys).astype(f32)
     ddx = (xs - xe).astype(f32); ddy = (ys - ye).astype(f32)
     length = (ddx * ddx + ddy * ddy).astype(f32)
+    return xe, ye, length
+
+
+def find_longest_line(img, px, py, max_gap):
+    xs, ys = f32(px), f32(py)
+    xe, ye, length = ray_lengths(img, px, py, max_gap)
     best, best_len = 0, f32(0)                                              # rayon reduce: identity (zero line, 0.0), b wins ties
     bx, by, ex, ey = f32(0), f32(0), f32(0), f32(0)
     m = length.max()
