@@ -245,7 +245,15 @@ SMHV_API int smhv_batch_run(smhv_batch *b, const void *d_frames, uint32_t n, uin
  * pipeline's submission into this batch) writes its frames' bytes with one more small kernel on its own stream right behind its
  * streaming pass (in a frame-granular pipeline ahead of the publication, so inside the submission's completion).  So the rule for
  * every pointer here stays "a run's results are in memory when its stream gets there"; a caller that never asks for d_mask never
- * pays for it (19 % of the streaming pass's written bytes at 1080p). */
+ * pays for it (19 % of the streaming pass's written bytes at 1080p).
+ * d_ui, the ui_map as RGBA8, is owed in the same way by GREY runs: a grey ui_map is (l, l, l, 255), so a grey run (grayscale != 0,
+ * without SMHV_STAGE_HEIGHTMAP_OVERLAY) writes one luma byte per pixel into a plane of the library's own, and the library makes the
+ * RGBA rows from it when one of ITS readers wants them (smhv_batch_read_image, smhv_batch_render*, smhv_batch_probe /
+ * smhv_batch_render_debug, smhv_batch_feed*), on the stream that call is given.  Colour runs and overlay runs write d_ui directly,
+ * and a frame a run finds closed keeps its older image whichever run wrote it.  A call with a non-NULL d_ui is the same switch as
+ * for d_mask: it waits for the device, brings the slab up to date, and from then on grey runs of this batch write RGBA themselves.
+ * Pass NULL for d_ui unless you read the slab with a kernel or a copy of your own: two thirds of the grey streaming pass's written
+ * bytes at 1080p are the three bytes per pixel it saves. */
 SMHV_API int smhv_batch_device_ptrs(smhv_batch *b, void **d_results, void **d_ui, void **d_mask, void **d_ocr, void **d_scales, void **d_bits);
 /* The marker mask a third time, as the streaming passes leave it for the line search (and for any host kernel that wants the
  * marker pixels without scanning a 1-4 % full image): TILE-MAJOR, 32 x 8 px tiles of the bit-packed rows -- tile (ty, wx) = rows

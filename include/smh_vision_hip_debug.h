@@ -113,6 +113,14 @@ SMHV_API int smhv_debug_feed_gray_form(uint32_t form);
  * their expansion is enqueued.  *eager <- 1 once a caller has asked smhv_batch_device_ptrs for d_mask: every run expands its own
  * frames behind its pass and nothing is ever owed.  Either pointer may be NULL. */
 SMHV_API int smhv_debug_batch_mask_state(smhv_batch *b, uint32_t *stale_frames, int *eager);
+/* host state only: how the batch stands with its RGBA ui slab (d_ui).  *stale_frames <- frames [0, stale_frames) that may have their
+ * newest ui_map in the luma plane (grey runs since the last expansion; which of them do is a byte per frame on the device): the next
+ * reader of the slab has them expanded; 0 = the slab is current or its expansion is enqueued.  *eager <- 1 once a caller has asked
+ * smhv_batch_device_ptrs for d_ui: grey runs write the RGBA slab themselves and nothing is ever owed.  Either pointer may be NULL. */
+SMHV_API int smhv_debug_batch_ui_state(smhv_batch *b, uint32_t *stale_frames, int *eager);
+/* what every reader of d_ui does first: the frames owed to the slab are expanded on `stream` (k_ui_expand; nothing owed: `stream`
+ * waits for the last expansion).  For tests and for measuring the expansion alone (tools/ui_on_demand_cost.py). */
+SMHV_API int smhv_debug_batch_materialize_ui(smhv_batch *b, void *stream);
 /* measuring: k_mask_expand alone -- the byte mask of frames [0, n) from their bit rows as they stand, on `stream`; changes no state
  * (the bytes it writes are the ones any expansion writes).  tools/mask_on_demand_cost.py times it. */
 SMHV_API int smhv_debug_mask_expand(smhv_batch *b, uint32_t n, void *stream);

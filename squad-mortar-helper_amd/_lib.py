@@ -233,6 +233,8 @@ SIGNATURES = {
     "smhv_ui_map": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "smhv_debug_pattern_copy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "smhv_debug_batch_mask_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    "smhv_debug_batch_ui_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    "smhv_debug_batch_materialize_ui": (C.c_int, [C.c_void_p, C.c_void_p]),
     "smhv_debug_mask_expand": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "smhv_debug_marker_table": (C.c_int, [C.c_void_p, C.c_void_p]),
     "smhv_ingest_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),

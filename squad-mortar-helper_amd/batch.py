@@ -45,7 +45,7 @@ _PTR_KEYS = ("results", "ui", "mask", "ocr", "scales", "bits")
 
 
 class _DevicePtrs(Mapping):
-    """FrameBatch.device_ptrs(): read-only; the "mask" entry asks the library for d_mask the first time it is read."""
+    """FrameBatch.device_ptrs(): read-only; the "mask" and "ui" entries ask the library for d_mask / d_ui the first time they are read."""
 
     def __init__(self, batch, ptrs):
         self._batch, self._ptrs = batch, ptrs
@@ -53,6 +53,8 @@ class _DevicePtrs(Mapping):
     def __getitem__(self, key):
         if key == "mask" and self._ptrs["mask"] is None:
             self._ptrs["mask"] = self._batch._mask_ptr()
+        if key == "ui" and self._ptrs["ui"] is None:
+            self._ptrs["ui"] = self._batch._ui_ptr()
         return self._ptrs[key]
 
     def __iter__(self):
@@ -127,12 +129,13 @@ class FrameBatch:
         return out
 
     def device_ptrs(self):
-        """Mapping of the output slabs' device addresses ("results", "ui", "mask", "ocr", "scales", "bits").  "mask" is fetched when it
-        is first read: asking the library for d_mask makes the batch write the byte mask behind every run from then on
-        (smhv_batch_device_ptrs), which a caller that reads the other slabs only never pays."""
+        """Mapping of the output slabs' device addresses ("results", "ui", "mask", "ocr", "scales", "bits").  "mask" and "ui" are fetched
+        when they are first read: asking the library for d_mask makes the batch write the byte mask behind every run from then on, and
+        asking it for d_ui makes grey runs write the RGBA slab themselves instead of the luma plane (smhv_batch_device_ptrs) -- which a
+        caller that reads the other slabs only never pays."""
         p = [C.c_void_p() for _ in range(6)]
         args = [C.byref(x) for x in p]
-        args[2] = None
+        args[1] = args[2] = None
         L.check(self._lib.smhv_batch_device_ptrs(self._b, *args))
         return _DevicePtrs(self, dict(zip(_PTR_KEYS, [x.value for x in p])))
 
@@ -140,6 +143,21 @@ class FrameBatch:
         m = C.c_void_p()
         L.check(self._lib.smhv_batch_device_ptrs(self._b, None, None, C.byref(m), None, None, None))
         return m.value
+
+    def _ui_ptr(self):
+        u = C.c_void_p()
+        L.check(self._lib.smhv_batch_device_ptrs(self._b, None, C.byref(u), None, None, None, None))
+        return u.value
+
+    def ui_state(self):
+        """(frames whose RGBA ui slab may be owed, whether grey runs write it themselves): smhv_debug_batch_ui_state."""
+        stale, eager = C.c_uint32(0), C.c_int(0)
+        L.check(self._lib.smhv_debug_batch_ui_state(self._b, C.byref(stale), C.byref(eager)))
+        return int(stale.value), bool(eager.value)
+
+    def materialize_ui(self, stream=0):
+        """Diagnostic: what the grey runs so far owe the RGBA ui slab is made on `stream` now (what every reader of the slab does first)."""
+        L.check(self._lib.smhv_debug_batch_materialize_ui(self._b, C.c_void_p(stream)))
 
     def mask_state(self):
         """(frames whose byte mask is owed, whether every run writes it): smhv_debug_batch_mask_state."""

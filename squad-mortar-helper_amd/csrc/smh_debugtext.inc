@@ -138,6 +138,8 @@ extern "C" SMHV_API int smhv_batch_probe(smhv_batch *b, uint32_t first, uint32_t
 	DebugRun r;
 	int rc = debug_prepare(b, ropt, probe_options(&d, points, n_points), false, s, &r);
 	if (rc) return rc;
+	rc = batch_materialize_ui(b, s);                              // the RGBA slab is made when it is read (smh_runtime.cpp)
+	if (rc) return rc;
 	r.ui = b->d_ui + (size_t)first * b->g.ui_stride;
 	r.aux = b->d_aux + first;
 	r.res = b->d_results + first;
@@ -184,6 +186,8 @@ extern "C" SMHV_API int smhv_batch_render_debug(smhv_batch *b, uint32_t first, u
 	HIPCHK(hipStreamWaitEvent(s, b->ev_render, 0));               // behind the render and the labels that drew the images, whatever stream they took
 	DebugRun r;
 	rc = debug_prepare(b, ropt, dopt, true, s, &r);
+	if (rc) return rc;
+	rc = batch_materialize_ui(b, s);                              // the RGBA slab is made when it is read (smh_runtime.cpp)
 	if (rc) return rc;
 	r.ui = b->d_ui + (size_t)first * b->g.ui_stride;
 	r.aux = b->d_aux + first;

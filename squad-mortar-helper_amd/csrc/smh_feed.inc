@@ -199,6 +199,8 @@ extern "C" SMHV_API int smhv_batch_feed_view(smhv_batch *b, smhv_feed *f, uint32
 		rc = batch_materialize_mask(b, (hipStream_t)stream);
 		if (rc) return rc;
 	}
+	rc = batch_materialize_ui(b, (hipStream_t)stream);         // ... and so is the RGBA ui slab
+	if (rc) return rc;
 	return feed_enqueue(f, v, b->d_results + first, first, n, flags, (hipStream_t)stream);
 }
 
@@ -253,6 +255,8 @@ extern "C" SMHV_API int smhv_feed_frame_view(smhv_ctx *c, smhv_feed *f, const sm
 	if (map_source > (uint32_t)SMHV_VIEW_CROPPED_BRQ) return fail(SMHV_E_INVALID, "feed_frame_view: unknown map source %u", map_source);
 	smhv_batch *b = c->fb;
 	const Geom &g = b->g;
+	rc = batch_materialize_ui(b, c->s_main);                   // (the single-frame batch's pass writes RGBA: nothing is ever owed)
+	if (rc) return rc;
 	FeedSrc v = feed_src_ui(g, b->d_ui);
 	if (map_source != (uint32_t)SMHV_VIEW_NONE) {             // smhv_get_debug_view's image of this moment, and its size
 		const int which = (int)map_source;

@@ -431,7 +431,20 @@ enum : uint32_t { MAP_UI = 1u, MAP_MASK = 2u, MAP_BYTES = 4u, MAP_PRIO = 0x100u,
 // made from the bit rows when a reader asks for it (launch_mask_expand; smh_runtime.cpp, batch_materialize_mask).
 enum : uint32_t { BRQ_OCR = 1u, BRQ_SCALES = 2u };
 
-hipError_t launch_button(const Geom &g, const Buffers &b, uint32_t n, int force_open, hipStream_t s);
+// ---- the grey ui_map as a luma plane ------------------------------------------------------------------------------------------
+// A grey ui_map is (l,l,l,255): three of every four bytes repeat a byte the pass also writes.  A grey batch run therefore writes
+// one byte per pixel into a plane of its own -- the ui slab's quads, rows and frames at a quarter of the pitch and stride -- and
+// the RGBA slab is made from it when a reader asks (launch_ui_expand; smh_runtime.cpp, batch_materialize_ui), as the byte mask is
+// made from the bit rows.  Unlike the mask the slab has two writers (colour runs, overlay runs and the runs of a batch whose caller
+// holds the slab write RGBA directly) and a frame a run finds closed keeps its older image, so ONE persistent byte per frame says
+// where a frame's newest ui_map lies: UI_FORM_LUMA the plane, UI_FORM_RGBA the slab.  k_button writes it for the open frames of a
+// run with the ui stage; k_ui_expand expands exactly the flagged frames and the flags are cleared behind it.
+// The passes take the plane where they take the slab: Buffers::ui = the plane and `grayscale` = 2.
+enum : uint32_t { UI_FORM_RGBA = 0u, UI_FORM_LUMA = 1u, UI_FORM_KEEP = 2u };
+hipError_t launch_button(const Geom &g, const Buffers &b, uint32_t n, int force_open, hipStream_t s, uint8_t *ui_form = nullptr, uint32_t ui_luma = UI_FORM_KEEP);
+// frames [0, n): where ui_form[f] == UI_FORM_LUMA, the frame's RGBA rows (d_ui) from its luma plane (d_luma); clears those flags behind it
+hipError_t launch_ui_expand(const Geom &g, const uint8_t *d_luma, uint8_t *d_ui, uint8_t *ui_form, uint32_t n, hipStream_t s);
+// grayscale: 0 = colour, 1 = (l,l,l,255), 2 = the luma plane (b.ui = the plane; not with MAP_BYTES)
 // tiles_wanted: the batch path (the mask also tile-major where the bands allow it: band_rows_for); the per-call path leaves it
 hipError_t launch_map_pass(const Geom &g, const Buffers &b, uint32_t n, uint32_t flags, int grayscale, hipStream_t s, bool tiles_wanted = false, bool overlapped = false);
 // map pass + quadrant pass in one (the quadrant pixels are read once); flags: MAP_*, qflags: BRQ_*

@@ -218,6 +218,8 @@ static int render_map_text(smhv_ctx *c, const smhv_heightmap *hm, const smhv_ren
 			DebugRun dr;
 			int rc2 = debug_prepare(b, opt, dopt, true, c->s_main, &dr);
 			if (rc2) return rc2;
+			rc2 = batch_materialize_ui(b, c->s_main);              // (the single-frame batch's pass writes RGBA: nothing is ever owed)
+			if (rc2) return rc2;
 			dr.ui = b->d_ui;
 			dr.aux = b->d_aux;
 			dr.res = b->d_results + 3;

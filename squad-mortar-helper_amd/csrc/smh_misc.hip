@@ -459,6 +459,45 @@ hipError_t launch_mask_expand(const Geom &g, const uint32_t *d_bits, uint8_t *d_
 	return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// k_ui_expand: the RGBA ui slab of the frames whose newest ui_map lies in the luma plane (smh_kernels.h, "the grey ui_map as a luma
+// plane") -- made when a reader of the slab asks for it (smh_runtime.cpp, batch_materialize_ui), not by every grey pass.  The plane
+// is the slab at a quarter of the pitch and stride, neither has a gap between rows or frames: dword j of the plane is the four luma
+// bytes of 16-byte group j of the slab.  grid = (groups of a frame / 256, frames): a workgroup reads its frame's flag once (a
+// uniform load) and leaves a frame whose slab is already the truth alone; a thread reads a dword (a wave: 256 contiguous bytes) and
+// stores (l,l,l,255) four times (a wave: 1 KB, contiguous).  Every quad the passes write (the first `quads` of a row's `pitch_q`: the
+// padded pixels left of m_xoff and right of the ROI's last included) and none of the others, which no pass writes in either form: the
+// slab is what the grey-RGBA pass would have left, byte for byte.  Memory-bound: 1 byte read per 4 written.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_ui_expand(const uint32_t *__restrict__ luma, uint4 *__restrict__ ui, const uint8_t *__restrict__ form, uint32_t groups,
+                                                   uint32_t pitch_q, uint32_t quads) {
+	const uint32_t f = blockIdx.y;
+	if (form[f] != UI_FORM_LUMA) return;
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if (i >= groups || i % pitch_q >= quads) return;
+	const size_t j = (size_t)f * groups + i;
+	const uint32_t v = luma[j];
+	uint4 o;
+	o.x = __builtin_amdgcn_perm(0u, v, 0x0D000000u);           // byte k of v three times, then 0xFF (selector 0x0D: the constant 0xFF)
+	o.y = __builtin_amdgcn_perm(0u, v, 0x0D010101u);
+	o.z = __builtin_amdgcn_perm(0u, v, 0x0D020202u);
+	o.w = __builtin_amdgcn_perm(0u, v, 0x0D030303u);
+	ui[j] = o;
+}
+hipError_t launch_ui_expand(const Geom &g, const uint8_t *d_luma, uint8_t *d_ui, uint8_t *ui_form, uint32_t n, hipStream_t s) {
+	if ((g.ui_stride & 15u) || g.ui_stride / 16u > 0xFFFFFF00ull || n == 0) return hipErrorInvalidValue;
+	const uint32_t groups = (uint32_t)(g.ui_stride / 16u);
+	hipError_t e = hipSuccess;
+	for (uint32_t done = 0; done < n && e == hipSuccess; done += 65535u) {   // (the grid's second dimension)
+		const uint32_t k = std::min(n - done, 65535u);
+		hipLaunchKernelGGL(k_ui_expand, dim3((groups + 255u) / 256u, k), dim3(256), 0, s, (const uint32_t *)d_luma + (size_t)done * groups, (uint4 *)d_ui + (size_t)done * groups,
+		                   (const uint8_t *)ui_form + done, groups, (uint32_t)(g.ui_pitch / 16u), g.m_quads);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemsetAsync(ui_form, 0, n, s);  // (behind the expansion on the same stream: the slab now holds these frames' truth)
+	return e;
+}
+
 hipError_t launch_debug_view(const Geom &g, const Buffers &b, uint32_t frame, int which, int isolated, uint8_t *d_rgba, hipStream_t s) {
 	const bool brq = which == SMHV_VIEW_OCR_INPUT || which == SMHV_VIEW_FIND_SCALES_INPUT || which == SMHV_VIEW_CROPPED_BRQ;
 	const uint32_t npx = brq ? g.qw * g.qh : g.rw * g.rh;

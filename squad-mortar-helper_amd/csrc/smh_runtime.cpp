@@ -251,6 +251,16 @@ struct smhv_batch {
 	uint32_t mask_stale = 0;
 	bool mask_eager = false;
 	hipEvent_t ev_mask = nullptr;
+	// The grey ui_map likewise (smh_kernels.h, "the grey ui_map as a luma plane"): a grey run writes d_ui_luma, one byte per pixel, and
+	// d_ui is made from it when somebody reads it (batch_materialize_ui).  d_ui_form: one persistent byte per frame on the device,
+	// UI_FORM_LUMA where the plane holds the frame's newest ui_map (k_button sets it, k_ui_expand's launcher clears it).  ui_stale:
+	// frames [0, ui_stale) may carry that flag (the largest n of the lazy runs since the last expansion); ev_ui: behind the last
+	// expansion; ui_eager: a caller holds d_ui itself (smhv_batch_device_ptrs), so grey runs write RGBA as colour runs do.  Under ui_mu.
+	uint8_t *d_ui_luma = nullptr, *d_ui_form = nullptr;
+	std::mutex ui_mu;
+	uint32_t ui_stale = 0;
+	bool ui_eager = false;
+	hipEvent_t ev_ui = nullptr;
 	smhv_render_prim *h_prims = nullptr, *d_prims = nullptr;
 	hipEvent_t ev_prims = nullptr;
 	// smhv_batch_render_labels: the label slab and the cull entries of its slots (allocated by the first call), the extras' way to
@@ -618,6 +628,8 @@ extern "C" SMHV_API int smhv_batch_create(smhv_ctx *c, uint32_t W, uint32_t H, u
 		if (_e != hipSuccess) { smhv_batch_destroy(b); return fail(SMHV_E_HIP, "allocating %zu bytes: %s", (size_t)(bytes), hipGetErrorString(_e)); } \
 	} while (0)
 	ALLOC0(b->d_ui, g.ui_stride * n);
+	ALLOC0(b->d_ui_luma, g.ui_stride / 4 * n);
+	ALLOC0(b->d_ui_form, n);
 	ALLOC0(b->d_mask, g.mask_stride * n);
 	ALLOC0(b->d_bits, g.bits_stride_w * 4 * n);
 	ALLOC0(b->d_tiled, tiled_stride_w(g) * 4 * n);
@@ -639,6 +651,7 @@ extern "C" SMHV_API int smhv_batch_create(smhv_ctx *c, uint32_t W, uint32_t H, u
 		if (e == hipSuccess) { memset(b->h_err, 0, sizeof(BatchError)); e = hipHostGetDevicePointer((void **)&b->d_err, b->h_err, 0); }
 		if (e == hipSuccess) e = hipEventCreateWithFlags(&b->ev_map_done, hipEventDisableTiming);
 		if (e == hipSuccess) e = hipEventCreateWithFlags(&b->ev_mask, hipEventDisableTiming);
+		if (e == hipSuccess) e = hipEventCreateWithFlags(&b->ev_ui, hipEventDisableTiming);
 		// Only for frame sizes that need them: a process has few hardware queues, and every extra stream makes it more
 		// likely that two independent branches share one (measured: 10 % off the pipelined 1080p throughput).
 		if (max_frames > 1 && !lsd_rows_only(b->g)) {
@@ -658,7 +671,7 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	if (!b) return;
 	if (b->ctx) (void)hipSetDevice(b->ctx->device);
 	(void)hipDeviceSynchronize();
-	void *ptrs[] = {b->d_ui, b->d_mask, b->d_bits, b->d_tiled, b->d_occ, b->d_ocr, b->d_scales, b->d_aux, b->d_results, b->d_anchors, b->d_bars, b->d_farm,
+	void *ptrs[] = {b->d_ui, b->d_ui_luma, b->d_ui_form, b->d_mask, b->d_bits, b->d_tiled, b->d_occ, b->d_ocr, b->d_scales, b->d_aux, b->d_results, b->d_anchors, b->d_bars, b->d_farm,
 	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run, b->d_overlay, b->d_render, b->d_prims, b->d_labels,
 	                b->d_label_cull, b->d_label_extra, b->d_probes, b->d_dbg_items, b->d_dbg_pool, b->d_dbg_stage};
 	for (void *p : ptrs)
@@ -693,6 +706,7 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	if (b->ev_join) (void)hipEventDestroy(b->ev_join);
 	if (b->ev_map_done) (void)hipEventDestroy(b->ev_map_done);
 	if (b->ev_mask) (void)hipEventDestroy(b->ev_mask);
+	if (b->ev_ui) (void)hipEventDestroy(b->ev_ui);
 	for (auto e : b->ev_probe) if (e) (void)hipEventDestroy(e);
 	if (b->lsd_fork.s1) (void)hipStreamDestroy(b->lsd_fork.s1);
 	if (b->lsd_fork.s2) (void)hipStreamDestroy(b->lsd_fork.s2);
@@ -921,6 +935,19 @@ static int batch_materialize_mask(smhv_batch *b, hipStream_t stream) {
 	return SMHV_OK;
 }
 
+// The RGBA ui slab, on demand: the same contract for d_ui.  Something stale: k_ui_expand over the frames of [0, ui_stale) whose
+// newest ui_map lies in the luma plane (d_ui_form), their flags cleared behind it, the event behind that.  A frame a run skipped
+// (a closed map) keeps its older image in whichever form holds it; a frame no run has written reads the zeros of its creation.
+static int batch_materialize_ui(smhv_batch *b, hipStream_t stream) {
+	std::lock_guard<std::mutex> lk(b->ui_mu);
+	if (b->ui_stale) {
+		HIPCHK(launch_ui_expand(b->g, b->d_ui_luma, b->d_ui, b->d_ui_form, std::min(b->ui_stale, b->max_frames), stream));
+		HIPCHK(hipEventRecord(b->ev_ui, stream));
+		b->ui_stale = 0;
+	} else HIPCHK(hipStreamWaitEvent(stream, b->ev_ui, 0));    // (no-op before the first expansion)
+	return SMHV_OK;
+}
+
 struct SvcPublish { SvcCtl *ctl; unsigned long long *ring; SvcSlot *slots; uint32_t slot, seq, ring_log2; const uint32_t *cull_tab; bool have_cull; hipStream_t s_pro; hipEvent_t ev_pro;
                     bool *published; };   // <- set once k_svc_publish has been enqueued (from then on the device WILL complete the submission)
 static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint32_t stages, int grayscale, uint32_t max_gap,
@@ -938,7 +965,10 @@ static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint3
 	Buffers bf = make_buffers(b, (const uint8_t *)d_frames, 0);
 	OverlayRun orun{};
 	if (stages & SMHV_STAGE_HEIGHTMAP_OVERLAY) {
-		int rc = overlay_prepare(b, b->fire_hm, b->fire_opt.flags, bf.results, s, &orun);
+		// the overlay reads the ui slab inside the run: this run writes RGBA itself (below), and what earlier runs owe the slab is made first
+		int rc = batch_materialize_ui(b, s);
+		if (rc) return rc;
+		rc = overlay_prepare(b, b->fire_hm, b->fire_opt.flags, bf.results, s, &orun);
 		if (rc) return rc;
 	}
 	// the helper exchange of k_lsd_tile tags its words with 16 bits of the launch epoch: start every 65,536th launch of a batch
@@ -980,8 +1010,19 @@ static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint3
 	hipEvent_t *ev = t ? b->ev[b->timed_runs % smhv_batch::TIMING_RING] : nullptr;
 #define STAGE_BEGIN(i, st) do { if (t) HIPCHK(hipEventRecord(ev[2 * (i)], (st))); } while (0)
 #define STAGE_END(i, st) do { if (t) HIPCHK(hipEventRecord(ev[2 * (i) + 1], (st))); } while (0)
+	// A grey run's ui_map goes into the luma plane, one byte per pixel, and the RGBA slab is owed to whoever reads it
+	// (batch_materialize_ui) -- unless the run itself reads the slab (the overlay) or a caller holds it (ui_eager): then, and in
+	// colour, the pass writes RGBA as it always has.  k_button notes per open frame which form this run leaves.
+	const bool ui_stage = (stages & SMHV_STAGE_UI_MAP) != 0u;
+	bool ui_lazy = false;
+	if (ui_stage) {
+		std::lock_guard<std::mutex> lk(b->ui_mu);
+		ui_lazy = grayscale && !(stages & SMHV_STAGE_HEIGHTMAP_OVERLAY) && !b->ui_eager;
+		if (ui_lazy) { b->ui_stale = std::max(b->ui_stale, n); bf.ui = b->d_ui_luma; }
+	}
+	const int pass_gray = ui_lazy ? 2 : (grayscale ? 1 : 0);
 	STAGE_BEGIN(0, sb);
-	HIPCHK(launch_button(g, bf, n, 0, sb));
+	HIPCHK(launch_button(g, bf, n, 0, sb, b->d_ui_form, ui_stage ? (ui_lazy ? UI_FORM_LUMA : UI_FORM_RGBA) : UI_FORM_KEEP));
 	STAGE_END(0, sb);
 	if (sb != s) {
 		HIPCHK(hipEventRecord(svc->ev_pro, sb));
@@ -997,8 +1038,8 @@ static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint3
 	if (scales) qflags |= BRQ_SCALES;
 	if (b->probe) HIPCHK(hipEventRecord(b->ev_probe[0], s));
 	STAGE_BEGIN(1, s);
-	if (mflags && qflags) HIPCHK(launch_map_brq_pass(g, bf, n, mflags, qflags, grayscale, 0, 1, s, &b->tune));
-	else if (mflags) HIPCHK(launch_map_pass(g, bf, n, mflags, grayscale, s, true, b->tune.map_overlapped != 0u));
+	if (mflags && qflags) HIPCHK(launch_map_brq_pass(g, bf, n, mflags, qflags, pass_gray, 0, 1, s, &b->tune));
+	else if (mflags) HIPCHK(launch_map_pass(g, bf, n, mflags, pass_gray, s, true, b->tune.map_overlapped != 0u));
 	if (mflags & MAP_MASK) {
 		// the mask as bytes: owed to whoever reads it (batch_materialize_mask) -- or, for a caller that holds d_mask itself, made
 		// here, behind the pass and ahead of everything a completion of this run is taken from (the publication included)
@@ -1127,7 +1168,17 @@ extern "C" SMHV_API int smhv_batch_lsd_coop_stats(smhv_batch *b, uint32_t first,
 extern "C" SMHV_API int smhv_batch_device_ptrs(smhv_batch *b, void **r, void **ui, void **mask, void **ocr, void **scales, void **bits) {
 	if (!b) return fail(SMHV_E_INVALID, "null batch");
 	if (r) *r = b->d_results;
-	if (ui) *ui = b->d_ui;
+	if (ui) {
+		// The same for d_ui: what the grey runs so far owe the slab is made now, and from here on grey runs write RGBA themselves.
+		CTX_OPEN(b->ctx);
+		HIPCHK(hipSetDevice(b->ctx->device));
+		{ std::lock_guard<std::mutex> lk(b->ui_mu); b->ui_eager = true; }
+		HIPCHK(hipDeviceSynchronize());
+		int rc = batch_materialize_ui(b, b->ctx->s_main);
+		if (rc) return rc;
+		HIPCHK(wait_stream(b->ctx->s_main));
+		*ui = b->d_ui;
+	}
 	if (mask) {
 		// A caller that holds d_mask reads it whenever it likes: the bytes of every run so far are made now (after everything enqueued
 		// on the device, and waited for), and from here on every run of this batch expands its own frames behind its pass
@@ -1205,6 +1256,11 @@ extern "C" SMHV_API int smhv_batch_read_image(smhv_batch *b, int which, uint32_t
 	switch (which) {
 	case 100:
 	case SMHV_IMAGE_HEIGHTMAP_OVERLAY:
+		{
+			int rc = batch_materialize_ui(b, b->ctx->s_main);     // (the runs are complete: the device was waited for above)
+			if (rc) return rc;
+			HIPCHK(wait_stream(b->ctx->s_main));
+		}
 		HIPCHK(hipMemcpy2D(out, (size_t)g.rw * 4, (which == 100 ? b->d_ui : b->d_overlay) + frame * g.ui_stride + (size_t)g.m_xoff * 4, g.ui_pitch, (size_t)g.rw * 4,
 		                   g.rh, hipMemcpyDeviceToHost));
 		break;
@@ -2901,6 +2957,21 @@ extern "C" SMHV_API int smhv_debug_batch_mask_state(smhv_batch *b, uint32_t *sta
 	return SMHV_OK;
 }
 
+extern "C" SMHV_API int smhv_debug_batch_ui_state(smhv_batch *b, uint32_t *stale_frames, int *eager) {
+	if (!b) return fail(SMHV_E_INVALID, "null batch");
+	std::lock_guard<std::mutex> lk(b->ui_mu);
+	if (stale_frames) *stale_frames = b->ui_stale;
+	if (eager) *eager = b->ui_eager ? 1 : 0;
+	return SMHV_OK;
+}
+
+extern "C" SMHV_API int smhv_debug_batch_materialize_ui(smhv_batch *b, void *stream) {
+	if (!b) return fail(SMHV_E_INVALID, "null batch");
+	CTX_OPEN(b->ctx);
+	HIPCHK(hipSetDevice(b->ctx->device));
+	return batch_materialize_ui(b, (hipStream_t)stream);
+}
+
 extern "C" SMHV_API int smhv_debug_mask_expand(smhv_batch *b, uint32_t n, void *stream) {
 	if (!b || n == 0 || n > b->max_frames) return fail(SMHV_E_INVALID, "debug_mask_expand: bad arguments");
 	CTX_OPEN(b->ctx);
@@ -3258,6 +3329,8 @@ extern "C" SMHV_API int smhv_batch_render(smhv_batch *b, uint32_t first, uint32_
 	if (rc) return rc;
 	render_bind(b, use_hm ? hm : nullptr);
 	hipStream_t s = (hipStream_t)stream;
+	rc = batch_materialize_ui(b, s);                           // the RGBA slab is made when it is read
+	if (rc) return rc;
 	// at most 65,535 frames per launch (the grid's third dimension)
 	for (uint32_t done = 0; done < n;) {
 		const uint32_t k = std::min(n - done, 65535u);
@@ -3424,6 +3497,8 @@ extern "C" SMHV_API int smhv_batch_render_layers(smhv_batch *b, uint32_t first, 
 		rc = batch_materialize_mask(b, s);
 		if (rc) return rc;
 	}
+	rc = batch_materialize_ui(b, s);                           // ... and so is the RGBA ui slab
+	if (rc) return rc;
 	rc = render_upload_prims(b, layers, &y, s);
 	if (rc) return rc;
 	render_bind(b, use_hm ? hm : nullptr);

@@ -47,8 +47,12 @@ __device__ __forceinline__ uint32_t tile_occupancy(uint64_t rows_any, uint32_t l
 
 // ------------------------------------------------------------------------------------------------
 // k_button: one workgroup per frame.  Also resets the per-frame scratch for the later passes.
+// ui_form (null: none) / ui_luma: the batch's persistent byte per frame that says which form holds the frame's newest ui_map --
+// 1 the luma plane, 0 the RGBA slab (smh_kernels.h, "the grey ui_map as a luma plane").  A run with the ui stage sets it for
+// the frames it finds open (ui_luma: UI_FORM_RGBA / UI_FORM_LUMA, what its pass is about to write) and leaves it alone for the
+// closed ones, which keep their older image in whichever form it has; a run without the stage passes UI_FORM_KEEP.
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_button(Geom g, Buffers b, int force_open) {
+__global__ void __launch_bounds__(256) k_button(Geom g, Buffers b, int force_open, uint8_t *ui_form, uint32_t ui_luma) {
 	const uint32_t f = blockIdx.x;
 	const uint8_t *fp = b.frames + (size_t)f * g.frame_bytes;
 	__shared__ uint32_t s_cnt;
@@ -87,6 +91,7 @@ __global__ void __launch_bounds__(256) k_button(Geom g, Buffers b, int force_ope
 		a.red = red; a.n_mask_px = 0;
 		a.y_min = 0xFFFFFFFFu; a.y_max = 0; a.w_min = 0xFFFFFFFFu; a.w_max = 0; a.tiles = 0;
 		b.aux[f] = a;
+		if (ui_form && ui_luma != UI_FORM_KEEP && a.open) ui_form[f] = (uint8_t)ui_luma;
 	}
 }
 
@@ -110,194 +115,14 @@ __global__ void __launch_bounds__(256) k_button(Geom g, Buffers b, int force_ope
 
 template <bool GRAY, bool TILES>
 __global__ void __launch_bounds__(1024) k_map_pass(Geom g, Buffers b, uint32_t flags, uint32_t RB) {
-	const uint32_t f = blockIdx.y;
-	if (!b.aux[f].open) return;
-	const uint32_t q = threadIdx.x, lane = q & 63u, wave = q >> 6, nwave = blockDim.x >> 6;
-	const int r0 = (int)(blockIdx.x * RB);
-	const int r1 = min(r0 + (int)RB, (int)g.rh);
-	const bool qact = q < g.m_quads;
-	uint32_t vmask = 0;
-#pragma unroll
-	for (int c = 0; c < 4; ++c)
-		if ((uint32_t)(4 * q + c - g.m_xoff) < g.rw) vmask |= 1u << c;
-	if (!qact) vmask = 0;
-
-	const uint8_t *fp = b.frames + (size_t)f * g.frame_bytes + ((size_t)g.ry * g.W + g.m_ax + 4 * q) * 4;
-	uint8_t *uip = b.ui + (size_t)f * g.ui_stride + (size_t)q * 16;
-	const size_t row_bytes = (size_t)g.W * 4;
-
-	uint64_t P[4] = {0, 0, 0, 0};
-	const int rs = max(r0 - 1, 0), re = min(r1, (int)g.rh - 1);
-	const bool do_ui = (flags & MAP_UI) != 0, do_mask = (flags & MAP_MASK) != 0;
-
-	// Software pipeline: the loads of the next four rows are issued before the current four are
-	// processed, so they fly under the compute and the stores (vmcnt is in-order: a load issued after
-	// the stores would also wait for them).  Inactive lanes re-read quad 0 (no divergent load).
-	const uint8_t *lp = qact ? fp : fp - (size_t)q * 16;
-	uint4 nx[4];
-#pragma unroll
-	for (int k = 0; k < 4; ++k) nx[k] = *(const uint4 *)(lp + (size_t)min(rs + k, re) * row_bytes);
-	// per-wave hit lists, sized by the launch (640 bytes per wave: 2.5 KB at 1080p, so that several of these workgroups fit
-	// into the LDS a k_lsd workgroup of the other pipelined step leaves free on its CU)
-	extern __shared__ __attribute__((aligned(16))) uint32_t s_hits[];
-	for (int r = rs; r <= re; r += 4) {
-		uint4 px[4];
-		uint32_t prehits = 0;
-#pragma unroll
-		for (int k = 0; k < 4; ++k) px[k] = nx[k];
-		if (r + 4 <= re) {
-#pragma unroll
-			for (int k = 0; k < 4; ++k) nx[k] = *(const uint4 *)(lp + (size_t)min(r + 4 + k, re) * row_bytes);
-		}
-#pragma unroll
-		for (int k = 0; k < 4; ++k) {
-			const int row = r + k;
-			if (row > re) break;
-			const uint32_t pv[4] = {px[k].x, px[k].y, px[k].z, px[k].w};
-			if (do_ui && row >= r0 && row < r1 && qact) {
-				uint4 o;
-				uint32_t ov[4];
-#pragma unroll
-				for (int c = 0; c < 4; ++c) {
-					const uint32_t p = pv[c], bb = p & 255u, gg = (p >> 8) & 255u, rr8 = (p >> 16) & 255u;
-					if (GRAY) ov[c] = luma8(rr8, gg, bb) * 0x00010101u | 0xFF000000u;   // Bgra::to_luma -> (l,l,l,255)
-					else ov[c] = rr8 | (gg << 8) | (bb << 16) | 0xFF000000u;           // (r,g,b,255)
-				}
-				o.x = ov[0]; o.y = ov[1]; o.z = ov[2]; o.w = ov[3];
-				*(uint4 *)(uip + (size_t)row * g.ui_pitch) = o;
-			}
-			if (do_mask) {
-				// branch-free integer pre-filter; hits of the four rows are collected (bit 4k+c)
-				uint32_t pre = 0;
-#pragma unroll
-				for (int c = 0; c < 4; ++c) pre |= marker_prefilter(pv[c]) ? (1u << c) : 0u;
-				prehits |= (pre & vmask) << (4 * k);
-			}
-		}
-		// ---- exact f32 HSV test for the pre-filter hits of this wave, one hit per lane ----
-		// A marker line crosses most rows of a band but only a few pixels of each, so testing hits where
-		// they sit would run the (long, divergent) exact test several times per row for two or three
-		// active lanes.  Instead the hit pixels of the whole wave and of all four rows are compacted into
-		// a 64-entry LDS list, every lane tests one of them, and the verdicts are scattered back with
-		// LDS atomic ORs.  (This path used to be 40 % of the kernel's time.)
-		if (do_mask && __any(prehits != 0u)) {
-			uint32_t *hpx = s_hits + wave * 160u;
-			uint32_t *hres = hpx + 64;
-			unsigned short *hid = (unsigned short *)(hres + 64);
-			const uint32_t cnt = (uint32_t)__popc(prehits);
-			uint32_t incl = cnt;
-			for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(incl, o); if (lane >= (uint32_t)o) incl += t; }
-			const uint32_t total = __shfl(incl, 63);
-			const uint32_t off = incl - cnt;
-			hres[lane] = 0u;
-			for (uint32_t base = 0; base < total; base += 64u) {
-				uint32_t o = off - base;                           // may wrap: compared unsigned below
-#pragma unroll
-				for (int k = 0; k < 4; ++k) {
-					const uint32_t pk[4] = {px[k].x, px[k].y, px[k].z, px[k].w};
-#pragma unroll
-					for (int c = 0; c < 4; ++c)
-						if ((prehits >> (4 * k + c)) & 1u) {
-							if (o < 64u) { hpx[o] = pk[c]; hid[o] = (unsigned short)((lane << 4) | (uint32_t)(4 * k + c)); }
-							++o;
-						}
-				}
-				__builtin_amdgcn_wave_barrier();
-				const uint32_t e = base + lane;
-				if (e < total) {
-					const uint32_t p = hpx[lane];
-					if (marker_exact((p >> 16) & 255u, (p >> 8) & 255u, p & 255u)) {
-						const uint32_t id = hid[lane];
-						atomicOr(&hres[id >> 4], 1u << (id & 15u));
-					}
-				}
-				__builtin_amdgcn_wave_barrier();
-			}
-			const uint32_t res = hres[lane];                       // bit 4k+c: pixel c of row r+k is a marker colour
-			if (res) {
-				const int sh = r - (r0 - 1);
-#pragma unroll
-				for (int c = 0; c < 4; ++c) {
-					uint32_t y = (res >> c) & 0x1111u;                 // rows k = 0..3 at bits 0,4,8,12
-					y = (y | (y >> 3) | (y >> 6) | (y >> 9)) & 0xFu;   // -> bits 0..3
-					P[c] |= (uint64_t)y << sh;
-				}
-			}
-		}
-	}
-	if (!do_mask) return;
-
-	// ---- dilation on the column masks ----
-	__shared__ uint64_t s_edge_first[16], s_edge_last[16];
-	if (lane == 0) s_edge_first[wave] = P[0];
-	if (lane == 63) s_edge_last[wave] = P[3];
-	__syncthreads();
-	uint64_t left = __shfl_up(P[3], 1), right = __shfl_down(P[0], 1);
-	if (lane == 0) left = wave > 0 ? s_edge_last[wave - 1] : 0ull;
-	if (lane == 63) right = wave + 1 < nwave ? s_edge_first[wave + 1] : 0ull;
-	const int nrows = r1 - r0;
-	const uint64_t rowmask = ((nrows >= 63 ? ~0ull : ((1ull << nrows) - 1ull)) << 1);   // bits 1..nrows
-	uint64_t D[4];
-#define SMH_VERT(p) ((p) | ((p) << 1) | ((p) >> 1))
-	D[0] = SMH_VERT(P[0]) | left | P[1];
-	D[1] = SMH_VERT(P[1]) | P[0] | P[2];
-	D[2] = SMH_VERT(P[2]) | P[1] | P[3];
-	D[3] = SMH_VERT(P[3]) | P[2] | right;
-#undef SMH_VERT
-#pragma unroll
-	for (int c = 0; c < 4; ++c) D[c] = ((vmask >> c) & 1u) ? (D[c] & rowmask) : 0ull;
-
-	// ---- outputs: bit-packed rows, and with MAP_BYTES (the per-call path, which hands the mask straight to the host) the u8 mask
-	// rows; a batch run leaves those to k_mask_expand (smh_misc.hip) ----
-	const bool do_bytes = (flags & MAP_BYTES) != 0;            // (uniform: a kernel argument)
-	const uint32_t quads_padded = (g.m_quads + 15u) & ~15u;
-	const uint64_t any = D[0] | D[1] | D[2] | D[3];
-	const uint64_t lanes_set = __ballot(any != 0ull);
-	// the tile-major mask and its occupancy bytes (TILES: bands of whole tile rows, launch_map_pass; a launch without them runs the
-	// instantiation that has no trace of this)
-	uint32_t occ7 = 0;
-	if constexpr (TILES) {
-		const uint32_t ntr = ((uint32_t)nrows + 7u) >> 3, op = occ_pitch(g);
-		uint8_t *occp = b.occ + (size_t)f * occ_stride(g) + (size_t)((uint32_t)r0 >> 3) * op + wave;
-		if (lanes_set) occ7 = tile_occupancy(any >> 1, lane, ntr, occp, op);
-		else if (lane < ntr) occp[(size_t)lane * op] = 0;
-		if (blockIdx.x == 0 && q == 0) b.aux[f].tiles = 1u;           // (k_button cleared it: this frame's tile-major mask is being written)
-	}
-	if (q < quads_padded) {
-		uint8_t *mp = b.mask + (size_t)f * g.mask_stride + (size_t)q * 4;
-		uint32_t *bp = b.bits + (size_t)f * g.bits_stride_w + (q >> 3);
-		uint32_t *tp = nullptr;
-		if constexpr (TILES) tp = b.tiled + (size_t)f * tiled_stride_w(g) + ((size_t)((uint32_t)r0 >> 3) * g.bits_pitch_w + (q >> 3)) * 8u;
-		for (int row = r0; row < r1; ++row) {
-			const int bit = row - r0 + 1;
-			const uint32_t nib = (uint32_t)((D[0] >> bit) & 1ull) | ((uint32_t)((D[1] >> bit) & 1ull) << 1) |
-			                     ((uint32_t)((D[2] >> bit) & 1ull) << 2) | ((uint32_t)((D[3] >> bit) & 1ull) << 3);
-			if (do_bytes) *(uint32_t *)(mp + (size_t)row * g.mask_pitch) = ((nib * 0x00204081u) & 0x01010101u) * 0xFFu;
-			// gather 8 lanes' nibbles into one dword of the bit-packed row (lane l supplies bits 4(l%8)..)
-			uint32_t v = nib;
-			v |= __shfl_down(v, 1) << 4;
-			v |= __shfl_down(v, 2) << 8;
-			v |= __shfl_down(v, 4) << 16;
-			if ((lane & 7u) == 0) bp[(size_t)row * g.bits_pitch_w] = v;
-			if constexpr (TILES) {
-				const uint32_t i = (uint32_t)(row - r0);
-				if ((occ7 >> (i >> 3)) & 1u) tp[(size_t)(i >> 3) * g.bits_pitch_w * 8u + (i & 7u)] = v;    // (occ7 is 0 outside the lanes 8 j)
-			}
-		}
-	}
-	// ---- bounding box + population count of the set bits (drives the LDS window of k_lsd) ----
-	if (lanes_set) {
-		const uint64_t rows_set = wave_or64(any);
-		const uint32_t cnt = wave_sum32(__popcll(D[0]) + __popcll(D[1]) + __popcll(D[2]) + __popcll(D[3]));
-		if (lane == 0) {
-			FrameAux *a = &b.aux[f];
-			atomicMin(&a->y_min, (uint32_t)(r0 - 1 + __builtin_ctzll(rows_set)));
-			atomicMax(&a->y_max, (uint32_t)(r0 - 1 + 63 - __builtin_clzll(rows_set)));
-			atomicMin(&a->w_min, (wave * 64u + (uint32_t)__builtin_ctzll(lanes_set)) >> 3);
-			atomicMax(&a->w_max, (wave * 64u + 63u - (uint32_t)__builtin_clzll(lanes_set)) >> 3);
-			atomicAdd(&a->n_mask_px, cnt);
-		}
-	}
+	constexpr int GRAYF = GRAY ? 1 : 0;
+#include "smh_map_pass.inc"
+}
+// the grey pass of a batch whose ui_map is a luma plane (b.ui = the plane)
+template <bool TILES>
+__global__ void __launch_bounds__(1024) k_map_pass_luma(Geom g, Buffers b, uint32_t flags, uint32_t RB) {
+	constexpr int GRAYF = 2;
+#include "smh_map_pass.inc"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -536,7 +361,11 @@ typedef const MapKernelArgs *MapKernelArgsPtr;                                  
 // TILES: this launch also writes the mask tile-major with occupancy bytes (bands of whole tile rows; launch_map_brq_pass).  A
 // launch that does not runs the instantiation without a trace of it: the same code as before round 6 (measured: the extra
 // epilogue code alone cost the 1440p pipeline 2.4 % and the three-set form 6 %, whether or not it was executed).
-template <bool GRAY, int SETS, bool TILES>
+// GRAY: 0 = colour, 1 = grey as (l,l,l,255), 2 = grey as a luma plane (k_map_brq_pass_luma): ka->b.ui is the plane, one byte per
+// pixel, its row pitch ui_pitch / 4 and its frame stride ui_stride / 4 -- the same quads, the padded ones left of m_xoff included, one
+// dword per quad and row instead of sixteen bytes.  A compile-time form: the colour and the (l,l,l,255) instantiations are the code
+// they were before the plane existed, to the instruction.
+template <int GRAY, int SETS, bool TILES>
 __device__ SMH_MAP_ITEM_INLINE void map_brq_item(MapKernelArgsPtr ka, uint32_t f, uint32_t band0) {
 	constexpr int GR = 4;                                       // rows per group (the hand-placed waits count four loads per set)
 	const Geom g = ka->g;
@@ -584,7 +413,7 @@ __device__ SMH_MAP_ITEM_INLINE void map_brq_item(MapKernelArgsPtr ka, uint32_t f
 	const uint8_t *fbase = b.frames + (size_t)f * g.frame_bytes + ((size_t)g.ry * g.W + g.m_ax) * 4;
 	const uint32_t loff = qact ? q * 16u : 0u;
 	const uint8_t *fp = fbase + (size_t)q * 16;                  // (patch loop below)
-	uint8_t *uibase = b.ui + (size_t)f * g.ui_stride;
+	uint8_t *uibase = b.ui + (size_t)f * (GRAY == 2 ? g.ui_stride >> 2 : g.ui_stride);
 	uint8_t *op = b.ocr + (size_t)f * g.ocr_stride;
 	uint8_t *sp = b.scales + (size_t)f * g.ocr_stride;
 	const uint32_t qoff = (uint32_t)(in_q ? qq : 0) * 4u;
@@ -667,7 +496,10 @@ __device__ SMH_MAP_ITEM_INLINE void map_brq_item(MapKernelArgsPtr ka, uint32_t f
 #pragma unroll
 					for (int c = 0; c < 4; ++c) lum[c] = luma_bgra(pv[c]);
 				}
-				if (do_ui && qact) {
+				if constexpr (GRAY == 2) {
+					// Bgra::to_luma, the byte alone: (l,l,l,255) is k_ui_expand's when somebody reads the slab (smh_misc.hip)
+					if (do_ui && qact) SMH_ST32(loff >> 2, lum[0] | (lum[1] << 8) | (lum[2] << 16) | (lum[3] << 24), uibase + (size_t)row * (g.ui_pitch >> 2));
+				} else if (do_ui && qact) {
 					u32x4 o;
 					uint32_t ov[4];
 #pragma unroll
@@ -952,7 +784,7 @@ __global__ void __launch_bounds__(1024) k_map_brq_pass(Geom g, Buffers b, uint32
 	if (LOOP) {
 		for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {
 			const uint32_t f = item / nbands, band = item - f * nbands;
-			map_brq_item<GRAY, SETS, TILES>(ka, f, band);
+			map_brq_item<GRAY ? 1 : 0, SETS, TILES>(ka, f, band);
 			__syncthreads();                                   // the next item reuses the LDS exchange arrays
 		}
 	} else {
@@ -968,15 +800,41 @@ __global__ void __launch_bounds__(1024) k_map_brq_pass(Geom g, Buffers b, uint32
 			const uint32_t id = blockIdx.y * gridDim.x + blockIdx.x;
 			band = id / gridDim.y; f = id - band * gridDim.y;
 		}
-		map_brq_item<GRAY, SETS, TILES>(ka, f, band);
+		map_brq_item<GRAY ? 1 : 0, SETS, TILES>(ka, f, band);
+	}
+}
+
+// The grey pass of a batch whose ui_map is a luma plane (map_brq_item<2>): k_map_brq_pass as it stands above, under a name of its
+// own -- the eight instantiations of k_map_brq_pass stay the eight they were.
+template <bool LOOP, int SETS, bool TILES>
+__global__ void __launch_bounds__(1024) k_map_brq_pass_luma(Geom g, Buffers b, uint32_t flags, uint32_t qflags, uint32_t RB, uint32_t fixed_start_y, int use_anchor_start,
+                                                            uint32_t nbands, uint32_t items) {
+#ifdef SMH_MAP_FAT
+	asm volatile("; register footprint experiment" ::: SMH_MAP_FAT);
+#endif
+	MapKernelArgsPtr ka = (MapKernelArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+	if (flags & MAP_PRIO) __builtin_amdgcn_s_setprio(3);
+	if (LOOP) {
+		for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {
+			const uint32_t f = item / nbands, band = item - f * nbands;
+			map_brq_item<2, SETS, TILES>(ka, f, band);
+			__syncthreads();
+		}
+	} else {
+		uint32_t f = blockIdx.y, band = blockIdx.x;
+		if (flags & MAP_BAND_MAJOR) {
+			const uint32_t id = blockIdx.y * gridDim.x + blockIdx.x;
+			band = id / gridDim.y; f = id - band * gridDim.y;
+		}
+		map_brq_item<2, SETS, TILES>(ka, f, band);
 	}
 }
 
 // ------------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------------
-hipError_t launch_button(const Geom &g, const Buffers &b, uint32_t n, int force_open, hipStream_t s) {
-	hipLaunchKernelGGL(k_button, dim3(n), dim3(256), 0, s, g, b, force_open);
+hipError_t launch_button(const Geom &g, const Buffers &b, uint32_t n, int force_open, hipStream_t s, uint8_t *ui_form, uint32_t ui_luma) {
+	hipLaunchKernelGGL(k_button, dim3(n), dim3(256), 0, s, g, b, force_open, ui_form, ui_luma);
 	return hipGetLastError();
 }
 
@@ -994,7 +852,11 @@ hipError_t launch_map_pass(const Geom &g, const Buffers &b, uint32_t n, uint32_t
 	const dim3 grid((g.rh + RB - 1) / RB, n);
 	const unsigned lds = (g.m_block / 64u) * 640u;             // 64 x (pixel, verdict, id) per wave
 	const bool tiles = tiles_wanted && b.tiled != nullptr && (RB & 7u) == 0u;
-	if (tiles) {
+	if (grayscale == 2) {                                      // the luma plane: b.ui is the plane (smh_kernels.h)
+		if (flags & MAP_BYTES) return hipErrorInvalidValue;       // (the per-call path's images go straight to the host: RGBA)
+		if (tiles) hipLaunchKernelGGL((k_map_pass_luma<true>), grid, dim3(g.m_block), lds, s, g, b, flags, RB);
+		else hipLaunchKernelGGL((k_map_pass_luma<false>), grid, dim3(g.m_block), lds, s, g, b, flags, RB);
+	} else if (tiles) {
 		if (grayscale) hipLaunchKernelGGL((k_map_pass<true, true>), grid, dim3(g.m_block), lds, s, g, b, flags, RB);
 		else hipLaunchKernelGGL((k_map_pass<false, true>), grid, dim3(g.m_block), lds, s, g, b, flags, RB);
 	} else {
@@ -1031,7 +893,9 @@ hipError_t launch_map_brq_pass(const Geom &g, const Buffers &b, uint32_t n, uint
 		if (dev >= 64 || !((attr_devices.load(std::memory_order_acquire) >> dev) & 1ull)) {
 			const void *fns[] = {(const void *)k_map_brq_pass<true, true, 2, false>, (const void *)k_map_brq_pass<false, true, 2, false>, (const void *)k_map_brq_pass<true, false, 2, false>,
 			                     (const void *)k_map_brq_pass<false, false, 2, false>, (const void *)k_map_brq_pass<true, false, 2, true>, (const void *)k_map_brq_pass<false, false, 2, true>,
-			                     (const void *)k_map_brq_pass<true, false, 3, false>, (const void *)k_map_brq_pass<false, false, 3, false>};
+			                     (const void *)k_map_brq_pass<true, false, 3, false>, (const void *)k_map_brq_pass<false, false, 3, false>,
+			                     (const void *)k_map_brq_pass_luma<true, 2, false>, (const void *)k_map_brq_pass_luma<false, 2, false>, (const void *)k_map_brq_pass_luma<false, 2, true>,
+			                     (const void *)k_map_brq_pass_luma<false, 3, false>};
 			for (const void *fn : fns) if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
 			if (e != hipSuccess) return e;
 			if (dev < 64) attr_devices.fetch_or(1ull << dev, std::memory_order_release);
@@ -1051,7 +915,14 @@ hipError_t launch_map_brq_pass(const Geom &g, const Buffers &b, uint32_t n, uint
 	const bool tiles = !no_tiles && (RB & 7u) == 0u && !(cap && cap < items) && !deep;
 #define SMH_LAUNCH_MAPQ(GRAYV, LOOPV, SETSV, TILESV, GRID) \
 	hipLaunchKernelGGL((k_map_brq_pass<GRAYV, LOOPV, SETSV, TILESV>), GRID, dim3(g.m_block), lds, s, g, b, flags, qflags, RB, fixed_start_y, use_anchor_start, nbands, items)
-	if (cap && cap < items) {
+#define SMH_LAUNCH_MAPQ_LUMA(LOOPV, SETSV, TILESV, GRID) \
+	hipLaunchKernelGGL((k_map_brq_pass_luma<LOOPV, SETSV, TILESV>), GRID, dim3(g.m_block), lds, s, g, b, flags, qflags, RB, fixed_start_y, use_anchor_start, nbands, items)
+	if (grayscale == 2) {                                    // the luma plane: b.ui is the plane (smh_kernels.h)
+		if (cap && cap < items) SMH_LAUNCH_MAPQ_LUMA(true, 2, false, dim3(cap));
+		else if (deep) SMH_LAUNCH_MAPQ_LUMA(false, 3, false, dim3(nbands, n));
+		else if (tiles) SMH_LAUNCH_MAPQ_LUMA(false, 2, true, dim3(nbands, n));
+		else SMH_LAUNCH_MAPQ_LUMA(false, 2, false, dim3(nbands, n));
+	} else if (cap && cap < items) {
 		if (grayscale) SMH_LAUNCH_MAPQ(true, true, 2, false, dim3(cap)); else SMH_LAUNCH_MAPQ(false, true, 2, false, dim3(cap));
 	} else if (deep) {
 		if (grayscale) SMH_LAUNCH_MAPQ(true, false, 3, false, dim3(nbands, n)); else SMH_LAUNCH_MAPQ(false, false, 3, false, dim3(nbands, n));
@@ -1060,6 +931,7 @@ hipError_t launch_map_brq_pass(const Geom &g, const Buffers &b, uint32_t n, uint
 	} else {
 		if (grayscale) SMH_LAUNCH_MAPQ(true, false, 2, false, dim3(nbands, n)); else SMH_LAUNCH_MAPQ(false, false, 2, false, dim3(nbands, n));
 	}
+#undef SMH_LAUNCH_MAPQ_LUMA
 #undef SMH_LAUNCH_MAPQ
 	return hipGetLastError();
 }

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Static check of k_map_brq_pass's hand-placed waits (squad-mortar-helper_amd/csrc/smh_stream.hip).
+"""Static check of the hand-placed waits of k_map_brq_pass and k_map_brq_pass_luma (squad-mortar-helper_amd/csrc/smh_stream.hip).
 
 The streaming loop issues its pixel loads through inline asm (SMH_LD128), which the compiler does not track: it will not
 wait for them, and it is free to copy or spill their destination registers like any other value.  A copy made while the
@@ -141,29 +141,41 @@ def main():
         if not asm:
             raise RuntimeError("--save-temps left no device assembly for %s in %s" % (arch, sorted(os.listdir(tmp))))
         text = open(os.path.join(tmp, asm[0])).read().split("\n")
-    errors, found = [], 0
-    i = 0
-    while i < len(text):
-        m = re.match(r"(_ZN3smh14k_map_brq_passILb[01]ELb[01]E\w*):", text[i])
-        if m:
-            j = next(k for k in range(i, len(text)) if "s_endpgm" in text[k])
-            found += 1
-            errors += check_kernel(m.group(1)[:58], text[i:j + 1])
-            i = j
-        i += 1
+    # the eight instantiations of k_map_brq_pass, and the four of k_map_brq_pass_luma (the grey pass that writes the ui_map as a luma
+    # plane: the same item under a name of its own, one per launch form) -- each family counted and reported on its own line
+    errors = []
+    families = (("k_map_brq_pass", r"_ZN3smh14k_map_brq_passILb[01]ELb[01]E", r"ILb[01]ELb1ELi\d+ELb[01]EEEv", 8,
+                 "eight instantiations of k_map_brq_pass (GRAY x {two sets, two sets + tile-major mask, two sets + loop, three sets})"),
+                ("k_map_brq_pass_luma", r"_ZN3smh19k_map_brq_pass_lumaILb[01]E", r"_lumaILb1ELi\d+ELb[01]EEEv", 4,
+                 "four instantiations of k_map_brq_pass_luma (two sets, two sets + tile-major mask, two sets + loop, three sets)"))
     meta = "\n".join(text)
-    for km in re.finditer(r"\.name:\s+(_ZN3smh14k_map_brq_pass\w+)\s*\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s*(\d+)", meta):
-        loop = re.search(r"ILb[01]ELb1ELi\d+ELb[01]EEEv", km.group(1)) is not None   # <GRAY, LOOP = true, SETS>: the grid-stride variant
-        if int(km.group(2)) > (128 if loop else 0):
-            errors.append("%s uses %s bytes of scratch (allowed: %s)" % (km.group(1)[:58], km.group(2), "the prologue / epilogue spills of the grid-stride loop's state, <= 128"
-                          if loop else "none: the variant without the loop is the one whose HBM traffic is profiled"))
-    if found == 0:
-        raise RuntimeError("no k_map_brq_pass instantiation in the device assembly")
-    if found != 8:
-        errors.append("expected eight instantiations of k_map_brq_pass (GRAY x {two sets, two sets + tile-major mask, two sets + loop, three sets}), found %d" % found)
+    reports = []
+    for fam, label_re, loop_re, want, what in families:
+        ferrors, found = [], 0
+        i = 0
+        while i < len(text):
+            m = re.match(r"(%s\w*):" % label_re, text[i])
+            if m:
+                j = next(k for k in range(i, len(text)) if "s_endpgm" in text[k])
+                found += 1
+                ferrors += check_kernel(m.group(1)[:58], text[i:j + 1])
+                i = j
+            i += 1
+        for km in re.finditer(r"\.name:\s+(%s\w+)\s*\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s*(\d+)" % label_re, meta):
+            loop = re.search(loop_re, km.group(1)) is not None   # LOOP = true: the grid-stride variant
+            if int(km.group(2)) > (128 if loop else 0):
+                ferrors.append("%s uses %s bytes of scratch (allowed: %s)" % (km.group(1)[:58], km.group(2), "the prologue / epilogue spills of the grid-stride loop's state, <= 128"
+                               if loop else "none: the variant without the loop is the one whose HBM traffic is profiled"))
+        if found == 0:
+            raise RuntimeError("no %s instantiation in the device assembly" % fam)
+        if found != want:
+            ferrors.append("expected %s, found %d" % (what, found))
+        errors += ferrors
+        reports.append("%s: %d instantiations checked, %d problems" % (fam, found, len(ferrors)))
     for e in errors:
         print("FAIL:", e)
-    print("k_map_brq_pass: %d instantiations checked, %d problems" % (found, len(errors)))
+    for r in reports:
+        print(r)
     return 1 if errors else 0
 
 
