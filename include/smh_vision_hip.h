@@ -409,8 +409,8 @@ SMHV_API int smhv_ingest_create(smhv_ctx *ctx, uint32_t frame_w, uint32_t frame_
 /* The same with flags.  SMHV_INGEST_ROI_UPLOAD: the CRC-32 of every committed frame is computed on the HOST (worker threads of the
  * queue, carry-less-multiply folding: the whole frame, as the reference hashes it) and only what the pipeline reads -- the map
  * ROI's rows and the button's rows, 39 % of a 1080p frame -- travels over PCIe, and nothing at all for a duplicate.  The slab
- * frames then hold exactly those two rectangles (zero elsewhere), which is all smhv_batch_run / the pipelines read.  BGRA8
- * commits only. */
+ * frames then hold exactly those two rectangles (zero elsewhere), which is all smhv_batch_run / the pipelines read.  BGRA8,
+ * NV12 and I420 commits only (for the two video layouts see SMHV_PIXELS_NV12 below: the CRC is of the committed YUV bytes). */
 #define SMHV_INGEST_ROI_UPLOAD 1u
 #define SMHV_INGEST_WORKERS(n) (((n) & 0xFFu) << 8)   /* diagnostic, with SMHV_INGEST_ROI_UPLOAD: hashing threads (0 = the library's choice: one per staging slot, at most half the cores the process may use -- the cgroup CPU quota counts -- and at least two) */
 #define SMHV_INGEST_NO_AFFINITY 2u   /* the hashing threads are left to the scheduler (default: on a multi-socket host they run on the CPUs next to the GPU) */
@@ -441,8 +441,60 @@ SMHV_API int smhv_ingest_push(smhv_ingest *q, const uint8_t *bgra);
 #define SMHV_PIXELS_RGB8    2u
 #define SMHV_PIXELS_LUMA8   3u
 #define SMHV_PIXELS_LUMA_A8 4u
+/* Frames that come out of a VIDEO decoder: 8-bit 4:2:0 planes, 1.5 bytes per pixel.  For a frame of w x h, cw = (w + 1) / 2 and
+ * ch = (h + 1) / 2 (odd sizes are legal).  Tight layouts, as the staging buffer holds them:
+ *   SMHV_PIXELS_NV12: the Y plane (w x h), then one plane of interleaved U, V pairs (cw pairs x ch rows).
+ *   SMHV_PIXELS_I420: Y, then U (cw x ch), then V (cw x ch).
+ * The colour description rides in the upper bits of the same word -- SMHV_PIXELS_YUV(layout, matrix, range, chroma):
+ *   matrix 0 = BT.709, 1 = BT.601;  range 0 = limited, 1 = full;  chroma 0 = nearest, 1 = bilinear.  Any other bit: SMHV_E_INVALID.
+ * The arithmetic, in int32 with >> the arithmetic shift:  c = cy * (Y - yoff), d = U' - 128, e = V' - 128,
+ *   R = clip8((c + rv * e + 128) >> 8), G = clip8((c - gu * d - gv * e + 128) >> 8), B = clip8((c + bu * d + 128) >> 8), A = 255,
+ * output bytes B, G, R, A, with (the real matrices times 256, rounded: within 1 level of the rounded float64 result everywhere)
+ *                    cy  yoff   rv   gu   gv   bu
+ *   709 limited     298   16   459   55  136  541
+ *   601 limited     298   16   409  100  208  516
+ *   709 full        256    0   403   48  120  475
+ *   601 full        256    0   359   88  183  454
+ * Chroma of pixel (x, y):  nearest: U' = U[y >> 1][x >> 1].  Bilinear, centre-sited: cx = x >> 1, cy_ = y >> 1,
+ *   nx = clamp(cx + ((x & 1) ? 1 : -1), 0, cw - 1), ny = clamp(cy_ + ((y & 1) ? 1 : -1), 0, ch - 1),
+ *   U' = (9 U[cy_][cx] + 3 U[cy_][nx] + 3 U[ny][cx] + U[ny][nx] + 8) >> 4.  The same for V.
+ * In the queue the frame is uploaded as it is (1.5 bytes per pixel) and converted on the device.  A plain queue converts in front
+ * of the device CRC, as for the other decoder layouts: its CRC is of the CONVERTED BGRA bytes.  A queue created with
+ * SMHV_INGEST_ROI_UPLOAD hashes on the host what was committed: its CRC is of the SOURCE bytes, the whole tight YUV frame
+ * (smhv_ingest_staging_bytes of them); it uploads the Y rows of the map ROI and of the button with the chroma rows and columns
+ * they need, and converts them into the slab frame.  Both CRCs are functions of the frame, so a repeated capture is a duplicate
+ * either way; they are different numbers.  The layout is kept per staging slot: BGRA and YUV commits may alternate. */
+#define SMHV_PIXELS_NV12    5u
+#define SMHV_PIXELS_I420    6u
+#define SMHV_YUV_BT709 0u
+#define SMHV_YUV_BT601 1u
+#define SMHV_YUV_LIMITED 0u
+#define SMHV_YUV_FULL 1u
+#define SMHV_YUV_NEAREST 0u
+#define SMHV_YUV_BILINEAR 1u
+#define SMHV_PIXELS_YUV(layout, matrix, range, chroma) ((uint32_t)(layout) | ((uint32_t)(matrix) << 8) | ((uint32_t)(range) << 9) | ((uint32_t)(chroma) << 10))
 SMHV_API int smhv_ingest_commit_pixels(smhv_ingest *q, uint32_t layout);
 SMHV_API int smhv_ingest_push_pixels(smhv_ingest *q, const uint8_t *pixels, uint32_t layout);
+/* how many bytes of a staging buffer (from its start) a frame of w x h in `pixels` fills; 0 for an unknown layout or a zero size.
+   Needs no device. */
+SMHV_API uint64_t smhv_ingest_staging_bytes(uint32_t w, uint32_t h, uint32_t pixels);
+/* Decoded surfaces that already sit in device memory -> BGRA8 frames that smhv_batch_run, smhv_pipeline_submit and
+ * smhv_load_frame_device take.  d_src = n frames, frame_stride bytes apart, each with its Y plane at offset 0 (rows y_pitch
+ * apart), its U plane (NV12: the U, V pairs) at u_offset and, for I420, its V plane at v_offset (chroma rows uv_pitch apart);
+ * bases and pitches may have any byte alignment.  layout = NULL, or a zero member, means tight: y_pitch = w, uv_pitch = 2 cw
+ * (NV12) / cw (I420), u_offset = y_pitch * h, v_offset = u_offset + uv_pitch * ch, frame_stride = the end of the last plane.
+ * `pixels` = SMHV_PIXELS_YUV(...).  d_bgra (4-byte aligned) receives n frames of w * h * 4 bytes with tight rows,
+ * out_stride_bytes apart (a multiple of 4; 0 = w * h * 4).  flags: SMHV_YUV_ROI_ONLY writes the map ROI's and the button's
+ * rectangles alone (smhv_map_bounds / smhv_button_bounds; the bytes of the full conversion) and leaves everything else in d_bgra
+ * as it was.  Asynchronous on `stream` (NULL: the context's own).  SMHV_E_INVALID, with nothing enqueued, for a null pointer,
+ * n, w or h = 0, a pitch shorter than its row, planes of a frame that reach beyond frame_stride when n > 1, an out_stride_bytes
+ * shorter than a frame, an unknown layout or colour bit, or an unknown flag. */
+typedef struct {
+	uint64_t y_pitch, uv_pitch, u_offset, v_offset, frame_stride;
+} smhv_yuv_layout;
+#define SMHV_YUV_ROI_ONLY 1u
+SMHV_API int smhv_yuv_to_bgra_device(smhv_ctx *ctx, const void *d_src, const smhv_yuv_layout *layout, uint32_t n, uint32_t w, uint32_t h, uint32_t pixels,
+                                     void *d_bgra, uint64_t out_stride_bytes, uint32_t flags, void *stream);
 /* wait for everything committed (or until the slab is full); *d_frames = slab of *n <= capacity accepted frames, valid
  * until smhv_ingest_reset; *last_crc (optional) = CRC-32 of the last accepted frame.  Frames committed after the slab
  * filled up are not lost: they stay queued in their staging slots (at most `slots` of them -- smhv_ingest_acquire

@@ -130,6 +130,9 @@ SMHV_API int smhv_debug_mask_expand(smhv_batch *b, uint32_t n, void *stream);
  * computes the same), smhv_ingest_commit.  What a Python loop spends per frame on three ctypes calls (~90 us: 11 k frames/s)
  * is the interpreter's, not the queue's. */
 SMHV_API int smhv_debug_ingest_feed(smhv_ingest *q, uint32_t n, uint32_t *counter);
+/* The same with every commit in `pixels` (SMHV_PIXELS_*): the stamp lands in the staging buffer's first three bytes, which for the
+ * video layouts are the Y samples of pixels (0..2, 0) -- outside every region the path reads as well. */
+SMHV_API int smhv_debug_ingest_feed_pixels(smhv_ingest *q, uint32_t n, uint32_t *counter, uint32_t pixels);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@ from ._lib import VisionError, STAGE_ALL, STAGE_EXACT_STATS, STAGE_FIRING, STAGE
 from .vision import DebugView, HipVision, VisionResults, VisionState, button_bounds, map_bounds, parse_ocr_labels  # noqa: F401
 from .batch import FrameBatch, Pipeline, make_anchors, results_to_dicts  # noqa: F401
 from .ingest import IngestQueue, crc32_device  # noqa: F401
+from . import yuv  # noqa: F401
 from .heightmap import Heightmap  # noqa: F401
 from .render import MapViewport, RenderOptions, render_options  # noqa: F401
 from .render import RenderLayers, ctl_marker_prims, ocr_box_prims, prim, scale_bar_prims  # noqa: F401

@@ -165,6 +165,15 @@ class FeedHeader(C.Structure):
                 ("last_crc", C.c_uint32), ("reserved", C.c_uint32), ("bytes_used", C.c_uint64)]
 
 
+PIXELS_NV12, PIXELS_I420 = 5, 6            # SMHV_PIXELS_*: 8-bit 4:2:0 video frames
+YUV_ROI_ONLY = 1                           # smhv_yuv_to_bgra_device flags
+
+
+class YuvLayout(C.Structure):
+    """smhv_yuv_layout: pitches and plane offsets of a decoded surface, in bytes (a zero member: tight)."""
+    _fields_ = [("y_pitch", C.c_uint64), ("uv_pitch", C.c_uint64), ("u_offset", C.c_uint64), ("v_offset", C.c_uint64), ("frame_stride", C.c_uint64)]
+
+
 LOG_FN = C.CFUNCTYPE(None, C.c_int, C.c_char_p)
 
 # name -> (restype, argtypes); every symbol include/smh_vision_hip.h declares
@@ -243,6 +252,7 @@ SIGNATURES = {
     "smhv_debug_map_band_rows": (C.c_int, [C.c_uint32]),
     "smhv_debug_band_rows": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "smhv_debug_ingest_feed": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "smhv_debug_ingest_feed_pixels": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]),
     "smhv_debug_crc32_host_level": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint32)]),
     "smhv_ingest_destroy": (None, [C.c_void_p]),
     "smhv_ingest_local_cpus": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
@@ -252,6 +262,9 @@ SIGNATURES = {
     "smhv_ingest_push": (C.c_int, [C.c_void_p, C.c_void_p]),
     "smhv_ingest_commit_pixels": (C.c_int, [C.c_void_p, C.c_uint32]),
     "smhv_ingest_push_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "smhv_ingest_staging_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "smhv_yuv_to_bgra_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(YuvLayout), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                          C.c_uint32, C.c_void_p]),
     "smhv_ingest_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "smhv_ingest_reset": (C.c_int, [C.c_void_p]),
     "smhv_ingest_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -546,6 +546,29 @@ hipError_t set_ray_table(const float *dx, const float *dy);
 #define SMH_CRC_BS 1024
 // decoder layouts -> BGRA8 (n_px pixels; layout = SMHV_PIXELS_*)
 hipError_t launch_to_bgra(const void *d_src, void *d_bgra, uint64_t n_px, uint32_t layout, hipStream_t s);
+// ---- 4:2:0 video frames -> BGRA8 (smh_yuv.hip; smhv_yuv_to_bgra_device and the ingest queue) ------------------------------
+#define SMH_YUV_NV12 5                       // == SMHV_PIXELS_NV12 / _I420
+#define SMH_YUV_I420 6
+#define SMH_YUV_BAND_PAIRS 4u                // row pairs of a workgroup's band
+struct YuvCoef { int cy, yoff, rv, gu, gv, bu; };   // a row of the header's table
+// A rectangle of the frame to convert and where its samples lie, as byte offsets from the frame's source base: the Y sample of
+// frame pixel (y_x0, y_y0) at y_off, rows y_pitch apart; the chroma sample (c_x0, c_y0) at u_off / v_off (NV12: the pair at
+// u_off), rows uv_pitch apart.  y_x0 <= x0 & ~3 and c_x0 <= (x0 & ~3) / 2; for the bilinear form the chroma rows and columns
+// reach one sample beyond what the rectangle's pixels lie in (clamped at the frame's edge).
+struct YuvRect {
+	uint32_t x0, y0, w, h;
+	uint64_t y_off, u_off, v_off;
+	uint32_t y_pitch, uv_pitch, y_x0, y_y0, c_x0, c_y0;
+};
+struct YuvRun {
+	const uint8_t *src; uint8_t *dst;        // first frame; frames src_stride / dst_stride bytes apart, output rows W * 4 bytes
+	uint64_t src_stride, dst_stride;
+	uint32_t W, H, n;
+	uint32_t bands0, bands_total;            // (filled in by the launcher)
+	YuvCoef k;
+	YuvRect r[2];
+};
+hipError_t launch_yuv_to_bgra(YuvRun run, uint32_t n_rects, uint32_t layout, uint32_t bilinear, hipStream_t s);
 hipError_t launch_unpack_rows(const void *d_pack, void *d_frame, uint32_t pitch_px, uint32_t roi_x, uint32_t roi_y, uint32_t roi_w, uint32_t roi_h, uint32_t btn_x,
                               uint32_t btn_y, uint32_t btn_w, uint32_t btn_h, hipStream_t s);
 hipError_t launch_crc32(const void *d_msg, uint64_t n_dwords, uint32_t wgs, uint32_t rounds, uint32_t x_skip, const uint32_t *d_x_local,

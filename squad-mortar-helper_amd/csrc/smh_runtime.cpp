@@ -2499,6 +2499,8 @@ extern "C" SMHV_API int smhv_debug_marker_table(smhv_ctx *c, uint32_t *bits) {
 // compute of earlier frames), its CRC-32 is computed on the device (k_crc32), and frames whose CRC
 // differs from the last accepted one are appended to a device-resident slab that smhv_batch_run takes.
 // ------------------------------------------------------------------------------------------------
+#include "smh_yuv.inc"
+
 struct smhv_ingest {
 	smhv_ctx *ctx = nullptr;
 	uint32_t W = 0, H = 0, slots = 0, capacity = 0;
@@ -2524,6 +2526,10 @@ struct smhv_ingest {
 	bool roi = false;
 	Geom g{};
 	size_t roi_row_bytes = 0, btn_row_bytes = 0, pack_bytes = 0;
+	// NV12 / I420 commits (smh_yuv.inc): the layout of every staging slot's frame, and the packed Y and chroma rows of the two rectangles
+	std::vector<uint32_t> slot_pixels;
+	YuvPack yuv_roi{}, yuv_btn{};
+	size_t yuv_pack_bytes = 0;
 	std::vector<uint8_t *> h_pack, d_pack;
 	std::vector<uint32_t> h_crc;
 	std::vector<int> crc_state;                              // 0 idle, 1 queued / being hashed, 2 done  (guarded by mu)
@@ -2622,6 +2628,34 @@ static void ingest_worker(smhv_ingest *q) {
 		// one pass over the frame: a few rows are hashed, then what the pipeline reads of them is copied while it is in the cache
 		const uint8_t *src = q->h_stage[slot];
 		const Geom &g = q->g;
+		YuvDesc yd;
+		if (yuv_decode(q->slot_pixels[slot], &yd)) {                // (written by the producer before the job was queued under mu)
+			// the tight YUV frame, plane by plane: the CRC is of the committed bytes in their order
+			uint8_t *pack = q->h_pack[slot];
+			uint32_t st = 0xFFFFFFFFu;
+			auto plane = [&st](const uint8_t *base, size_t row_bytes, uint32_t rows, auto &&copy_row) {
+				const uint32_t step = (uint32_t)std::max<size_t>(1, 65536 / row_bytes);
+				for (uint32_t r0 = 0; r0 < rows; r0 += step) {
+					const uint32_t r1 = std::min(rows, r0 + step);
+					st = smh::crc32_host_update(st, base + (size_t)r0 * row_bytes, (size_t)(r1 - r0) * row_bytes);
+					for (uint32_t r = r0; r < r1; ++r) copy_row(r, base + (size_t)r * row_bytes);
+				}
+			};
+			const uint32_t cw = (g.W + 1u) / 2u, ch = (g.H + 1u) / 2u, lay = yd.layout;
+			plane(src, g.W, g.H, [&](uint32_t y, const uint8_t *row) { yuv_pack_y_row(q->yuv_roi, pack, y, row); yuv_pack_y_row(q->yuv_btn, pack, y, row); });
+			const uint8_t *chroma = src + (size_t)g.W * g.H;
+			if (lay == SMHV_PIXELS_NV12)
+				plane(chroma, 2u * (size_t)cw, ch, [&](uint32_t r, const uint8_t *row) { yuv_pack_c_row(q->yuv_roi, pack, lay, 0, r, row); yuv_pack_c_row(q->yuv_btn, pack, lay, 0, r, row); });
+			else
+				plane(chroma, cw, 2u * ch, [&](uint32_t r, const uint8_t *row) { yuv_pack_c_row(q->yuv_roi, pack, lay, r / ch, r % ch, row); yuv_pack_c_row(q->yuv_btn, pack, lay, r / ch, r % ch, row); });
+			{
+				std::lock_guard<std::mutex> lk(q->mu);
+				q->h_crc[slot] = ~st;
+				q->crc_state[slot] = 2;
+			}
+			q->cv_done.notify_all();
+			continue;
+		}
 		uint8_t *roi_dst = q->h_pack[slot], *btn_dst = roi_dst + (size_t)g.rh * q->roi_row_bytes;
 		const size_t pitch = (size_t)g.W * 4;
 		uint32_t st = 0xFFFFFFFFu;
@@ -2722,6 +2756,7 @@ extern "C" SMHV_API void smhv_ingest_destroy(smhv_ingest *q) {
 static int ingest_setup(smhv_ingest *q) {
 	HIPCHK(hipStreamCreateWithFlags(&q->s, hipStreamNonBlocking));
 	HIPCHK(hipStreamCreateWithFlags(&q->s_alt, hipStreamNonBlocking));
+	q->slot_pixels.assign(q->slots, SMHV_PIXELS_BGRA8);
 	q->h_stage.assign(q->slots, nullptr); q->d_stage.assign(q->slots, nullptr); q->d_raw.assign(q->slots, nullptr); q->done.assign(q->slots, nullptr);
 	for (uint32_t i = 0; i < q->slots; ++i) {
 		HIPCHK(hipHostMalloc((void **)&q->h_stage[i], q->frame_bytes, hipHostMallocDefault));
@@ -2744,10 +2779,14 @@ static int ingest_setup(smhv_ingest *q) {
 		const uint32_t roi_px = std::min<uint32_t>(g.m_quads * 4u, g.W - g.m_ax);
 		q->roi_row_bytes = (size_t)roi_px * 4; q->btn_row_bytes = (size_t)g.bw * 4;
 		q->pack_bytes = q->roi_row_bytes * g.rh + q->btn_row_bytes * g.bh;
+		yuv_pack_geom(g.W, g.H, g.rx, g.ry, g.rw, g.rh, 0, &q->yuv_roi);
+		yuv_pack_geom(g.W, g.H, g.bx, g.by, g.bw, g.bh, q->yuv_roi.bytes, &q->yuv_btn);
+		q->yuv_pack_bytes = (size_t)(q->yuv_roi.bytes + q->yuv_btn.bytes);
+		const size_t pack_alloc = std::max(q->pack_bytes, q->yuv_pack_bytes);
 		q->h_pack.assign(q->slots, nullptr); q->d_pack.assign(q->slots, nullptr); q->h_crc.assign(q->slots, 0u); q->crc_state.assign(q->slots, 0);
 		for (uint32_t i = 0; i < q->slots; ++i) {
-			HIPCHK(hipHostMalloc((void **)&q->h_pack[i], q->pack_bytes, hipHostMallocDefault));
-			HIPCHK(hipMalloc((void **)&q->d_pack[i], q->pack_bytes));
+			HIPCHK(hipHostMalloc((void **)&q->h_pack[i], pack_alloc, hipHostMallocDefault));
+			HIPCHK(hipMalloc((void **)&q->d_pack[i], pack_alloc));
 		}
 		// (frames outside the copied rectangles are never read by any kernel; zero them once so that the slab is deterministic)
 		HIPCHK(hipMemset(q->d_slab, 0, q->frame_bytes * q->capacity));
@@ -2832,8 +2871,17 @@ static int ingest_resolve_one(smhv_ingest *q) {
 		// (frames are independent appends to the slab: consecutive ones take two streams in turn, so that one frame's 3.3 MB cross PCIe
 		// while the previous frame's are still on their way -- one stream of such copies reaches 25 GB/s of the link's 50)
 		const hipStream_t st = (q->tail & 1ull) ? q->s_alt : q->s;
-		HIPCHK(hipMemcpyAsync(q->d_pack[slot], q->h_pack[slot], q->pack_bytes, hipMemcpyHostToDevice, st));
-		HIPCHK(launch_unpack_rows(q->d_pack[slot], dst, g.W, g.m_ax, g.ry, (uint32_t)(q->roi_row_bytes / 4), g.rh, g.bx, g.by, g.bw, g.bh, st));
+		YuvDesc yd;
+		if (yuv_decode(q->slot_pixels[slot], &yd)) {               // the packed Y and chroma rows become the two rectangles' BGRA in their place
+			HIPCHK(hipMemcpyAsync(q->d_pack[slot], q->h_pack[slot], q->yuv_pack_bytes, hipMemcpyHostToDevice, st));
+			YuvRun run{};
+			run.src = q->d_pack[slot]; run.dst = dst; run.W = g.W; run.H = g.H; run.n = 1; run.k = yuv_coef(yd);
+			run.r[0] = yuv_pack_rect(q->yuv_roi, yd.layout); run.r[1] = yuv_pack_rect(q->yuv_btn, yd.layout);
+			HIPCHK(launch_yuv_to_bgra(run, 2, yd.layout, yd.bilinear, st));
+		} else {
+			HIPCHK(hipMemcpyAsync(q->d_pack[slot], q->h_pack[slot], q->pack_bytes, hipMemcpyHostToDevice, st));
+			HIPCHK(launch_unpack_rows(q->d_pack[slot], dst, g.W, g.m_ax, g.ry, (uint32_t)(q->roi_row_bytes / 4), g.rh, g.bx, g.by, g.bw, g.bh, st));
+		}
 		HIPCHK(hipEventRecord(q->done[slot], st));               // the slot's pack buffers are free again when this has passed
 		{ std::lock_guard<std::mutex> lk(q->mu); q->crc_state[slot] = 0; }
 		q->tail++; q->count++; q->n_new++;
@@ -2885,13 +2933,16 @@ static uint32_t pixel_layout_bytes(uint32_t layout) {
 extern "C" SMHV_API int smhv_ingest_commit_pixels(smhv_ingest *q, uint32_t layout) {
 	if (!q || !q->acquired) return fail(SMHV_E_INVALID, "ingest_commit: nothing acquired");
 	const uint32_t bpp = pixel_layout_bytes(layout);
-	if (!bpp) return fail(SMHV_E_INVALID, "ingest_commit_pixels: unknown pixel layout %u", layout);
+	YuvDesc yd;
+	const bool yuv = !bpp && yuv_decode(layout, &yd);
+	if (!bpp && !yuv) return fail(SMHV_E_INVALID, "ingest_commit_pixels: unknown pixel layout 0x%x", layout);
 	HIPCHK(hipSetDevice(q->ctx->device));
 	const uint32_t slot = (uint32_t)(q->head % q->slots);
 	if (q->roi) {
-		if (layout != SMHV_PIXELS_BGRA8) return fail(SMHV_E_INVALID, "ingest_commit_pixels: a queue created with SMHV_INGEST_ROI_UPLOAD takes BGRA8 frames only");
+		if (layout != SMHV_PIXELS_BGRA8 && !yuv) return fail(SMHV_E_INVALID, "ingest_commit_pixels: a queue created with SMHV_INGEST_ROI_UPLOAD takes BGRA8, NV12 and I420 frames only");
 		{
 			std::lock_guard<std::mutex> lk(q->mu);
+			q->slot_pixels[slot] = layout;
 			q->crc_state[slot] = 1;
 			q->jobs.push_back(slot);
 		}
@@ -2902,6 +2953,13 @@ extern "C" SMHV_API int smhv_ingest_commit_pixels(smhv_ingest *q, uint32_t layou
 	}
 	if (layout == SMHV_PIXELS_BGRA8) {
 		HIPCHK(hipMemcpyAsync(q->d_stage[slot], q->h_stage[slot], q->frame_bytes, hipMemcpyHostToDevice, q->s));
+	} else if (yuv) {                                        // 1.5 bytes per pixel over the link; BGRA in front of the CRC like the other layouts
+		if (!q->d_raw[slot]) HIPCHK(hipMalloc((void **)&q->d_raw[slot], q->frame_bytes));
+		HIPCHK(hipMemcpyAsync(q->d_raw[slot], q->h_stage[slot], yuv_tight_bytes(q->W, q->H), hipMemcpyHostToDevice, q->s));
+		YuvRun run{};
+		run.src = q->d_raw[slot]; run.dst = q->d_stage[slot]; run.W = q->W; run.H = q->H; run.n = 1; run.k = yuv_coef(yd);
+		run.r[0] = yuv_tight_rect(q->W, q->H, yd.layout);
+		HIPCHK(launch_yuv_to_bgra(run, 1, yd.layout, yd.bilinear, q->s));
 	} else {
 		if (!q->d_raw[slot]) HIPCHK(hipMalloc((void **)&q->d_raw[slot], q->frame_bytes));
 		HIPCHK(hipMemcpyAsync(q->d_raw[slot], q->h_stage[slot], q->frame_bytes / 4 * bpp, hipMemcpyHostToDevice, q->s));
@@ -2921,11 +2979,13 @@ extern "C" SMHV_API int smhv_ingest_commit(smhv_ingest *q) { return smhv_ingest_
 extern "C" SMHV_API int smhv_ingest_push_pixels(smhv_ingest *q, const uint8_t *pixels, uint32_t layout) {
 	if (!q || !pixels) return fail(SMHV_E_INVALID, "ingest_push: null argument");
 	const uint32_t bpp = pixel_layout_bytes(layout);
-	if (!bpp) return fail(SMHV_E_INVALID, "ingest_push_pixels: unknown pixel layout %u", layout);
+	YuvDesc yd;
+	if (!bpp && !yuv_decode(layout, &yd)) return fail(SMHV_E_INVALID, "ingest_push_pixels: unknown pixel layout 0x%x", layout);
+	if (q->roi && bpp && layout != SMHV_PIXELS_BGRA8) return fail(SMHV_E_INVALID, "ingest_push_pixels: a queue created with SMHV_INGEST_ROI_UPLOAD takes BGRA8, NV12 and I420 frames only");
 	uint8_t *dst = nullptr;
 	int rc = smhv_ingest_acquire(q, &dst);
 	if (rc) return rc;
-	memcpy(dst, pixels, q->frame_bytes / 4 * bpp);
+	memcpy(dst, pixels, bpp ? q->frame_bytes / 4 * bpp : (size_t)yuv_tight_bytes(q->W, q->H));
 	return smhv_ingest_commit_pixels(q, layout);
 }
 
@@ -2980,7 +3040,9 @@ extern "C" SMHV_API int smhv_debug_mask_expand(smhv_batch *b, uint32_t n, void *
 	return SMHV_OK;
 }
 
-extern "C" SMHV_API int smhv_debug_ingest_feed(smhv_ingest *q, uint32_t n, uint32_t *counter) {
+extern "C" SMHV_API int smhv_debug_ingest_feed(smhv_ingest *q, uint32_t n, uint32_t *counter) { return smhv_debug_ingest_feed_pixels(q, n, counter, SMHV_PIXELS_BGRA8); }
+
+extern "C" SMHV_API int smhv_debug_ingest_feed_pixels(smhv_ingest *q, uint32_t n, uint32_t *counter, uint32_t pixels) {
 	if (!q || !counter) return fail(SMHV_E_INVALID, "ingest_feed: null argument");
 	for (uint32_t i = 0; i < n; ++i) {
 		uint8_t *buf = nullptr;
@@ -2988,7 +3050,7 @@ extern "C" SMHV_API int smhv_debug_ingest_feed(smhv_ingest *q, uint32_t n, uint3
 		if (rc) return rc;
 		const uint32_t c = (*counter)++;
 		buf[0] = (uint8_t)c; buf[1] = (uint8_t)(c >> 8); buf[2] = (uint8_t)(c >> 16); buf[3] = 255;
-		rc = smhv_ingest_commit(q);
+		rc = smhv_ingest_commit_pixels(q, pixels);
 		if (rc) return rc;
 	}
 	return SMHV_OK;

@@ -29,6 +29,16 @@ def crc32_device(vision, device_ptr, nbytes):
 PIXEL_LAYOUTS = {"bgra": (0, 4), "rgba": (1, 4), "rgb": (2, 3), "l": (3, 1), "la": (4, 2)}
 
 
+def _pixel_code(layout, yuv_kw):
+    """The `pixels` word of a layout name: a decoder layout above, or "nv12" / "i420" with yuv.pixels' keywords."""
+    from . import yuv
+    if layout in yuv.LAYOUTS:
+        return yuv.pixels(layout, **yuv_kw)
+    if yuv_kw:
+        raise TypeError("%s apply to \"nv12\" and \"i420\" only" % sorted(yuv_kw))
+    return PIXEL_LAYOUTS[layout][0]
+
+
 class IngestQueue:
     """`slots` pinned staging buffers + one device slab of `capacity` frames of w x h BGRA."""
 
@@ -82,14 +92,17 @@ class IngestQueue:
             a = self._views[p.value] = np.frombuffer(buf, dtype=np.uint8).reshape(self.h, self.w, 4)
         return a
 
-    def commit(self):
-        check(self._lib.smhv_ingest_commit(self._q))
+    def commit(self, layout="bgra", **yuv_kw):
+        """Start upload + CRC of the acquired buffer.  layout "nv12" / "i420" (with matrix=, full_range=, chroma= as yuv.pixels takes
+        them): the buffer's first yuv.staging_bytes(w, h, layout) bytes hold the tight video frame."""
+        check(self._lib.smhv_ingest_commit_pixels(self._q, _pixel_code(layout, yuv_kw)))
 
-    def feed(self, n, counter):
+    def feed(self, n, counter, layout="bgra", **yuv_kw):
         """Benchmark driver (smhv_debug_ingest_feed): a native capture loop -- n x (acquire, stamp a fresh 24-bit counter into pixel
-        (0, 0), commit) without the interpreter between the frames.  -> the counter after the last frame."""
+        (0, 0), commit) without the interpreter between the frames.  -> the counter after the last frame.  layout (and, for
+        "nv12" / "i420", yuv.pixels' keywords): what every commit is committed as."""
         c = C.c_uint32(int(counter) & 0xFFFFFFFF)
-        check(self._lib.smhv_debug_ingest_feed(self._q, int(n), C.byref(c)))
+        check(self._lib.smhv_debug_ingest_feed_pixels(self._q, int(n), C.byref(c), _pixel_code(layout, yuv_kw)))
         return int(c.value)
 
     def push(self, frame):
@@ -99,18 +112,29 @@ class IngestQueue:
             raise ValueError("frame must be (%d, %d, 4) BGRA" % (self.h, self.w))
         check(self._lib.smhv_ingest_push(self._q, a.ctypes.data_as(C.c_void_p)))
 
-    def push_pixels(self, pixels, layout):
+    def push_pixels(self, pixels, layout, **yuv_kw):
         """A decoded image (src/ui/debug.rs:169, `image::load_from_memory(..).into_bgra8()`): uint8[h, w, c] (or [h, w] for
-        "l") in the decoder's layout -- "rgba", "rgb", "l", "la" or "bgra"; it becomes BGRA on the device, before the CRC."""
+        "l") in the decoder's layout -- "rgba", "rgb", "l", "la" or "bgra"; it becomes BGRA on the device, before the CRC.
+        "nv12" / "i420" (with matrix=, full_range=, chroma=): a video decoder's tight 4:2:0 frame as a flat uint8 array of
+        yuv.staging_bytes(w, h, layout) bytes."""
+        from . import yuv
+        if layout in yuv.LAYOUTS:
+            a = np.ascontiguousarray(pixels, dtype=np.uint8).reshape(-1)
+            if a.size != yuv.staging_bytes(self.w, self.h, layout):
+                raise ValueError("a tight %s frame of %d x %d has %d bytes" % (layout, self.w, self.h, yuv.staging_bytes(self.w, self.h, layout)))
+            check(self._lib.smhv_ingest_push_pixels(self._q, a.ctypes.data_as(C.c_void_p), yuv.pixels(layout, **yuv_kw)))
+            return
+        if yuv_kw:
+            raise TypeError("%s apply to \"nv12\" and \"i420\" only" % sorted(yuv_kw))
         code, bpp = PIXEL_LAYOUTS[layout]
         a = np.ascontiguousarray(pixels, dtype=np.uint8)
         if a.size != self.h * self.w * bpp or a.shape[:2] != (self.h, self.w):
             raise ValueError("pixels must be (%d, %d, %d) for layout %r" % (self.h, self.w, bpp, layout))
         check(self._lib.smhv_ingest_push_pixels(self._q, a.ctypes.data_as(C.c_void_p), code))
 
-    def commit_pixels(self, layout):
+    def commit_pixels(self, layout, **yuv_kw):
         """commit() for a staging buffer whose first h * w * bytes-per-pixel bytes hold pixels in a decoder's layout."""
-        check(self._lib.smhv_ingest_commit_pixels(self._q, PIXEL_LAYOUTS[layout][0]))
+        check(self._lib.smhv_ingest_commit_pixels(self._q, _pixel_code(layout, yuv_kw)))
 
     def batch(self):
         """Wait for everything committed: (device pointer of the slab, accepted frames in it, CRC of the last one)."""
