@@ -495,6 +495,54 @@ typedef struct {
 #define SMHV_YUV_ROI_ONLY 1u
 SMHV_API int smhv_yuv_to_bgra_device(smhv_ctx *ctx, const void *d_src, const smhv_yuv_layout *layout, uint32_t n, uint32_t w, uint32_t h, uint32_t pixels,
                                      void *d_bgra, uint64_t out_stride_bytes, uint32_t flags, void *stream);
+/* ---- video frames OUT: RGBA8 / BGRA8 images -> NV12 / I420, what a hardware encoder takes ----------------------------------------
+ * The output word is SMHV_PIXELS_YUV(layout, matrix, range, 0): the layouts, the matrix bit and the range bit of the inbound
+ * direction.  The chroma bit must be 0 on output -- chroma is always the centre-sited 2 x 2 box -- and a set chroma bit, like
+ * any other bit, is SMHV_E_INVALID.  For a source of w x h, cw = (w + 1) / 2 and ch = (h + 1) / 2 (odd sizes are legal).
+ * The arithmetic, in int32 with >> the arithmetic shift; alpha is ignored:
+ *   Y[y][x]   = clip8(((yr * R + yg * G + yb * B + 32768) >> 16) + yoff)
+ *   Rs, Gs, Bs = the sums over the four pixels (min(2 cx + i, w - 1), min(2 cy + j, h - 1)), i, j in {0, 1}
+ *                (at an odd edge a pixel counts twice: always four terms)
+ *   U[cy][cx] = clip8(((ur * Rs + ug * Gs + ub * Bs + 131072) >> 18) + 128)
+ *   V[cy][cx] = clip8(((vr * Rs + vg * Gs + vb * Bs + 131072) >> 18) + 128)
+ * with (the real matrices times 65536, rounded; the green one of each row chosen so that yr + yg + yb is exactly 56284 (limited)
+ * or 65536 (full) and ur + ug + ub = vr + vg + vb = 0)
+ *                    yr     yg    yb  yoff     ur      ug     ub     vr      vg     vb
+ *   709 limited   11966  40254  4064   16   -6596  -22188  28784  28784  -26145  -2639
+ *   709 full      13933  46871  4732    0   -7509  -25259  32768  32768  -29763  -3005
+ *   601 limited   16829  33039  6416   16   -9714  -19070  28784  28784  -24103  -4681
+ *   601 full      19595  38470  7471    0  -11058  -21710  32768  32768  -27439  -5329
+ * Grey pixels: R = G = B = l gives Y = clip8(((T * l + 32768) >> 16) + yoff) with T = 56284 (limited) or 65536 (full), and
+ * U = V = 128 exactly -- so a grey image that is held as one luma byte per pixel converts without ever becoming RGBA.
+ * Range: the largest product is 32768 * 1020 < 2^31, so int32 suffices; U reaches 256 in full range (saturated blue), so
+ * clip8 is needed.  Y is within 1 level of the rounded float64 matrix for every colour, U and V within 1 level.
+ *
+ * smhv_bgra_to_yuv_device, the inverse of smhv_yuv_to_bgra_device: n images in device memory (d_src 4-byte aligned, rows
+ * src_pitch_bytes apart: 0 = 4 w, a multiple of 4; images src_stride_bytes apart: 0 = src_pitch_bytes * h, a multiple of 4;
+ * bytes B, G, R, A, or R, G, B, A with SMHV_VIDEO_SRC_RGBA in src_flags) -> n frames at d_dst laid out by `layout` as
+ * smhv_yuv_layout describes them above (NULL or a zero member: tight).  Destination bases and pitches may have any byte
+ * alignment; nothing but the planes' samples is written (pitch padding, gaps and what lies between frames keep their bytes).
+ * Asynchronous on `stream` (NULL: the context's own).  SMHV_E_INVALID, with nothing enqueued, for a null pointer, n, w or h = 0,
+ * a pitch shorter than its row, planes of a frame that reach beyond frame_stride when n > 1, a non-zero v_offset for NV12
+ * (other than u_offset + 1), an unknown layout, colour bit or flag. */
+#define SMHV_VIDEO_SRC_RGBA 1u
+SMHV_API int smhv_bgra_to_yuv_device(smhv_ctx *ctx, const void *d_src, uint64_t src_pitch_bytes, uint64_t src_stride_bytes, uint32_t n, uint32_t w, uint32_t h,
+                                     uint32_t src_flags, uint32_t pixels, void *d_dst, const smhv_yuv_layout *layout, void *stream);
+/* What a batch shows a viewer, as video frames: frames [first, first + n) of `source` -> n frames at d_dst (`pixels`, `layout` as
+ * above).  A call of its own, like the feed: no stage bit.  It reads what is in memory when `stream` reaches the call and works on
+ * a plain batch and on a pipeline slot's batch after smhv_pipeline_wait.
+ *   SMHV_VIDEO_RENDER: the render slab at the window size of the most recent render (smhv_batch_render_size);
+ *                      SMHV_E_STATE before the first render.
+ *   SMHV_VIDEO_UI_MAP: the ui_map at the ROI's size (smhv_map_bounds); SMHV_E_STATE when no run has produced one.  Per frame,
+ *                      on the device, the kernel reads the form that holds the frame's newest ui_map: the luma plane of a grey
+ *                      run (by the grey formula above: no RGBA is made, and the batch's state is left as it is) or the RGBA slab.
+ *                      A frame a run found closed keeps its older image, in whichever form holds it. */
+#define SMHV_VIDEO_RENDER 0u
+#define SMHV_VIDEO_UI_MAP 1u
+SMHV_API int smhv_batch_video(smhv_batch *b, uint32_t source, uint32_t first, uint32_t n, uint32_t pixels, void *d_dst, const smhv_yuv_layout *layout, void *stream);
+/* the tight size of a frame of w x h in `pixels` (an output word): w h + 2 cw ch = smhv_ingest_staging_bytes of the same word;
+   0 for a zero size or a word that is not an output word.  Needs no device. */
+SMHV_API uint64_t smhv_video_bytes(uint32_t w, uint32_t h, uint32_t pixels);
 /* wait for everything committed (or until the slab is full); *d_frames = slab of *n <= capacity accepted frames, valid
  * until smhv_ingest_reset; *last_crc (optional) = CRC-32 of the last accepted frame.  Frames committed after the slab
  * filled up are not lost: they stay queued in their staging slots (at most `slots` of them -- smhv_ingest_acquire

@@ -167,6 +167,8 @@ class FeedHeader(C.Structure):
 
 PIXELS_NV12, PIXELS_I420 = 5, 6            # SMHV_PIXELS_*: 8-bit 4:2:0 video frames
 YUV_ROI_ONLY = 1                           # smhv_yuv_to_bgra_device flags
+VIDEO_SRC_RGBA = 1                         # smhv_bgra_to_yuv_device src_flags: the source bytes are R, G, B, A
+VIDEO_RENDER, VIDEO_UI_MAP = 0, 1          # smhv_batch_video sources
 
 
 class YuvLayout(C.Structure):
@@ -265,6 +267,10 @@ SIGNATURES = {
     "smhv_ingest_staging_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "smhv_yuv_to_bgra_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(YuvLayout), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
                                           C.c_uint32, C.c_void_p]),
+    "smhv_bgra_to_yuv_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                          C.POINTER(YuvLayout), C.c_void_p]),
+    "smhv_batch_video": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(YuvLayout), C.c_void_p]),
+    "smhv_video_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "smhv_ingest_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "smhv_ingest_reset": (C.c_int, [C.c_void_p]),
     "smhv_ingest_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

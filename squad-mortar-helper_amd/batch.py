@@ -327,6 +327,29 @@ class FrameBatch:
         else:
             L.check(self._lib.smhv_batch_feed_view(self._b, feed._f, first, n, flags, int(map_source), C.c_void_p(stream)))
 
+    def video(self, source, pixels, first=0, n=None, out_ptr=None, layout=None, stream=None):
+        """Frames [first, first + n) of what the batch shows a viewer as NV12 / I420 video frames on `stream` (smhv_batch_video).
+        source: "render" (the render slab at the most recent render's window size) or "ui_map" (the ui_map at the ROI's size; a grey
+        one is read from its luma plane, no RGBA is made).  pixels: yuv.pixels(...) with nearest chroma; layout: None (tight), a
+        yuv.yuv_layout(...) or a dict of its members.  out_ptr None: a torch uint8 tensor [n, yuv.video_bytes(w, h, pixels)] of tight
+        frames is allocated and returned after the device has finished; otherwise asynchronous, returns None."""
+        from . import yuv
+        n = self.max_frames - first if n is None else n
+        src = {"render": L.VIDEO_RENDER, "ui_map": L.VIDEO_UI_MAP}[source]
+        if isinstance(layout, dict):
+            layout = yuv.yuv_layout(**layout)
+        out = None
+        if out_ptr is None:
+            import torch
+            w, h = self.render_size() if source == "render" else self.roi[2:]
+            out = yuv._video_out(n, w, h, pixels)
+            out_ptr, layout = out.data_ptr(), None
+        L.check(self._lib.smhv_batch_video(self._b, src, first, n, int(pixels), C.c_void_p(int(out_ptr)), C.byref(layout) if layout is not None else None,
+                                           C.c_void_p(int(stream)) if stream else None))
+        if out is not None:
+            torch.cuda.synchronize()
+        return out
+
     def read_image(self, which, frame):
         x, y, w, h = self.roi
         if which in (L.IMAGE_UI_MAP, L.IMAGE_HEIGHTMAP_OVERLAY):

@@ -569,6 +569,25 @@ struct YuvRun {
 	YuvRect r[2];
 };
 hipError_t launch_yuv_to_bgra(YuvRun run, uint32_t n_rects, uint32_t layout, uint32_t bilinear, hipStream_t s);
+// ---- RGBA8 / BGRA8 / luma images -> 4:2:0 video frames (smh_yuvout.hip; smhv_bgra_to_yuv_device, smhv_batch_video) -----------
+struct YuvOutCoef { int yr, yg, yb, yoff, ur, ug, ub, vr, vg, vb; };   // a row of the header's outbound table
+// n images of w x h.  A frame is read from ONE of two sources: its pixels (src: 4 bytes each, 4-byte aligned, rows src_pitch and
+// images src_stride apart, both multiples of 4) or its luma plane (luma: one byte per pixel, rows luma_pitch and images luma_stride
+// apart, any byte alignment; the kernel reads the aligned dwords its bytes lie in, so the allocation begins and ends on a 4-byte
+// boundary, as the batch's plane does).
+// form: null = every frame from src (or from luma where src is null); else frame f from luma where form[f] == UI_FORM_LUMA.
+// dst: frames dst_stride apart, Y rows y_pitch apart from offset 0, chroma rows uv_pitch apart at u_off / v_off (NV12: the pairs
+// at u_off), any byte alignment.
+struct YuvOutRun {
+	const uint8_t *src, *luma, *form;
+	uint8_t *dst;
+	uint64_t src_pitch, src_stride, luma_pitch, luma_stride;
+	uint64_t y_pitch, uv_pitch, u_off, v_off, dst_stride;
+	uint32_t w, h, n, rgba;                  // rgba: the pixels' bytes are R, G, B, A (0: B, G, R, A)
+	uint32_t groups, pairs, items;           // (filled in by the launcher: columns of 8 pixels, row pairs, n * pairs * groups)
+	YuvOutCoef k;
+};
+hipError_t launch_bgra_to_yuv(YuvOutRun run, uint32_t layout, hipStream_t s);
 hipError_t launch_unpack_rows(const void *d_pack, void *d_frame, uint32_t pitch_px, uint32_t roi_x, uint32_t roi_y, uint32_t roi_w, uint32_t roi_h, uint32_t btn_x,
                               uint32_t btn_y, uint32_t btn_w, uint32_t btn_h, hipStream_t s);
 hipError_t launch_crc32(const void *d_msg, uint64_t n_dwords, uint32_t wgs, uint32_t rounds, uint32_t x_skip, const uint32_t *d_x_local,

@@ -2500,6 +2500,7 @@ extern "C" SMHV_API int smhv_debug_marker_table(smhv_ctx *c, uint32_t *bits) {
 // differs from the last accepted one are appended to a device-resident slab that smhv_batch_run takes.
 // ------------------------------------------------------------------------------------------------
 #include "smh_yuv.inc"
+#include "smh_yuvout.inc"
 
 struct smhv_ingest {
 	smhv_ctx *ctx = nullptr;

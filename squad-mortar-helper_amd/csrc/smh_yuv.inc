@@ -77,6 +77,33 @@ static void yuv_pack_c_row(const YuvPack &p, uint8_t *pack, uint32_t layout, uin
 	memcpy(pack + p.c_off + (size_t)plane * pitch * p.c_rows + (size_t)(r - p.c_y0) * pitch, row + (size_t)p.c_x0 * bpc, (size_t)p.c_cols * bpc);
 }
 
+// smhv_yuv_layout as the caller gave it (null, or zero members: tight) -> every member filled in, for n frames of w x h in
+// `layout` (SMHV_PIXELS_NV12 / _I420; NV12: v_offset = u_offset).  SMHV_E_INVALID for what the header lists.  Both directions.
+static int yuv_resolve_layout(const char *what, uint32_t layout, const smhv_yuv_layout *given, uint32_t n, uint32_t w, uint32_t h, smhv_yuv_layout *out) {
+	const uint64_t cw = (w + 1u) / 2u, ch = (h + 1u) / 2u;
+	const uint64_t uv_row = layout == SMHV_PIXELS_NV12 ? 2u * cw : cw;
+	smhv_yuv_layout L{};
+	if (given) L = *given;
+	if (!L.y_pitch) L.y_pitch = w;
+	if (!L.uv_pitch) L.uv_pitch = uv_row;
+	if (L.y_pitch < w || L.uv_pitch < uv_row || L.y_pitch > 0x7FFFFFFFull || L.uv_pitch > 0x7FFFFFFFull)
+		return fail(SMHV_E_INVALID, "%s: pitches %llu / %llu for rows of %u / %llu bytes", what, (unsigned long long)L.y_pitch, (unsigned long long)L.uv_pitch, w,
+		            (unsigned long long)uv_row);
+	if (!L.u_offset) L.u_offset = L.y_pitch * h;
+	if (layout == SMHV_PIXELS_NV12) {
+		if (L.v_offset && L.v_offset != L.u_offset + 1u) return fail(SMHV_E_INVALID, "%s: NV12 has its V samples at u_offset + 1", what);
+		L.v_offset = L.u_offset;
+	} else if (!L.v_offset) L.v_offset = L.u_offset + L.uv_pitch * ch;
+	// (the last row of a plane ends with its samples, not with its pitch)
+	const uint64_t y_end = L.y_pitch * (h - 1u) + w, u_end = L.u_offset + L.uv_pitch * (ch - 1u) + uv_row, v_end = L.v_offset + L.uv_pitch * (ch - 1u) + uv_row;
+	const uint64_t frame_end = std::max(y_end, std::max(u_end, v_end));
+	if (!L.frame_stride) L.frame_stride = frame_end;
+	if (n > 1u && L.frame_stride < frame_end) return fail(SMHV_E_INVALID, "%s: frame_stride %llu, a frame's planes end at %llu", what, (unsigned long long)L.frame_stride,
+	                                                      (unsigned long long)frame_end);
+	*out = L;
+	return SMHV_OK;
+}
+
 extern "C" SMHV_API uint64_t smhv_ingest_staging_bytes(uint32_t w, uint32_t h, uint32_t pixels) {
 	if (w == 0 || h == 0 || w > 32768u || h > 32768u) { (void)fail(SMHV_E_INVALID, "ingest_staging_bytes: %u x %u (1 .. 32768 each way)", w, h); return 0; }
 	YuvDesc d;
@@ -98,26 +125,10 @@ extern "C" SMHV_API int smhv_yuv_to_bgra_device(smhv_ctx *c, const void *d_src, 
 	if (!yuv_decode(pixels, &d)) return fail(SMHV_E_INVALID, "yuv_to_bgra: pixels 0x%x is not SMHV_PIXELS_YUV(NV12 | I420, matrix, range, chroma)", pixels);
 	if (flags & ~SMHV_YUV_ROI_ONLY) return fail(SMHV_E_INVALID, "yuv_to_bgra: unknown flags 0x%x", flags);
 	if ((uintptr_t)d_bgra & 3u) return fail(SMHV_E_INVALID, "yuv_to_bgra: the output is not 4-byte aligned");
-	const uint64_t cw = (w + 1u) / 2u, ch = (h + 1u) / 2u, out_frame = (uint64_t)w * h * 4u;
-	const uint64_t uv_row = d.layout == SMHV_PIXELS_NV12 ? 2u * cw : cw;
-	smhv_yuv_layout L{};
-	if (layout) L = *layout;
-	if (!L.y_pitch) L.y_pitch = w;
-	if (!L.uv_pitch) L.uv_pitch = uv_row;
-	if (L.y_pitch < w || L.uv_pitch < uv_row || L.y_pitch > 0x7FFFFFFFull || L.uv_pitch > 0x7FFFFFFFull)
-		return fail(SMHV_E_INVALID, "yuv_to_bgra: pitches %llu / %llu for rows of %u / %llu bytes", (unsigned long long)L.y_pitch, (unsigned long long)L.uv_pitch, w,
-		            (unsigned long long)uv_row);
-	if (!L.u_offset) L.u_offset = L.y_pitch * h;
-	if (d.layout == SMHV_PIXELS_NV12) {
-		if (L.v_offset && L.v_offset != L.u_offset + 1u) return fail(SMHV_E_INVALID, "yuv_to_bgra: NV12 has its V samples at u_offset + 1");
-		L.v_offset = L.u_offset;
-	} else if (!L.v_offset) L.v_offset = L.u_offset + L.uv_pitch * ch;
-	// (the last row of a plane ends with its samples, not with its pitch)
-	const uint64_t y_end = L.y_pitch * (h - 1u) + w, u_end = L.u_offset + L.uv_pitch * (ch - 1u) + uv_row, v_end = L.v_offset + L.uv_pitch * (ch - 1u) + uv_row;
-	const uint64_t frame_end = std::max(y_end, std::max(u_end, v_end));
-	if (!L.frame_stride) L.frame_stride = frame_end;
-	if (n > 1u && L.frame_stride < frame_end) return fail(SMHV_E_INVALID, "yuv_to_bgra: frame_stride %llu, a frame's planes end at %llu", (unsigned long long)L.frame_stride,
-	                                                      (unsigned long long)frame_end);
+	const uint64_t out_frame = (uint64_t)w * h * 4u;
+	smhv_yuv_layout L;
+	int lrc = yuv_resolve_layout("yuv_to_bgra", d.layout, layout, n, w, h, &L);
+	if (lrc) return lrc;
 	if (!out_stride_bytes) out_stride_bytes = out_frame;
 	if (out_stride_bytes < out_frame || (out_stride_bytes & 3u)) return fail(SMHV_E_INVALID, "yuv_to_bgra: out_stride_bytes %llu for frames of %llu bytes (a multiple of 4)",
 	                                                                         (unsigned long long)out_stride_bytes, (unsigned long long)out_frame);
