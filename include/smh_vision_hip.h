@@ -1109,6 +1109,101 @@ SMHV_API int smhv_web_event_heightmap(const uint16_t *data, uint32_t w, uint32_t
 SMHV_API int smhv_web_event_fit(int fit_to_minimap, uint8_t *out, uint64_t cap, uint64_t *len);
 SMHV_API int smhv_web_interaction_parse(const uint8_t *data, uint64_t len, uint32_t *kind, float line[4], uint32_t *index);
 
+/* ---- reach map: the firing solution from an origin to every window pixel -----------------------------------------------------
+ * Where a tube at an origin can reach, and in which band of elevation: the firing solution of "firing solutions" evaluated for
+ * every pixel of a map view's window.  The reference draws no such picture; the arithmetic is the reference's alone (markers.rs,
+ * squadex::milliradians::calc), restated for a dense pass.  Every f32 / f64 operation is one operation, left to right, unfused.
+ * Target.  Frame f, window pixel (X, Y): cx = X + 0.5f, cy = Y + 0.5f; sw, sh, tx, ty = the render options' viewport_scale (0 = 1)
+ *   and viewport_top_left.  t = ((cx - tx) / sw, (cy - ty) / sh) in f32 (MapViewport::inverse_xy), map-ROI coordinates.
+ * The pixel's value is a function of the firing solution of the line (o, t), direction 0, by the rule "firing solutions" pins for an
+ *   explicit line: P0 = o * s + t_, P1 = t * s + t_ (translate_xy, f32); the heightmap branch when the frame has a minimap rectangle,
+ *   a heightmap is given and all four rounded coordinates lie inside it (range = sqrt(dx*dx + dy*dy) of the heightmap coordinates,
+ *   alt = height(P1) - height(P0)); else the scales branch with alt = 0 when the frame has m/px, meters =
+ *   sqrt(ax*ax + ay*ay) * mpx with ax = (double)o.x - (double)t.x, ay likewise (Marker::new, the labels' rule for a line that is
+ *   not a detected one); else none.  SMHV_RENDER_BOUNDS_OFFSET acts as SMHV_FIRING_BOUNDS_OFFSET.  The heightmap passed to the call
+ *   feeds the numbers whatever ropt->flags says.
+ * Origin o (smhv_reach_options.origin_mode).  SMHV_REACH_ORIGIN_POINT: origin[2], map-ROI coordinates, the same for every frame.
+ *   SMHV_REACH_ORIGIN_LINE_P0 / _LINE_P1: that end of rec.lines[line] of each frame, read on the device.  A frame with
+ *   n_lines <= line, a closed map or an origin that is not finite has NO origin: class 0 everywhere, a result of zeros.  The
+ *   per-call path takes POINT only and has no closed map (it is stateless: it takes what it is given).
+ * Class byte.  No atan is evaluated: in-range-ness and the mil band are decided in exact IEEE arithmetic.  m = meters, V^2, V^4, g
+ *   the constants of "firing solutions" (V^2 = pow(109.890938, 2), V^4 = pow(109.890938, 4), g = 9.8):
+ *     0        nothing: no origin, source NONE, a coordinate of t not finite, or m NaN.
+ *     1        out of range: disc = V^4 - g * (g * (m * m) + 2.0 * alt * V^2) is < 0 (or NaN) -- exactly "mils[0] is NaN".
+ *     2 + k    in range, k = 0 .. 7: q = (V^2 + sqrt(disc)) / (g * m); k = the number of j in 0 .. 6 with q >= T_j, T_j =
+ *              tan(mils_j * pi / 3200) for mils_j = 900, 1000, ..., 1500, as the f64 constants smhv_reach_thresholds returns
+ *              (0x1.37efd8d87607ep+0, 0x1.7f218e25a745fp+0, 0x1.def13b73c1408p+0, 0x1.3504f333f9de6p+1, 0x1.a5f59e90600d8p+1,
+ *              0x1.41bfee2424769p+2, 0x1.44e6c595afdc2p+3).  Band k holds the elevations of [800 + 100 k, 900 + 100 k) mils, band 0
+ *              everything below 900, band 7 everything from 1500 up; m == 0 gives q = +inf and k = 7.
+ *     | 0x80   a range ring, only when ring_m > 0 and the class is not 0: set iff floor(m / ring_m) of this pixel differs from that
+ *              of pixel (X + 1, Y) or of pixel (X, Y + 1), each evaluated by the same rule even where it lies outside the window.  A
+ *              neighbour whose source differs from this pixel's, or whose class would be 0, does not count.
+ * Paint (SMHV_REACH_PAINT), into the batch's render slab, over whatever is there.  p = the palette entry of the class
+ *   (out_of_range for 1, band[k] for 2 + k), a = its fourth byte: each of R, G, B becomes (c * (255 - a) + p * a + 127) / 255 in
+ *   integers; on a ring pixel the same blend with ring[4] follows.  The image's alpha byte is untouched; class 0 leaves the pixel
+ *   as it is.  THIS DEVIATES from the reference's layering as the labels do: the tint lies over everything already drawn, the
+ *   marker strokes included.  A caller draws the text passes (labels, debug text) afterwards.
+ * Classes (SMHV_REACH_CLASSES): the class bytes, out_w * out_h per frame, rows and frames tightly packed, the call's first frame
+ *   at d_classes, into caller-provided device memory.  Needs no render slab.
+ * Summary.  One smhv_reach_result per frame in the batch's reach slab (allocated by the first call): valid = 1 iff the frame had an
+ *   origin (else every field is 0); origin = o; count[c - 1] = window pixels of class c (ring bit ignored), c = 1 .. 9; ring =
+ *   window pixels with the ring bit; source_mask: bit 1 << s iff some window pixel has a class other than 0 and source s
+ *   (SMHV_FIRING_SCALES, _HEIGHTMAP), bit 0 iff some window pixel has class 0. */
+#define SMHV_REACH_PAINT 1u            /* smhv_reach_options.flags: tint the render slab (per call: implied by rgba_inout) */
+#define SMHV_REACH_CLASSES 2u          /*   ... write the class bytes (per call: implied by classes) */
+#define SMHV_REACH_ORIGIN_POINT 0u     /* smhv_reach_options.origin_mode */
+#define SMHV_REACH_ORIGIN_LINE_P0 1u
+#define SMHV_REACH_ORIGIN_LINE_P1 2u
+#define SMHV_REACH_OUT_OF_RANGE 1u     /* the class byte */
+#define SMHV_REACH_BAND0 2u
+#define SMHV_REACH_RING 0x80u
+typedef struct {
+	uint32_t size;                       /*  0: sizeof(smhv_reach_options) == 80 */
+	uint32_t flags;                      /*  4: SMHV_REACH_PAINT | SMHV_REACH_CLASSES (0: the summary alone) */
+	uint32_t origin_mode;                /*  8: SMHV_REACH_ORIGIN_* */
+	uint32_t line;                       /* 12: _LINE_P0 / _LINE_P1: which line of the record, < SMHV_MAX_LINES */
+	float origin[2];                     /* 16: _POINT: the origin, map-ROI coordinates */
+	double ring_m;                       /* 24: metres between range rings; 0 = none; finite, >= 0 */
+	uint8_t out_of_range[4];             /* 32: the palette: R, G, B and the blend weight a */
+	uint8_t band[8][4];                  /* 36 */
+	uint8_t ring[4];                     /* 68 */
+	uint32_t reserved[2];                /* 72 */
+} smhv_reach_options;
+typedef struct {
+	uint32_t valid;                      /*  0 */
+	uint32_t source_mask;                /*  4 */
+	float origin[2];                     /*  8 */
+	uint32_t count[9];                   /* 16: classes 1 .. 9 */
+	uint32_t ring;                       /* 52 */
+	uint32_t reserved[2];                /* 56 */
+} smhv_reach_result;                     /* 64 bytes */
+/* Host only.  Fills *opt: size, flags = PAINT, origin_mode = POINT at (0, 0), ring_m = 0 and the palette -- out of range
+ * (200, 30, 30, 96); the bands from flat fire to high angle (40, 90, 255), (0, 170, 255), (0, 220, 200), (0, 230, 110), (120, 235, 0),
+ * (220, 230, 0), (255, 180, 0), (255, 120, 40), each with a = 72; ring (255, 255, 255, 160). */
+SMHV_API int smhv_reach_defaults(smhv_reach_options *opt);
+/* Host only.  The seven T_j above. */
+SMHV_API int smhv_reach_thresholds(double out[7]);
+/* The reach map of frames [first, first + n), asynchronously on `stream`; the frames' results in the reach slab are cleared on the
+ * stream ahead of the kernel.  ropt supplies the window and the viewport (quad, background and the HEIGHTMAP / MARKERS flags are
+ * not used); hm (NULL: none) feeds the numbers.  With PAINT the call runs behind whatever the batch's previous render enqueued and
+ * ropt->out_w / out_h must be the most recent render's (SMHV_E_STATE for another size or before the first render).  Without PAINT
+ * only the records are read: a plain batch after smhv_batch_run, or a pipeline slot's batch after smhv_pipeline_wait, for both
+ * searches (a batch that has not run has closed maps only).  SMHV_E_INVALID: what smhv_batch_render rejects in ropt, a wrong size,
+ * unknown flags, an unknown origin_mode, line >= SMHV_MAX_LINES, a ring_m that is negative or not finite, CLASSES with
+ * d_classes == NULL, n == 0, a range beyond the batch's capacity, a heightmap on another device.  A failed call enqueues nothing.
+ * The batch keeps a reference of hm as smhv_batch_render does. */
+SMHV_API int smhv_batch_reach(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_render_options *ropt,
+                              const smhv_reach_options *opt, void *d_classes, void *stream);
+/* The batch's reach slab: read is a synchronising host copy, ptr the device address (SMHV_E_STATE before the first smhv_batch_reach) */
+SMHV_API int smhv_batch_read_reach(smhv_batch *b, uint32_t first, uint32_t n, smhv_reach_result *out);
+SMHV_API int smhv_batch_reach_ptr(smhv_batch *b, void **d_reach);
+/* The per-call path, stateless like smhv_firing_solutions: mpx (NULL: none), minimap = {left, right, top, bottom} (NULL: none), hm
+ * (NULL: none); origin_mode must be POINT.  rgba_inout (host, out_w * out_h * 4 bytes, an image of any smhv_render_map* call or any
+ * other) is tinted in place; classes (host, out_w * out_h bytes) receives the class bytes; either may be NULL, not both; result
+ * (optional) receives the summary.  opt->flags is checked for unknown bits and otherwise not used.  Runs on the context's stream. */
+SMHV_API int smhv_reach_map(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_reach_options *opt, const double *mpx,
+                            const uint32_t minimap[4], uint8_t *rgba_inout, uint8_t *classes, smhv_reach_result *result);
+
 #ifdef __cplusplus
 }
 #endif

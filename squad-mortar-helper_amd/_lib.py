@@ -126,6 +126,24 @@ class LabelResult(C.Structure):
     _fields_ = [("n_labels", C.c_uint32), ("reserved", C.c_uint32), ("label", Label * LABEL_SLOTS)]
 
 
+REACH_PAINT, REACH_CLASSES = 1, 2                                      # smhv_reach_options.flags
+REACH_ORIGIN_POINT, REACH_ORIGIN_LINE_P0, REACH_ORIGIN_LINE_P1 = 0, 1, 2   # smhv_reach_options.origin_mode
+REACH_OUT_OF_RANGE, REACH_BAND0, REACH_RING = 1, 2, 0x80              # the class byte
+
+
+class ReachOptionsStruct(C.Structure):
+    """smhv_reach_options: what a reach map is computed from and how it is painted (80 bytes)."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("origin_mode", C.c_uint32), ("line", C.c_uint32), ("origin", C.c_float * 2),
+                ("ring_m", C.c_double), ("out_of_range", C.c_uint8 * 4), ("band", (C.c_uint8 * 4) * 8), ("ring", C.c_uint8 * 4),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class ReachResult(C.Structure):
+    """smhv_reach_result: a frame's summary of its reach map (64 bytes)."""
+    _fields_ = [("valid", C.c_uint32), ("source_mask", C.c_uint32), ("origin", C.c_float * 2), ("count", C.c_uint32 * 9), ("ring", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
 TEXT_MAX_RUNS, TEXT_MAX_BYTES, TEXT_MAX_LINES, TEXT_MAP_COORDS = 64, 64, 8, 1
 MAX_PROBES = 16
 DEBUG_DRAW_PROBES, DEBUG_MINIMAP_CAPTION = 1, 2   # smhv_debug_options.flags
@@ -326,6 +344,14 @@ SIGNATURES = {
     "smhv_debug_feed_gray_form": (C.c_int, [C.c_uint32]),
     "smhv_batch_feed_view": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "smhv_feed_frame_view": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32]),
+    "smhv_reach_defaults": (C.c_int, [C.POINTER(ReachOptionsStruct)]),
+    "smhv_reach_thresholds": (C.c_int, [C.POINTER(C.c_double)]),
+    "smhv_batch_reach": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(ReachOptionsStruct), C.c_void_p,
+                                   C.c_void_p]),
+    "smhv_batch_read_reach": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ReachResult)]),
+    "smhv_batch_reach_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smhv_reach_map": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(ReachOptionsStruct), C.POINTER(C.c_double),
+                                 C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.POINTER(ReachResult)]),
     "smhv_debug_render_form": (C.c_int, [C.c_uint32]),
     "smhv_debug_render_rule": (C.c_int, [C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -284,6 +284,39 @@ class FrameBatch:
         L.check(self._lib.smhv_batch_labels_ptr(self._b, C.byref(d)))
         return d.value or 0
 
+    def reach(self, options, reach, first=0, n=None, heightmap=None, classes_ptr=None, stream=None):
+        """The reach map of frames [first, first + n) on `stream` (smhv_batch_reach): options = a RenderOptions (the window and the
+        viewport; with paint the most recent render's), reach = a ReachOptions, heightmap = what range and altitude come from.
+        With reach.classes and classes_ptr None a torch uint8 tensor [n, out_h, out_w] is allocated, filled and returned (the call
+        then returns after the device has finished); with classes_ptr (device memory, n * out_h * out_w bytes) the call is
+        asynchronous and returns None, as it does without classes."""
+        n = self.max_frames - first if n is None else n
+        ro = reach.struct()
+        out = None
+        if reach.classes and classes_ptr is None:
+            import torch
+            out = torch.zeros((n, int(options.out_h), int(options.out_w)), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            classes_ptr = out.data_ptr()
+        L.check(self._lib.smhv_batch_reach(self._b, first, n, heightmap._hm if heightmap is not None else None, C.byref(options), C.byref(ro),
+                                           C.c_void_p(int(classes_ptr)) if classes_ptr else None, C.c_void_p(int(stream)) if stream else None))
+        if out is not None:
+            torch.cuda.synchronize()
+        return out
+
+    def read_reach(self, first=0, n=None):
+        """Synchronising host copy of the reach slab -> a ctypes array of n ReachResult."""
+        n = self.max_frames - first if n is None else n
+        out = (L.ReachResult * n)()
+        L.check(self._lib.smhv_batch_read_reach(self._b, first, n, out))
+        return out
+
+    def reach_ptr(self):
+        """Device address of the reach slab (one smhv_reach_result per frame)."""
+        d = C.c_void_p()
+        L.check(self._lib.smhv_batch_reach_ptr(self._b, C.byref(d)))
+        return d.value or 0
+
     def probe(self, options, points, first=0, n=None, stream=None):
         """The vision debugger's numbers of frames [first, first + n) at `points` = [(mx, my)] window positions (at most
         MAX_PROBES) through the viewport of `options` (a RenderOptions), on `stream` (smhv_batch_probe): no pixels.  Asynchronous;

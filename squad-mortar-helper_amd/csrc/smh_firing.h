@@ -2,7 +2,8 @@
 // mils and bearings (src/ui/markers.rs:23-200, src/squadex/milliradians.rs, heightmap-ripper/src/lib.rs:22-25; the semantics are
 // spelt out in include/smh_vision_hip.h).  One lane per line.  Device code shared by the record tail (smh_record.inc: the
 // batch-granular searches' fused tails, the service's frame_record_tail_wave, k_finalize_firing / k_scales_finalize_firing) and by
-// k_firing_lines (smhv_firing_solutions).  Built with -ffp-contract=off: every f32 / f64 operation below is the reference's, in
+// k_firing_lines (smhv_firing_solutions); the same rule restated per axis for a dense pass is k_reach's (smh_reach.hip: reach_axis,
+// reach_eval, reach_class below).  Built with -ffp-contract=off: every f32 / f64 operation below is the reference's, in
 // its order, unfused.
 #pragma once
 #include "smh_device.h"
@@ -103,6 +104,64 @@ __device__ __forceinline__ smhv_firing firing_line(const FiringRun &r, bool has_
 	o.source = source;
 	o.reserved = 0u;
 	return o;
+}
+
+// ---- the reach map (k_reach, smh_reach.hip): firing_line()'s rule for the line (origin, the target of a window pixel), direction 0,
+// restated per axis -- the heightmap coordinate of a pixel depends on its column or its row alone, and so do the scales branch's
+// differences.  The operations are firing_line()'s, one for one; what is not needed (bearings, the reverse direction, atan) is left out.
+// One axis of a pixel at centre c (cx or cy): o = the origin's coordinate, s / t = the viewport's scale and top left on this axis,
+// r0 / rlen = the heightmap rectangle's near edge and its length as firing_line() takes them, n = the heightmap's texels on this axis.
+struct ReachAxis {
+	double dh;        // heightmap branch: coordinate of the origin minus coordinate of the target (firing_line's dx / dy)
+	double ds;        // scales branch: (double)o - (double)target
+	int32_t ix;       // the target's rounded heightmap coordinate; -1 unless it AND the origin's lie inside [0, n) and a heightmap applies
+	uint32_t fin;     // the target's coordinate is finite
+};
+__device__ __forceinline__ ReachAxis reach_axis(float c, float o, float s, float t, bool use_hm, float r0, double rlen, uint32_t n) {
+	ReachAxis a;
+	const float tg = (c - t) / s;                                // MapViewport::inverse_xy
+	const float p0 = o * s + t, p1 = tg * s + t;                   // MapViewport::translate_xy
+	a.fin = isfinite(tg) ? 1u : 0u;
+	a.ds = (double)o - (double)tg;
+	a.dh = 0.0;
+	a.ix = -1;
+	if (use_hm) {
+		const double c0 = (((double)p0 - (double)r0) / rlen) * (double)n, c1 = (((double)p1 - (double)r0) / rlen) * (double)n;
+		a.dh = c0 - c1;
+		const int32_t i0 = round_i32(c0), i1 = round_i32(c1), N = (int32_t)n;
+		if (i0 >= 0 && i0 < N && i1 >= 0 && i1 < N) a.ix = i1;
+	}
+	return a;
+}
+// the origin's own rounded heightmap coordinate on one axis (-1: outside)
+__device__ __forceinline__ int32_t reach_origin_texel(float o, float s, float t, float r0, double rlen, uint32_t n) {
+	const float p0 = o * s + t;
+	const int32_t i0 = round_i32((((double)p0 - (double)r0) / rlen) * (double)n);
+	return i0 >= 0 && i0 < (int32_t)n ? i0 : -1;
+}
+// What decides a pixel's class but for the altitude: source (NONE also where the class would be 0 for another reason), meters and,
+// with rings, floor(meters / ring_m).
+struct ReachEval { double m, b; uint32_t src; };
+__device__ __forceinline__ ReachEval reach_eval(const ReachAxis &c, const ReachAxis &r, bool has_mpx, double mpx, bool rings, double ring_m) {
+	const bool hm = c.ix >= 0 && r.ix >= 0;
+	const double dx = hm ? c.dh : c.ds, dy = hm ? r.dh : r.ds;
+	const double len = sqrt(dx * dx + dy * dy);
+	ReachEval e;
+	e.m = hm ? len : len * mpx;
+	e.src = hm ? SMHV_FIRING_HEIGHTMAP : has_mpx ? SMHV_FIRING_SCALES : SMHV_FIRING_NONE;
+	if (!(c.fin & r.fin) || !(e.m == e.m)) e.src = SMHV_FIRING_NONE;
+	e.b = rings ? floor(e.m / ring_m) : 0.0;
+	return e;
+}
+// the class of a pixel with a source: 1 = out of range (mortar_mils() would be NaN), 2 + k = band k (header, "reach map")
+__device__ __forceinline__ uint32_t reach_class(double meters, double alt_delta) {
+	const double T[7] = SMH_REACH_THRESHOLDS;
+	const double disc = SMH_MORTAR_V4 - SMH_MORTAR_G * (SMH_MORTAR_G * (meters * meters) + 2.0 * alt_delta * SMH_MORTAR_V2);
+	const double q = (SMH_MORTAR_V2 + sqrt(disc)) / (SMH_MORTAR_G * meters);   // (NaN when out of range: no threshold is met)
+	uint32_t k = 0u;
+#pragma unroll
+	for (int j = 0; j < 7; ++j) k += q >= T[j] ? 1u : 0u;
+	return disc >= 0.0 ? SMHV_REACH_BAND0 + k : SMHV_REACH_OUT_OF_RANGE;
 }
 
 // The frame's firing slab from its finished record: lane l (< 64) takes line l.  Called by one wave after a wave barrier behind

@@ -237,6 +237,30 @@ struct LabelRun {
 	uint32_t per_call;                   // 1: `lines`, `mpx` / has_mpx are the call's and res is one record for the rectangle alone
 	uint32_t has_mpx;
 };
+// smhv_batch_reach / smhv_reach_map (k_reach: smh_reach.hip): the reach map of n frames.  Launch arguments, taken by value at the
+// launch.  T_j = tan(mils_j * pi / 3200), mils_j = 900 .. 1500, from glibc's tan (the header's "reach map"; never computed at run time).
+#define SMH_REACH_THRESHOLDS {0x1.37efd8d87607ep+0, 0x1.7f218e25a745fp+0, 0x1.def13b73c1408p+0, 0x1.3504f333f9de6p+1, 0x1.a5f59e90600d8p+1, \
+                              0x1.41bfee2424769p+2, 0x1.44e6c595afdc2p+3}
+#define SMH_REACH_TW 64u                 // a workgroup's tile: one column per lane ...
+#define SMH_REACH_ROWS 4u                //   ... and this many rows per wave, four waves
+#define SMH_REACH_TH (4u * SMH_REACH_ROWS)
+struct ReachRun {
+	FiringRun fr;                        // the heightmap and the viewport, as the firing solutions take them (`out` is not used)
+	const FrameAux *aux;                 // batch, per frame: open
+	const smhv_frame_result *res;        // batch, per frame: m/px, the minimap rectangle, the lines (the origin)
+	smhv_reach_result *out;              // the reach slab, at the first frame of the call; cleared ahead of the launch
+	uint8_t *img;                        // PAINT: the render slab, at the first frame of the call
+	uint8_t *cls;                        // CLASSES: out_w * out_h bytes per frame
+	uint64_t img_stride, cls_stride;     // out_w * out_h * 4, out_w * out_h
+	double mpx;                          // per call: the frame's meters per pixel (valid iff has_mpx)
+	double ring_m;
+	float origin[2];                     // SMHV_REACH_ORIGIN_POINT
+	uint32_t mm[4];                      // per call: the minimap rectangle (valid iff has_mm)
+	uint32_t out_w, out_h;
+	uint32_t origin_mode, line;
+	uint32_t per_call, has_mpx, has_mm;  // 1: mpx / has_mpx, mm / has_mm are the call's and aux, res are not read
+	uint32_t pal[10];                    // out_of_range, band[0 .. 7], ring: R, G, B, a as a little-endian word
+};
 // smhv_batch_probe / smhv_batch_render_debug / smhv_render_map_debug (k_probe, k_debug_plan, k_debug_draw: smh_debugtext.hip): the
 // vision debugger's numbers and the debug text of n frames.  Launch arguments, taken by value at the launch.
 #define SMH_DBG_ITEMS (SMHV_TEXT_MAX_RUNS + 1u + 4u * SMHV_MAX_PROBES)   // a frame's item list: the runs, the caption, four per probe
@@ -513,6 +537,8 @@ hipError_t launch_heightmap_lut16(const uint32_t *lut, uint16_t *lut16, uint32_t
 #define SMH_HM_LUT_WORDS (SMH_HM_LUT_ENTRIES + 4u + SMH_HM_LUT_ENTRIES / 2u)   // 32-bit table, {max, min, vr, -}, 16-bit table
 // the marker labels (smh_labels.hip): k_label_plan over n frames, then k_label_draw over their images
 hipError_t launch_labels(const LabelRun &r, uint32_t n, hipStream_t s);
+// the reach map (smh_reach.hip): k_reach<paint, classes> over n frames (at most 65,535: the grid's third dimension)
+hipError_t launch_reach(const ReachRun &r, uint32_t n, bool paint, bool classes, hipStream_t s);
 // the vision debugger and the debug text (smh_debugtext.hip): k_probe over n frames; with r.img also k_debug_plan and k_debug_draw
 hipError_t launch_debug_text(const Geom &g, const DebugRun &r, uint32_t n, hipStream_t s);
 void render_set_form(uint32_t form);

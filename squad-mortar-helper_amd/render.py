@@ -186,6 +186,47 @@ class LabelOptions:
         return o, (arr, mpx)
 
 
+# ---- reach map (smhv_batch_reach / smhv_reach_map): the firing solution from an origin to every window pixel ---------------------
+class ReachOptions:
+    """What a reach call computes: origin = (x, y) in map-ROI coordinates, or ("p0", i) / ("p1", i): that end of each frame's line i
+    (a batch only); ring_m = metres between range rings (0: none); paint / classes = tint the render slab / write the class bytes;
+    palette = None (the library's, smhv_reach_defaults) or dict(out_of_range=rgba, band=[8 rgba], ring=rgba), a = the blend weight."""
+
+    def __init__(self, origin=(0.0, 0.0), ring_m=0.0, paint=True, classes=False, palette=None):
+        self.origin = origin
+        self.ring_m = float(ring_m)
+        self.paint = bool(paint)
+        self.classes = bool(classes)
+        self.palette = palette
+
+    def struct(self):
+        """-> smhv_reach_options."""
+        o = L.ReachOptionsStruct()
+        L.check(L.load().smhv_reach_defaults(C.byref(o)))
+        o.flags = (L.REACH_PAINT if self.paint else 0) | (L.REACH_CLASSES if self.classes else 0)
+        if isinstance(self.origin[0], str):
+            o.origin_mode = {"p0": L.REACH_ORIGIN_LINE_P0, "p1": L.REACH_ORIGIN_LINE_P1}[self.origin[0]]
+            o.line = int(self.origin[1])
+        else:
+            o.origin_mode = L.REACH_ORIGIN_POINT
+            o.origin[0], o.origin[1] = float(self.origin[0]), float(self.origin[1])
+        o.ring_m = self.ring_m
+        if self.palette is not None:
+            for k in range(4):
+                o.out_of_range[k] = int(self.palette["out_of_range"][k])
+                o.ring[k] = int(self.palette["ring"][k])
+                for j in range(8):
+                    o.band[j][k] = int(self.palette["band"][j][k])
+        return o
+
+
+def reach_thresholds():
+    """The seven tan(mils * pi / 3200), mils = 900 .. 1500, that split the in-range classes (smhv_reach_thresholds; host only)."""
+    out = (C.c_double * 7)()
+    L.check(L.load().smhv_reach_thresholds(out))
+    return [float(v) for v in out]
+
+
 # ---- debug text and the vision debugger (smhv_batch_probe / smhv_batch_render_debug / smhv_render_map_debug) ------------------------
 def text_run(x, y, text, rgba=(255, 255, 255, 255), map_coords=False):
     """One smhv_text_run as a tuple (x, y, (r, g, b, a), flags, bytes): `text` a str (encoded as Latin-1) or bytes, '\\n' starts a

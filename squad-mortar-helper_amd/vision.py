@@ -288,6 +288,23 @@ class HipVision:
                                           len(ln), out.ctypes.data))
         return out
 
+    def reach_map(self, options, reach, mpx=None, minimap=None, heightmap=None, image=None, classes=True):
+        """The reach map of one window (smhv_reach_map; stateless like firing_solutions): options = a RenderOptions (the window and
+        the viewport), reach = a ReachOptions with a point origin; mpx, minimap = (left, right, top, bottom), heightmap: the frame's,
+        or None.  image: uint8 [out_h, out_w, 4] (any render_map image), tinted in place; classes: return the class bytes.
+        -> (uint8 [out_h, out_w] or None, ReachResult)."""
+        ro = reach.struct()
+        h, w = int(options.out_h), int(options.out_w)
+        if image is not None and (image.dtype != np.uint8 or image.shape != (h, w, 4) or not image.flags["C_CONTIGUOUS"]):
+            raise L.VisionError(L.E_INVALID, "reach_map: image must be a contiguous uint8 [%d, %d, 4]" % (h, w))
+        cls = np.empty((max(h, 1), max(w, 1)), np.uint8) if classes else None
+        res = L.ReachResult()
+        m = C.byref(C.c_double(float(mpx))) if mpx is not None else None
+        mm = (C.c_uint32 * 4)(*[int(v) for v in minimap]) if minimap is not None else None
+        L.check(self._lib.smhv_reach_map(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(options), C.byref(ro), m, mm,
+                                         image.ctypes.data if image is not None else None, cls.ctypes.data if cls is not None else None, C.byref(res)))
+        return cls, res
+
     def probe(self, viewport, points, out_w=1, out_h=1):
         """The vision debugger's numbers of the current frame at `points` = [(mx, my)] window positions through `viewport` (a
         MapViewport) -> a ctypes array of MAX_PROBES Probe.  The per-call path has no probe-only entry point: this is
