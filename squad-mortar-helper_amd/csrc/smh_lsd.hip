@@ -1515,7 +1515,7 @@ uint32_t svc_waves_for(const Geom &g, uint32_t tile_limit, uint32_t *part_words,
 	uint32_t best_w = 0, best_part = 0, best_lc = 0, best_c = 0;
 	for (uint32_t c = 0; c < 2u; ++c) {
 		const uint32_t lc = c ? W_LIST_CAP_MAX / 2u : tile_list_cap_for(g);
-		const uint32_t part = (SVC_WS_WORDS + (c ? tilec_mask_words(g.rw, g.rh, cap) : tile_mask_words(g.rw, g.rh, cap)) + 2u * lc + W_WIN_STRIDE + 3u) & ~3u;
+		const uint32_t part = (SVC_WS_WORDS + (c ? tilec_mask_words(g.rw, g.rh, cap) : tile_mask_words(g.rw, g.rh, cap)) + 2u * lc + SVC_WIN_STRIDE(c) + 3u) & ~3u;
 		uint32_t w = SVC_MAX_WAVES;
 		while (w > 0u && lsd_service_static_lds() + w * part * 4u + beside > lds_cu) --w;
 		if (w > best_w) { best_w = w; best_part = part; best_lc = lc; best_c = c; }

@@ -273,12 +273,30 @@ __device__ __forceinline__ void tilec_win(Win &m, uint32_t rw, uint32_t rh, uint
 	m.tc_rows = (const LdsWord *)(smem + (tile_cap + 1u) * 8u + G * 4u); m.tc_groups = G; m.compact = true;
 }
 
+// The service's candidate window.  In k_lsd_service a wave casts one candidate after the other in ONE window block, and the block
+// keeps its window from candidate to candidate (WinTag, smh_lsd_wave.inc): a fill happens only when the next candidate reads
+// outside it, and covers SVC_WIN_EXTRA rows BELOW its candidate's needed region, so that the scan's next rows find their window
+// there too (6 words of LDS per row and wave; svc_waves_for counts them).  k_lsd_service_c (the compact index, above 1080p) fills
+// 135 rows for every candidate as before: measured, reuse buys nothing there (DESIGN.md section 5).
+// -DSMH_NO_WINDOW_REUSE: the same in k_lsd_service -- the code before the tag (the A/B switch).
+#ifndef SVC_WIN_EXTRA
+#define SVC_WIN_EXTRA 24u               // measured among 0, 8, 16, 24 on the headline (DESIGN.md section 5, profiles/window_reuse_sweep.json); the geometry at 1080p is the same
+#endif
+#ifdef SMH_NO_WINDOW_REUSE
+#define SVC_WIN_REUSE(compact) false
+#else
+#define SVC_WIN_REUSE(compact) (!(compact))
+#endif
+#define SVC_WIN_ROWS(compact) (SVC_WIN_REUSE(compact) ? W_WIN_ROWS + SVC_WIN_EXTRA : W_WIN_ROWS)
+#define SVC_WIN_STRIDE(compact) (SVC_WIN_ROWS(compact) * LSD_W2_PITCH + 2u)   // words per service window block (as W_WIN_STRIDE)
+
 // One candidate from its pixel to its longest ray, by one wave: window + get_centre + sector culling (cand_setup), then its
 // live 64-ray units one after the other (the next unit's directions fetched while this one is cast).
 // -> start point; wkey = len^2 bits << 32 | ray index of the longest exactly evaluated ray (0: none could make a line), its end
 // point; mask samples taken (sum over the wave)
-template <int MODE>
-__device__ __forceinline__ void seq_cast_candidate(const Win &m, uint32_t *wwin, const uint32_t *cull_tab, bool cull, const RayDir *dirs, const float *ray_off, float max_gap,
+// REUSE: `wwin` holds the window `tag` places (W_WIN_ROWS + SVC_WIN_EXTRA rows) and is filled only when it does not serve; else: filled for this candidate
+template <int MODE, bool REUSE = false>
+__device__ __forceinline__ void seq_cast_candidate(const Win &m, uint32_t *wwin, WinTag *tag, const uint32_t *cull_tab, bool cull, const RayDir *dirs, const float *ray_off, float max_gap,
                                                    uint32_t px, uint32_t py, float &xs, float &ys, unsigned long long &wkey, float &ex0, float &ey0, uint32_t &steps_sum
 #ifdef SMH_LSD_WDEBUG
                                                    , unsigned long long *sprof, unsigned long long &slast, unsigned long long *uprof, uint32_t &n_units
@@ -287,10 +305,10 @@ __device__ __forceinline__ void seq_cast_candidate(const Win &m, uint32_t *wwin,
 	const uint32_t lane = opaque_lane();
 	unsigned long long live;
 #ifdef SMH_LSD_WDEBUG
-	cand_setup<MODE == LSD_MODE_TILEC>(m, wwin, cull_tab, cull, px, py, xs, ys, live, uprof);
+	cand_setup<MODE == LSD_MODE_TILEC, (REUSE ? W_WIN_ROWS + SVC_WIN_EXTRA : W_WIN_ROWS), REUSE>(m, wwin, cull_tab, cull, px, py, xs, ys, live, tag, uprof);
 	{ const unsigned long long _n = __builtin_amdgcn_s_memtime(); sprof[2] += _n - slast; slast = _n; }
 #else
-	cand_setup<MODE == LSD_MODE_TILEC>(m, wwin, cull_tab, cull, px, py, xs, ys, live);
+	cand_setup<MODE == LSD_MODE_TILEC, (REUSE ? W_WIN_ROWS + SVC_WIN_EXTRA : W_WIN_ROWS), REUSE>(m, wwin, cull_tab, cull, px, py, xs, ys, live, tag);
 #endif
 	unsigned long long bkey = 0ull;
 	float bxe = xs, bye = ys;
@@ -305,10 +323,10 @@ __device__ __forceinline__ void seq_cast_candidate(const Win &m, uint32_t *wwin,
 		unsigned long long key;
 		float xe, ye;
 #ifdef SMH_LSD_WDEBUG
-		unit_rays<MODE, (MODE == LSD_MODE_TILEC ? SEQ_RAY_GROUP_C : SEQ_RAY_GROUP)>(m, wwin, ray_off, px, py, xs, ys, u, d, max_gap, key, xe, ye, st, uprof);
+		unit_rays<MODE, (MODE == LSD_MODE_TILEC ? SEQ_RAY_GROUP_C : SEQ_RAY_GROUP), REUSE>(m, wwin, ray_off, px, py, xs, ys, u, d, max_gap, key, xe, ye, st, uprof, tag);
 		++n_units;
 #else
-		unit_rays<MODE, (MODE == LSD_MODE_TILEC ? SEQ_RAY_GROUP_C : SEQ_RAY_GROUP)>(m, wwin, ray_off, px, py, xs, ys, u, d, max_gap, key, xe, ye, st);
+		unit_rays<MODE, (MODE == LSD_MODE_TILEC ? SEQ_RAY_GROUP_C : SEQ_RAY_GROUP), REUSE>(m, wwin, ray_off, px, py, xs, ys, u, d, max_gap, key, xe, ye, st, tag);
 #endif
 		if (key > bkey) { bkey = key; bxe = xe; bye = ye; }
 	}
@@ -565,8 +583,8 @@ __device__ __forceinline__ void desk_post_more(WShared &ws, const uint32_t *list
 }
 
 // dirs: the 3600 ray directions in LDS (a copy of g_ray_table).  TEAM: the frame may ask the other waves of its workgroup for
-// help (the search service; tile store only)
-template <int MODE, bool WAVE = false, bool TEAM = false>
+// help (the search service; tile store only).  REUSE: the wave's window block keeps its window between candidates (seq_cast_candidate)
+template <int MODE, bool WAVE = false, bool TEAM = false, bool REUSE = false>
 __device__ void lsd_frame_seq(const Geom &g, const Buffers &b, uint32_t f, float max_gap, const FrameAux &aux, uint32_t *smem, WShared &ws, const uint32_t *cull_tab, const RayDir *dirs,
                               uint32_t win_cap, uint32_t list_cap, const FrameView *tile_view = nullptr) {
 	static_assert(!TEAM || (WAVE && (MODE == LSD_MODE_TILE || MODE == LSD_MODE_TILEC)), "helpers read the owner's tile store in LDS");
@@ -582,7 +600,7 @@ __device__ void lsd_frame_seq(const Geom &g, const Buffers &b, uint32_t f, float
 	const bool cull = b.cull_tab != nullptr && max_gap > 0.0f && max_gap <= 49.0f;
 	if (lane == 0) { ws.n_lines = 0u; ws.rounds = 0u; ws.steps = 0ull; }
 	if (TEAM && lane < SEQ_DESK_ENTRIES) ws.rob[lane].state = H_FREE;
-	if (TEAM && lane == 0) { ws.rem_open = 0u; ws.rem_nr = 0u; }
+	if (TEAM && lane == 0) { ws.rem_open = 0u; ws.rem_nr = 0u; if (REUSE) ws.frame_no += 1u; }   // (frame_no: what a helper keys its window by, svc_help)
 #ifdef SMH_LSD_WDEBUG
 	if (lane < 8u) ws.dbg[lane] = 0u;
 	if (lane < 10u) ws.rdbg[lane] = 0ull;
@@ -595,6 +613,9 @@ __device__ void lsd_frame_seq(const Geom &g, const Buffers &b, uint32_t f, float
 	uint32_t seg_start = 0, cur_e = 0, ahead = 0;
 	int cur_bit = -1;
 	bool done = false, want = false, desk_valid = false;        // desk_valid: the posts and the cursor belong to this list and these lines
+	// The window block holds nothing of THIS frame yet (the frame's set-up used it as scratch; the wave may have helped another
+	// frame in it since its last own).  The mask does not change during the frame, so the tag stands until the frame ends.
+	WinTag wtag = {0, 0, false};
 #ifdef SMH_LSD_WDEBUG
 	unsigned long long sprof[8] = {0, 0, 0, 0, 0, 0, 0, 0}, slast = __builtin_amdgcn_s_memtime(), uprof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 	uint32_t n_units = 0, n_taken = 0;
@@ -633,9 +654,9 @@ __device__ void lsd_frame_seq(const Geom &g, const Buffers &b, uint32_t f, float
 #endif
 #ifdef SMH_LSD_WDEBUG
 			if (have) ++n_taken;
-			if (!have) seq_cast_candidate<MODE>(m, wwin, cull_tab, cull, dirs, b.ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum, sprof, slast, uprof, n_units);
+			if (!have) seq_cast_candidate<MODE, REUSE>(m, wwin, &wtag, cull_tab, cull, dirs, b.ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum, sprof, slast, uprof, n_units);
 #else
-			if (!have) seq_cast_candidate<MODE>(m, wwin, cull_tab, cull, dirs, b.ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum);
+			if (!have) seq_cast_candidate<MODE, REUSE>(m, wwin, &wtag, cull_tab, cull, dirs, b.ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum);
 #endif
 			if (lane == 0) ws.steps += st_sum;
 			if (wkey != 0ull && __uint_as_float((uint32_t)(wkey >> 32)) > SMH_LSD_ACCEPT_LEN_SQ) {   // lsd.rs:94
@@ -742,6 +763,7 @@ __device__ void lsd_frame_seq(const Geom &g, const Buffers &b, uint32_t f, float
 		for (int k = 0; k < 5; ++k) res->meters[20 + k] = (double)sprof[k];
 		for (int k = 0; k < 3; ++k) res->meters[25 + k] = (double)uprof[8 + k];
 		res->meters[30] = (double)uprof[0]; res->meters[31] = (double)uprof[1];   // inside set-up: window fill, culling scan
+		res->length_px[28] = (double)uprof[2];                                    // window fills of the owner (candidates cast here minus windows reused)
 		res->meters[28] = (double)n_units;
 		res->meters[29] = (double)n_taken;
 		// help across workgroups: arrivals at remote posts, taken back, waited for (and for how many cycles), requests opened, round of the request

@@ -36,6 +36,8 @@
 // at most W_NWIN candidates are in flight (the speculation width stops there: measured, wider buys nothing).
 #define W_WIN_R 67
 #define W_WIN_ROWS (2 * W_WIN_R + 1)
+#include "smh_window_place.h"
+static_assert(W_WIN_R == SMH_WIN_R && LSD_W2_PITCH == SMH_WIN_WORDS, "smh_window_place.h speaks of this window");
 #define W_WIN_STRIDE (W_WIN_ROWS * LSD_W2_PITCH + 2u)   // words per window (+2: the culling scan's funnel shift reads one word past a row's end)
 #ifndef W_SPEC_MAX
 #define W_SPEC_MAX 8u                   // candidates between dispatch and retirement (W_NWIN of them being cast, the others waiting for their turn to retire)
@@ -88,7 +90,7 @@ struct WShared {
 	uint32_t ntiles;                    // LSD_MODE_TILE: non-empty tiles found while building the tile store
 	uint32_t stuck;                     // watchdog
 	uint32_t win_free;                  // windows nobody uses (bit mask)
-	uint32_t farm_on, farm_posted, farm_retired, pad0;       // helper exchange: helper attached; candidates posted / retired
+	uint32_t farm_on, farm_posted, farm_retired, frame_no;   // helper exchange: helper attached; candidates posted / retired; (the search service:) frames this block's wave has begun
 	uint32_t late, want_set, want_tick, pick;                 // late helpers: mode; the frame has asked for help; retirements since the last refresh; (target choice)
 	unsigned long long t0, late_cycles;                        // s_memtime when the search of the frame began; how long it works alone before it asks
 	// the search service's help across workgroups (smh_lsd_seq.inc, "the desk across workgroups"): set once per wave by the kernel ...
@@ -128,25 +130,45 @@ __device__ __forceinline__ const LdsByte *window_base(const uint32_t *wwin, uint
 	const int x0 = ((int)px - W_WIN_R) & ~31, y0 = (int)py - W_WIN_R;
 	return (const LdsByte *)(const LdsWord *)wwin - (__mul24(y0, (int)(4u * LSD_W2_PITCH)) + ((x0 >> 5) << 2));
 }
+// ... and of the window placed at word column x0w, row y0
+__device__ __forceinline__ const LdsByte *window_base_at(const uint32_t *wwin, int x0w, int y0) {
+	return (const LdsByte *)(const LdsWord *)wwin - (__mul24(y0, (int)(4u * LSD_W2_PITCH)) + (x0w << 2));
+}
+// Where the window in a block lies (the search service: one wave, one block, one candidate after the other).  The scan visits
+// white pixels in raster order and its rejected candidates are neighbours, so the next candidate nearly always needs words that
+// are already there: cand_setup fills the block only when its rectangle no longer contains what the candidate reads
+// (smh_window_place.h) and places every reader through the tag.  Wave-uniform; lives in the caller's scalar registers.
+// Whoever owns the tag clears `valid` whenever the mask store the window was filled from may have changed.
+struct WinTag { int x0w, y0; bool valid; };
 // A freshly dispatched candidate: its window (copied from the frame's mask store), get_centre (lsd.rs:5-44) of its pixel,
 // then the sector culling scan -> ptx, pty, live.  `wwin`: the candidate's window block (W_WIN_STRIDE words).
 // (lane ids are made opaque at the start of every per-candidate phase: the compiler otherwise hoists two dozen lane-derived
 // index constants out of the candidate loop and spills them -- and a spill reload is a vector-memory access, which beside the
 // HBM-bound streaming pass takes microseconds)
 __device__ __forceinline__ uint32_t opaque_lane() { uint32_t l = threadIdx.x & 63u; asm volatile("" : "+v"(l)); return l; }
-template <bool COMPACT = false>
-__device__ __forceinline__ void cand_setup(const Win &m, uint32_t *wwin, const uint32_t *cull_tab, bool cull, uint32_t px, uint32_t py, float &xs, float &ys, unsigned long long &live
+// TAGGED with `tag` (neither: k_lsd_tile's shared windows, filled for every candidate): the block's window may serve as it lies.  ROWS: the
+// rows a fill covers, from py - W_WIN_R on (the service's taller window: rows BELOW the needed region, for the scan's next rows).
+template <bool COMPACT = false, uint32_t ROWS = W_WIN_ROWS, bool TAGGED = false>
+__device__ __forceinline__ void cand_setup(const Win &m, uint32_t *wwin, const uint32_t *cull_tab, bool cull, uint32_t px, uint32_t py, float &xs, float &ys, unsigned long long &live,
+                                           WinTag *tag = nullptr
 #ifdef SMH_LSD_WDEBUG
-                                           , unsigned long long *cprof = nullptr                       // [0] window fill, [1] culling scan (cycles)
+                                           , unsigned long long *cprof = nullptr                       // [0] window fill, [1] culling scan (cycles), [2] window fills
 #endif
                                            ) {
+	static_assert(ROWS >= W_WIN_ROWS, "a fill covers its own candidate's needed rows");
 	const uint32_t lane = opaque_lane();
 #ifdef SMH_LSD_WDEBUG
 	const unsigned long long c_t0 = __builtin_amdgcn_s_memtime();
 #endif
-	{
-		const int wq0 = (((int)px - W_WIN_R) & ~31) >> 5, y0 = (int)py - W_WIN_R;
-		constexpr uint32_t NIT = (W_WIN_ROWS * LSD_W2_PITCH + 63u) / 64u;
+	[[maybe_unused]] bool fill = true;
+	if constexpr (TAGGED) {                                         // (the pixel is wave-uniform: the tag stays in scalar registers)
+		const int upx = (int)uniform_u32(px), upy = (int)uniform_u32(py);
+		if (tag->valid && smh_window_holds(tag->x0w, tag->y0, (int)ROWS, upx, upy)) fill = false;
+		else { smh_window_fresh(upx, upy, &tag->x0w, &tag->y0); tag->valid = true; }
+	}
+	if (!TAGGED || fill) {
+		const int wq0 = TAGGED ? tag->x0w : (((int)px - W_WIN_R) & ~31) >> 5, y0 = TAGGED ? tag->y0 : (int)py - W_WIN_R;
+		constexpr uint32_t NIT = (ROWS * LSD_W2_PITCH + 63u) / 64u;
 		if (m.tiled) {
 			// A marker mask is 1-4 % non-empty: of the 18 x 6 tiles under a window a handful hold a set bit.  So: the window is
 			// zeroed (stores, nothing to wait for), the index entries of the tiles under it are read in ONE round trip (two per
@@ -156,11 +178,11 @@ __device__ __forceinline__ void cand_setup(const Win &m, uint32_t *wwin, const u
 #pragma unroll
 			for (uint32_t k = 0; k < NIT; ++k) {
 				const uint32_t i = lane + 64u * k;
-				if (i < W_WIN_ROWS * LSD_W2_PITCH) wwin[i] = 0u;
+				if (i < ROWS * LSD_W2_PITCH) wwin[i] = 0u;
 			}
-			const int ty0 = y0 >> 3, ty1 = (y0 + (int)W_WIN_ROWS - 1) >> 3;     // (arithmetic shifts: rows above the image are negative)
-			const uint32_t nslots = (uint32_t)(ty1 - ty0 + 1) * LSD_W2_PITCH;   // <= 18 x 6 = 108 = two per lane
-			static_assert(((W_WIN_ROWS + 14u) / 8u + 1u) * LSD_W2_PITCH <= 128u, "two tile slots per lane cover the window");
+			const int ty0 = y0 >> 3, ty1 = (y0 + (int)ROWS - 1) >> 3;     // (arithmetic shifts: rows above the image are negative)
+			const uint32_t nslots = (uint32_t)(ty1 - ty0 + 1) * LSD_W2_PITCH;   // <= 18 x 6 = 108 = two per lane (135 rows; 159 rows: 21 x 6 = 126)
+			static_assert(((ROWS + 6u) / 8u + 1u) * LSD_W2_PITCH <= 128u, "two tile slots per lane cover the window (ROWS rows from any row of a tile on touch at most (ROWS + 6) / 8 + 1 tile rows)");
 			uint32_t tv[2];
 #pragma unroll
 			for (uint32_t rnd = 0; rnd < 2u; ++rnd) {
@@ -185,26 +207,26 @@ __device__ __forceinline__ void cand_setup(const Win &m, uint32_t *wwin, const u
 					const uint32_t tt = (uint32_t)__shfl((int)tv[rnd], (int)(src & 63u));
 					const uint32_t sidx = src + 64u * rnd, tr = sidx / LSD_W2_PITCH, tc = sidx - tr * LSD_W2_PITCH;
 					const int rr = ((ty0 + (int)tr) << 3) + (int)row - y0;      // the window row this lane's tile row lands in
-					if (src < 64u && rr >= 0 && rr < (int)W_WIN_ROWS) wwin[(uint32_t)rr * LSD_W2_PITCH + tc] = (uint32_t)m.t_tiles[(tt << 3) + row];
+					if (src < 64u && rr >= 0 && rr < (int)ROWS) wwin[(uint32_t)rr * LSD_W2_PITCH + tc] = (uint32_t)m.t_tiles[(tt << 3) + row];
 				}
 			}
 		} else {
 #pragma unroll 1
-			for (uint32_t i = lane; i < W_WIN_ROWS * LSD_W2_PITCH; i += 64u) {
+			for (uint32_t i = lane; i < ROWS * LSD_W2_PITCH; i += 64u) {
 				const uint32_t r = i / LSD_W2_PITCH, c = i - r * LSD_W2_PITCH;
 				const int b0 = ((wq0 + (int)c) << 5) + m.xbias;             // (the global rows start xbias bits left of pixel 0)
 				wwin[i] = __builtin_amdgcn_alignbit(win_word(m, (b0 >> 5) + 1, y0 + (int)r), win_word(m, b0 >> 5, y0 + (int)r), (uint32_t)b0 & 31u);
 			}
 		}
-		if (lane < 2u) wwin[W_WIN_ROWS * LSD_W2_PITCH + lane] = 0u;
+		if (lane < 2u) wwin[ROWS * LSD_W2_PITCH + lane] = 0u;
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");        // this wave reads the window next; the others after the release of `todo`
 		__builtin_amdgcn_wave_barrier();
 	}
 #ifdef SMH_LSD_WDEBUG
-	if (cprof) cprof[0] += __builtin_amdgcn_s_memtime() - c_t0;
+	if (cprof) { cprof[0] += __builtin_amdgcn_s_memtime() - c_t0; if (fill) cprof[2] += 1ull; }
 #endif
 	Win mw = m;
-	mw.w2 = window_base(wwin, px, py);
+	mw.w2 = TAGGED ? window_base_at(wwin, tag->x0w, tag->y0) : window_base(wwin, px, py);
 	{   // lane (dir, k) evaluates the k-th loop condition of direction dir (left, right, up, down)
 		const uint32_t l = lane & 31u, dir = l >> 3, k = l & 7u;
 		const float cx = (float)px, cy = (float)py, fk = (float)k;
@@ -422,10 +444,10 @@ __device__ __forceinline__ void long_rays_round(const Win &m, const float *ray_o
 // The rays of unit u of the candidate whose pixel is (px, py) and start point (xs, ys): per lane the ray's key (len^2 bits << 32
 // | ray index; 0 = not evaluated exactly: it cannot matter), its end point and the mask samples it took (added to `steps`).
 __device__ __forceinline__ RayDir unit_dirs(uint32_t u) { return g_ray_table[min(u * 64u + (threadIdx.x & 63u), (uint32_t)SMH_LSD_RAYS - 1u)]; }
-// (d = unit_dirs(u): a global load the caller may issue early)
-template <int MODE, int G = 8>
+// (d = unit_dirs(u): a global load the caller may issue early; tag: where the window lies when cand_setup was given one)
+template <int MODE, int G = 8, bool TAGGED = false>
 __device__ __forceinline__ void unit_rays(const Win &m, const uint32_t *wwin, const float *ray_off, uint32_t px, uint32_t py, float xs, float ys, uint32_t u, const RayDir d, float max_gap,
-                                          unsigned long long &key, float &xe, float &ye, uint32_t &steps UPROF_PARAM) {
+                                          unsigned long long &key, float &xe, float &ye, uint32_t &steps UPROF_PARAM, const WinTag *tag = nullptr) {
 #ifdef SMH_LSD_WDEBUG
 	unsigned long long ulast = __builtin_amdgcn_s_memtime();
 #endif
@@ -445,7 +467,7 @@ __device__ __forceinline__ void unit_rays(const Win &m, const uint32_t *wwin, co
 		if (fast) {
 			// the first batches out of the candidate's window (the start point is in the image, within 2.5 px of the pixel)
 			Win mw = m;
-			mw.w2 = window_base(wwin, px, py);
+			mw.w2 = TAGGED ? window_base_at(wwin, tag->x0w, tag->y0) : window_base(wwin, px, py);
 			status = RAY_CONTINUE;
 #pragma unroll 1
 			for (uint32_t bi = 0; bi < W_A_BATCHES && status == RAY_CONTINUE; ++bi) status = ray_batch<LSD_MODE_WIN2, G>(mw, xs, ys, dx, dy, T, s, steps);

@@ -53,7 +53,7 @@ __device__ __attribute__((noinline)) void svc_frame_global(const void *kargs, ui
 	const Geom g = ka->g;
 	const Buffers b = ((SvcSlotPtr)(ka->p.slots + slot))->b;
 	const FrameAux aux = b.aux[f];
-	lsd_frame_seq<LSD_MODE_GLOBAL, true>(g, b, f, ka->p.max_gap, aux, part + SVC_WS_WORDS, *(WShared *)part, lds_ptr(cull_off), (const RayDir *)lds_ptr(dirs_off), 0u, ka->p.list_cap);
+	lsd_frame_seq<LSD_MODE_GLOBAL, true, false, SVC_WIN_REUSE(COMPACT)>(g, b, f, ka->p.max_gap, aux, part + SVC_WS_WORDS, *(WShared *)part, lds_ptr(cull_off), (const RayDir *)lds_ptr(dirs_off), 0u, ka->p.list_cap);
 }
 
 // -> s_memtime at the end of the search proper (before the record)
@@ -82,17 +82,17 @@ __device__ __attribute__((noinline)) unsigned long long svc_frame(const void *ka
 		bool fits;
 		if constexpr (COMPACT) {
 			uint32_t rc = 2u;
-			if (b.tiled && aux.tiles && !(ka->p.flags & 32u)) rc = frame_setup_tilec_occ(g, b, f, aux, smem, tile_cap, &ws.ntiles, v, smem + tilec_mask_words(g.rw, g.rh, tile_cap), 2u * ka->p.list_cap + W_WIN_STRIDE);
+			if (b.tiled && aux.tiles && !(ka->p.flags & 32u)) rc = frame_setup_tilec_occ(g, b, f, aux, smem, tile_cap, &ws.ntiles, v, smem + tilec_mask_words(g.rw, g.rh, tile_cap), 2u * ka->p.list_cap + SVC_WIN_STRIDE(true));
 			fits = rc == 2u ? frame_setup_tilec(g, b, f, aux, smem, tile_cap, &ws.ntiles, v) : rc == 0u;
 		} else {
 			// from the tile-major mask the pass left (2-3 round trips); the walk over the bit rows' bounding box when there is none
 			uint32_t rc = 2u;
-			if (b.tiled && aux.tiles && !(ka->p.flags & 32u)) rc = frame_setup_tile_occ(g, b, f, aux, smem, tile_cap, &ws.ntiles, v, smem + tile_mask_words(g.rw, g.rh, tile_cap), 2u * ka->p.list_cap + W_WIN_STRIDE);
+			if (b.tiled && aux.tiles && !(ka->p.flags & 32u)) rc = frame_setup_tile_occ(g, b, f, aux, smem, tile_cap, &ws.ntiles, v, smem + tile_mask_words(g.rw, g.rh, tile_cap), 2u * ka->p.list_cap + SVC_WIN_STRIDE(false));
 			fits = rc == 2u ? frame_setup_tile<true>(g, b, f, aux, smem, tile_cap, &ws.ntiles, v) : rc == 0u;
 		}
 		if (fits) {
-			if constexpr (COMPACT) lsd_frame_seq<LSD_MODE_TILEC, true, true>(g, b, f, ka->p.max_gap, aux, smem, ws, lds_ptr(cull_off), (const RayDir *)lds_ptr(dirs_off), tilec_mask_words(g.rw, g.rh, tile_cap), ka->p.list_cap, &v);
-			else lsd_frame_seq<LSD_MODE_TILE, true, true>(g, b, f, ka->p.max_gap, aux, smem, ws, lds_ptr(cull_off), (const RayDir *)lds_ptr(dirs_off), tile_mask_words(g.rw, g.rh, tile_cap), ka->p.list_cap, &v);
+			if constexpr (COMPACT) lsd_frame_seq<LSD_MODE_TILEC, true, true, SVC_WIN_REUSE(true)>(g, b, f, ka->p.max_gap, aux, smem, ws, lds_ptr(cull_off), (const RayDir *)lds_ptr(dirs_off), tilec_mask_words(g.rw, g.rh, tile_cap), ka->p.list_cap, &v);
+			else lsd_frame_seq<LSD_MODE_TILE, true, true, SVC_WIN_REUSE(false)>(g, b, f, ka->p.max_gap, aux, smem, ws, lds_ptr(cull_off), (const RayDir *)lds_ptr(dirs_off), tile_mask_words(g.rw, g.rh, tile_cap), ka->p.list_cap, &v);
 		} else svc_frame_global<COMPACT>(kargs, slot, f, part_off, cull_off, dirs_off);
 	}
 	const unsigned long long t_search_end = __builtin_amdgcn_s_memtime();
@@ -127,6 +127,16 @@ __device__ __attribute__((noinline)) void svc_help(const void *kargs, uint32_t o
 	const uint32_t *cull_tab = lds_ptr(cull_off);
 	const RayDir *dirs = (const RayDir *)lds_ptr(dirs_off);
 	uint32_t idle = 0;
+	// The window this wave keeps between the casts of ONE attach: invalid at entry (whatever the block holds is of another frame),
+	// and every cast below is for the same frame of the owner.  Proof: this wave is counted in wo.late from the attach above to
+	// the fetch_sub at the end of this function, and the owner ends its frame with `want_set = 0; wait until late == 0`
+	// (lsd_frame_seq) BEFORE it writes its next frame's tile store.  The attach raised `late` and then saw want_set != 0, so the
+	// owner had not passed that wait -- had it passed, it would have found late != 0 -- and it cannot pass it while this wave
+	// is counted.  The same argument is what lets a helper read the owner's tiles at all; the window does not rest on it alone:
+	// the tag is keyed by the owner's frame counter (WShared::frame_no, raised at the start of every frame), read with every post
+	// taken -- one LDS read per cast -- and a window of another frame is never reused.
+	WinTag wtag = {0, 0, false};
+	uint32_t wframe = 0u;
 	while (uniform_u32(W_LD_ACQ(&wo.want_set))) {
 		// the oldest post nobody has taken
 		uint32_t key = 0u;                                      // ~(running number << 2 | entry), 0 = none
@@ -143,15 +153,19 @@ __device__ __attribute__((noinline)) void svc_help(const void *kargs, uint32_t o
 		if (!uniform_u32(got)) continue;                        // (the owner took it back, or another helper was quicker)
 		idle = 0;
 		const uint32_t px = uniform_u32(sl.px), py = uniform_u32(sl.py);
+		if (SVC_WIN_REUSE(COMPACT)) {
+			const uint32_t oframe = uniform_u32(W_LD(&wo.frame_no));
+			if (oframe != wframe) { wframe = oframe; wtag.valid = false; }
+		}
 		float xs, ys, ex0, ey0;
 		unsigned long long wkey;
 		uint32_t st_sum;
 #ifdef SMH_LSD_WDEBUG
 		unsigned long long sprof[8] = {0, 0, 0, 0, 0, 0, 0, 0}, slast = __builtin_amdgcn_s_memtime(), uprof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 		uint32_t n_units = 0;
-		seq_cast_candidate<COMPACT ? LSD_MODE_TILEC : LSD_MODE_TILE>(m, wwin, cull_tab, cull, dirs, ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum, sprof, slast, uprof, n_units);
+		seq_cast_candidate<COMPACT ? LSD_MODE_TILEC : LSD_MODE_TILE, SVC_WIN_REUSE(COMPACT)>(m, wwin, &wtag, cull_tab, cull, dirs, ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum, sprof, slast, uprof, n_units);
 #else
-		seq_cast_candidate<COMPACT ? LSD_MODE_TILEC : LSD_MODE_TILE>(m, wwin, cull_tab, cull, dirs, ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum);
+		seq_cast_candidate<COMPACT ? LSD_MODE_TILEC : LSD_MODE_TILE, SVC_WIN_REUSE(COMPACT)>(m, wwin, &wtag, cull_tab, cull, dirs, ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum);
 #endif
 		if (lane == 0) {
 			sl.ptx = xs; sl.pty = ys; sl.best = wkey; sl.ex = ex0; sl.ey = ey0; sl.steps = st_sum;
@@ -206,6 +220,9 @@ __device__ __attribute__((noinline)) void svc_help_remote(const void *kargs, uin
 	uint32_t *wwin = store + (COMPACT ? tilec_mask_words(rw, rh, tile_cap) : tile_mask_words(rw, rh, tile_cap)) + 2u * list_cap;
 	const uint32_t *cull_tab = lds_ptr(cull_off);
 	const RayDir *dirs = (const RayDir *)lds_ptr(dirs_off);
+	// The window between the casts of this attach: invalid at entry (the store above has just been copied in), and the store is
+	// this wave's own copy of ONE request's tiles -- the loop leaves when the request's number changes -- so it stands until the end.
+	WinTag wtag = {0, 0, false};
 	uint32_t idle = 0, n_cast = 0, n_polls = 0, n_empty = 0, n_lost = 0, exit_idle = 0;
 	unsigned long long t_cast = 0ull;
 	const unsigned long long t_att = __builtin_amdgcn_s_memtime();
@@ -244,9 +261,9 @@ __device__ __attribute__((noinline)) void svc_help_remote(const void *kargs, uin
 #ifdef SMH_LSD_WDEBUG
 		unsigned long long sprof[8] = {0, 0, 0, 0, 0, 0, 0, 0}, slast = __builtin_amdgcn_s_memtime(), uprof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 		uint32_t n_units = 0;
-		seq_cast_candidate<COMPACT ? LSD_MODE_TILEC : LSD_MODE_TILE>(m, wwin, cull_tab, cull, dirs, ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum, sprof, slast, uprof, n_units);
+		seq_cast_candidate<COMPACT ? LSD_MODE_TILEC : LSD_MODE_TILE, SVC_WIN_REUSE(COMPACT)>(m, wwin, &wtag, cull_tab, cull, dirs, ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum, sprof, slast, uprof, n_units);
 #else
-		seq_cast_candidate<COMPACT ? LSD_MODE_TILEC : LSD_MODE_TILE>(m, wwin, cull_tab, cull, dirs, ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum);
+		seq_cast_candidate<COMPACT ? LSD_MODE_TILEC : LSD_MODE_TILE, SVC_WIN_REUSE(COMPACT)>(m, wwin, &wtag, cull_tab, cull, dirs, ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum);
 #endif
 		++n_cast;
 		t_cast += __builtin_amdgcn_s_memtime() - t_c0;
@@ -406,6 +423,7 @@ __device__ __forceinline__ void svc_kernel_body(const Geom &g, const SvcParams &
 	if (lane == 0) {
 		WShared &w0 = *(WShared *)(smem + wave * p.part_words);
 		w0.want_set = 0u; w0.late = 0u;
+		if (SVC_WIN_REUSE(COMPACT)) w0.frame_no = 0u;
 		const uint32_t owner = blockIdx.x * (blockDim.x >> 6) + wave;
 		const bool rem = p.remote != nullptr && !(p.flags & 8u) && owner < 0x10000u;
 		w0.rem_r = rem ? (unsigned long long)(uintptr_t)(p.remote + owner) : 0ull;

@@ -107,6 +107,10 @@ if os.environ.get("SVC_RATE_WPROF"):
     prof["rounds"] = float(np.mean([r.rounds for r in recs]))
     prof["s_window_fill"] = float(np.mean([r.meters[30] for r in recs]))
     prof["s_cull_scan"] = float(np.mean([r.meters[31] for r in recs]))
+    # windows the frame's own wave filled (candidates it cast itself minus those whose window was already there): tools/window_reuse_count.py
+    # predicts it for a wave that casts every candidate of its frame (RATE_FLAGS=9: no help)
+    prof["window_fills"] = float(np.mean([r.length_px[28] for r in recs]))
+    prof["cast_by_owner"] = prof["rounds"] - float(np.mean([r.meters[29] for r in recs]))
 pipe.close()
 print(json.dumps({"frames_per_s": N * passes / dt, "ms_per_pass": dt / passes * 1e3, "N": N, "depth": depth, "stages": stages, "frame": [W, H],
                   "slots_equal_plain_run": all(equal), "env": {k: v for k, v in os.environ.items() if k.startswith(("SMH_", "RATE_"))}, "search_service": st, "scan_profile_cycles_per_frame": prof, "stage_ms": stage_ms, "slow_submits": len(slow)}))
