@@ -1,5 +1,5 @@
 // smh_debugtext.inc -- the vision debugger and the Debug menu's text of the map view: public entry points (smh_vision_hip.h, "map
-// view: debug text and the vision debugger"; device code in smh_debugtext.hip).  Included at the end of smh_runtime.cpp.
+// view: debug text and the vision debugger"; device code in smh_debugtext.hip).  Included at the end of smh_runtime.cpp, after smh_render.inc and smh_labels.inc.
 #include "smh_font5x7_ascii.h"
 
 extern "C" SMHV_API int smhv_text_font(uint8_t ch, uint8_t rows[7]) {
@@ -116,8 +116,8 @@ static int debug_prepare(smhv_batch *b, const smhv_render_options *ropt, const s
 	r->scale = d->scale ? d->scale : 2u;
 	r->out_w = ropt->out_w; r->out_h = ropt->out_h;
 	r->img_stride = (uint64_t)ropt->out_w * ropt->out_h * 4u;
-	r->sw = ropt->viewport_scale[0] == 0.0f ? 1.0f : ropt->viewport_scale[0];
-	r->sh = ropt->viewport_scale[1] == 0.0f ? 1.0f : ropt->viewport_scale[1];
+	r->sw = view_scale(ropt->viewport_scale[0]);
+	r->sh = view_scale(ropt->viewport_scale[1]);
 	r->tx = ropt->viewport_top_left[0]; r->ty = ropt->viewport_top_left[1];
 	return SMHV_OK;
 }
@@ -130,13 +130,14 @@ extern "C" SMHV_API int smhv_batch_probe(smhv_batch *b, uint32_t first, uint32_t
 	if (ropt->size != sizeof(smhv_render_options)) return fail(SMHV_E_INVALID, "batch_probe: smhv_render_options.size %u != %zu", ropt->size, sizeof(smhv_render_options));
 	if (n_points > SMHV_MAX_PROBES) return fail(SMHV_E_INVALID, "batch_probe: %u points (at most %u)", n_points, SMHV_MAX_PROBES);
 	if (n_points && !points) return fail(SMHV_E_INVALID, "batch_probe: %u points and a null pointer", n_points);
-	if (n == 0u || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_probe: frames [%u, %u + %u) of a batch of %u", first, first, n, b->max_frames);
+	int rc = check_frames(b, first, n, "batch_probe");
+	if (rc) return rc;
 	if (!b->ui_written) return fail(SMHV_E_STATE, "batch_probe: no run of this batch has produced a ui_map (SMHV_STAGE_UI_MAP)");
 	HIPCHK(hipSetDevice(b->ctx->device));
 	hipStream_t s = (hipStream_t)stream;
 	smhv_debug_options d;
 	DebugRun r;
-	int rc = debug_prepare(b, ropt, probe_options(&d, points, n_points), false, s, &r);
+	rc = debug_prepare(b, ropt, probe_options(&d, points, n_points), false, s, &r);
 	if (rc) return rc;
 	rc = batch_materialize_ui(b, s);                              // the RGBA slab is made when it is read (smh_runtime.cpp)
 	if (rc) return rc;
@@ -153,10 +154,7 @@ extern "C" SMHV_API int smhv_batch_probe(smhv_batch *b, uint32_t first, uint32_t
 extern "C" SMHV_API int smhv_batch_read_probes(smhv_batch *b, uint32_t first, uint32_t n, smhv_probe *out) {
 	if (!b || !out || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_read_probes: bad arguments");
 	if (!b->probed) return fail(SMHV_E_STATE, "batch_read_probes: this batch has not probed");
-	HIPCHK(hipSetDevice(b->ctx->device));
-	HIPCHK(hipDeviceSynchronize());
-	HIPCHK(hipMemcpy(out, b->d_probes + (size_t)first * SMHV_MAX_PROBES, sizeof(smhv_probe) * SMHV_MAX_PROBES * n, hipMemcpyDeviceToHost));
-	return SMHV_OK;
+	return batch_read_rows(b, b->d_probes, sizeof(smhv_probe) * SMHV_MAX_PROBES, first, n, out);
 }
 
 extern "C" SMHV_API int smhv_batch_probes_ptr(smhv_batch *b, void **d_probes) {
@@ -177,10 +175,11 @@ extern "C" SMHV_API int smhv_batch_render_debug(smhv_batch *b, uint32_t first, u
 	if (rc) return rc;
 	rc = check_debug_options(dopt, "batch_render_debug");
 	if (rc) return rc;
-	if (n == 0u || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_render_debug: frames [%u, %u + %u) of a batch of %u", first, first, n, b->max_frames);
+	rc = check_frames(b, first, n, "batch_render_debug");
+	if (rc) return rc;
 	if (!b->d_render) return fail(SMHV_E_STATE, "batch_render_debug: this batch has not rendered");
-	if (ropt->out_w != b->render_w || ropt->out_h != b->render_h)
-		return fail(SMHV_E_STATE, "batch_render_debug: a window of %u x %u, the batch's most recent render is %u x %u", ropt->out_w, ropt->out_h, b->render_w, b->render_h);
+	rc = check_window_is_last_render(b, ropt, "batch_render_debug");
+	if (rc) return rc;
 	HIPCHK(hipSetDevice(b->ctx->device));
 	hipStream_t s = (hipStream_t)stream;
 	HIPCHK(hipStreamWaitEvent(s, b->ev_render, 0));               // behind the render and the labels that drew the images, whatever stream they took
@@ -208,5 +207,5 @@ extern "C" SMHV_API int smhv_render_map_debug(smhv_ctx *c, const smhv_heightmap 
                                               uint8_t *rgba, smhv_label_result *labels, smhv_probe *probes) {
 	const int rc = check_debug_options(dopt, "render_map_debug");
 	if (rc) return rc;
-	return render_map_text(c, hm, ropt, layers, lines, n_lines, lopt, dopt, rgba, labels, probes, "render_map_debug");
+	return render_map_per_call(c, hm, ropt, layers, lines, n_lines, lopt, dopt, rgba, labels, probes, PER_CALL_TEXT, "render_map_debug");
 }

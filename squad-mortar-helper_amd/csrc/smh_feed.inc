@@ -185,10 +185,12 @@ extern "C" SMHV_API int smhv_batch_feed_view(smhv_batch *b, smhv_feed *f, uint32
 	if (!b || !f) return fail(SMHV_E_INVALID, "batch_feed: null argument");
 	CTX_OPEN(b->ctx);
 	CTX_OPEN(f->ctx);
-	if (f->ctx->device != b->ctx->device) return fail(SMHV_E_INVALID, "batch_feed: the feed lives on device %d, the batch on %d", f->ctx->device, b->ctx->device);
-	if (n == 0u || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_feed: frames [%u, %u + %u) of a batch of %u", first, first, n, b->max_frames);
+	int rc = check_device(f->ctx->device, b->ctx->device, "batch_feed", "feed", "batch");
+	if (rc) return rc;
+	rc = check_frames(b, first, n, "batch_feed");
+	if (rc) return rc;
 	FeedSrc v;
-	int rc = feed_batch_source(b, first, map_source, false, &v);
+	rc = feed_batch_source(b, first, map_source, false, &v);
 	if (rc) return rc;
 	rc = feed_check(f, v.w, v.h, n, flags, "batch_feed");
 	if (rc) return rc;
@@ -250,7 +252,8 @@ extern "C" SMHV_API int smhv_feed_frame_view(smhv_ctx *c, smhv_feed *f, const sm
 	CTX_OPEN(c);
 	if (!f || (n_lines && !lines)) return fail(SMHV_E_INVALID, "feed_frame: null argument");
 	CTX_OPEN(f->ctx);
-	if (f->ctx->device != c->device) return fail(SMHV_E_INVALID, "feed_frame: the feed lives on device %d, the context on %d", f->ctx->device, c->device);
+	rc = check_device(f->ctx->device, c->device, "feed_frame", "feed", "context");
+	if (rc) return rc;
 	if (n_lines > SMHV_MAX_LINES) return fail(SMHV_E_INVALID, "feed_frame: %u lines (at most %u)", n_lines, (unsigned)SMHV_MAX_LINES);
 	if (map_source > (uint32_t)SMHV_VIEW_CROPPED_BRQ) return fail(SMHV_E_INVALID, "feed_frame_view: unknown map source %u", map_source);
 	smhv_batch *b = c->fb;
@@ -259,9 +262,8 @@ extern "C" SMHV_API int smhv_feed_frame_view(smhv_ctx *c, smhv_feed *f, const sm
 	if (rc) return rc;
 	FeedSrc v = feed_src_ui(g, b->d_ui);
 	if (map_source != (uint32_t)SMHV_VIEW_NONE) {             // smhv_get_debug_view's image of this moment, and its size
-		const int which = (int)map_source;
-		const bool brq = which == SMHV_VIEW_OCR_INPUT || which == SMHV_VIEW_FIND_SCALES_INPUT || which == SMHV_VIEW_CROPPED_BRQ;
-		v.mode = SMH_RND_SRC_RGBA; v.w = brq ? g.qw : g.rw; v.h = brq ? g.qh : g.rh;
+		v.mode = SMH_RND_SRC_RGBA;
+		debug_view_size(g, (int)map_source, &v.w, &v.h);
 		v.xoff = 0u; v.quads = 0u; v.pitch = 4ull * v.w; v.stride = 0;
 	}
 	rc = feed_check(f, v.w, v.h, 1, flags, "feed_frame");
@@ -283,8 +285,7 @@ extern "C" SMHV_API int smhv_feed_frame_view(smhv_ctx *c, smhv_feed *f, const sm
 		v.lead = (uint32_t)(rows * SMH_FEED_IMAGE_ROW - dw);
 		v.base = f->d_view + 4ull * v.lead;
 		if (v.lead) HIPCHK(hipMemsetAsync(f->d_view, 0, 4ull * v.lead, c->s_main));
-		Buffers bf = make_buffers(b, c->frame_ptr, 0);
-		HIPCHK(launch_debug_view(g, bf, 0, (int)map_source, c->isolated ? 1 : 0, f->d_view + 4ull * v.lead, c->s_main));
+		HIPCHK(ctx_debug_view(c, (int)map_source, f->d_view + 4ull * v.lead));
 	}
 	smhv_frame_result *h = f->h_rec;
 	memset(h, 0, sizeof *h);

@@ -38,11 +38,7 @@ static int check_reach_options(const smhv_reach_options *o, const char *what) {
 // the launch arguments but for the frames' own pointers
 static void reach_run_params(const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_reach_options *o, ReachRun *r) {
 	memset(r, 0, sizeof *r);
-	smhv_firing_options fo{};
-	fo.size = sizeof fo;
-	fo.flags = (ropt->flags & SMHV_RENDER_BOUNDS_OFFSET) ? SMHV_FIRING_BOUNDS_OFFSET : 0u;
-	fo.viewport_scale[0] = ropt->viewport_scale[0]; fo.viewport_scale[1] = ropt->viewport_scale[1];
-	fo.viewport_top_left[0] = ropt->viewport_top_left[0]; fo.viewport_top_left[1] = ropt->viewport_top_left[1];
+	const smhv_firing_options fo = firing_opts_of_render(ropt);
 	firing_run_params(hm, &fo, &r->fr);
 	r->out_w = ropt->out_w; r->out_h = ropt->out_h;
 	r->img_stride = (uint64_t)ropt->out_w * ropt->out_h * 4u;
@@ -63,14 +59,16 @@ extern "C" SMHV_API int smhv_batch_reach(smhv_batch *b, uint32_t first, uint32_t
 	if (rc) return rc;
 	rc = check_reach_options(opt, "batch_reach");
 	if (rc) return rc;
-	if (n == 0u || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_reach: frames [%u, %u + %u) of a batch of %u", first, first, n, b->max_frames);
-	if (hm && hm->ctx->device != b->ctx->device) return fail(SMHV_E_INVALID, "batch_reach: the heightmap lives on device %d, the batch on %d", hm->ctx->device, b->ctx->device);
+	rc = check_frames(b, first, n, "batch_reach");
+	if (rc) return rc;
+	rc = check_hm_device(hm, b->ctx->device, "batch_reach", "batch");
+	if (rc) return rc;
 	const bool paint = (opt->flags & SMHV_REACH_PAINT) != 0u, classes = (opt->flags & SMHV_REACH_CLASSES) != 0u;
 	if (classes && !d_classes) return fail(SMHV_E_INVALID, "batch_reach: SMHV_REACH_CLASSES and a null d_classes");
 	if (paint) {
 		if (!b->d_render) return fail(SMHV_E_STATE, "batch_reach: SMHV_REACH_PAINT and this batch has not rendered");
-		if (ropt->out_w != b->render_w || ropt->out_h != b->render_h)
-			return fail(SMHV_E_STATE, "batch_reach: a window of %u x %u, the batch's most recent render is %u x %u", ropt->out_w, ropt->out_h, b->render_w, b->render_h);
+		rc = check_window_is_last_render(b, ropt, "batch_reach");
+		if (rc) return rc;
 	}
 	HIPCHK(hipSetDevice(b->ctx->device));
 	if (!b->d_reach) {
@@ -84,15 +82,7 @@ extern "C" SMHV_API int smhv_batch_reach(smhv_batch *b, uint32_t first, uint32_t
 	}
 	hipStream_t s = (hipStream_t)stream;
 	if (paint) HIPCHK(hipStreamWaitEvent(s, b->ev_render, 0));     // behind the render (and the text passes) that drew the images
-	{                                                               // the batch's reference of the heightmap its enqueued call reads
-		smhv_heightmap *h = const_cast<smhv_heightmap *>(hm);
-		if (b->reach_hm != h) {
-			hm_retain(h);
-			smhv_heightmap *old = b->reach_hm;
-			b->reach_hm = h;
-			hm_release(old);
-		}
-	}
+	hm_rebind(&b->reach_hm, hm);                                   // the batch's reference of the heightmap its enqueued call reads
 	ReachRun r;
 	reach_run_params(hm, ropt, opt, &r);
 	HIPCHK(hipMemsetAsync(b->d_reach + first, 0, sizeof(smhv_reach_result) * (size_t)n, s));
@@ -114,10 +104,7 @@ extern "C" SMHV_API int smhv_batch_reach(smhv_batch *b, uint32_t first, uint32_t
 extern "C" SMHV_API int smhv_batch_read_reach(smhv_batch *b, uint32_t first, uint32_t n, smhv_reach_result *out) {
 	if (!b || !out || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_read_reach: bad arguments");
 	if (!b->d_reach) return fail(SMHV_E_STATE, "batch_read_reach: this batch has computed no reach map");
-	HIPCHK(hipSetDevice(b->ctx->device));
-	HIPCHK(hipDeviceSynchronize());
-	HIPCHK(hipMemcpy(out, b->d_reach + first, sizeof(smhv_reach_result) * n, hipMemcpyDeviceToHost));
-	return SMHV_OK;
+	return batch_read_rows(b, b->d_reach, sizeof(smhv_reach_result), first, n, out);
 }
 
 extern "C" SMHV_API int smhv_batch_reach_ptr(smhv_batch *b, void **d_reach) {
@@ -139,7 +126,8 @@ extern "C" SMHV_API int smhv_reach_map(smhv_ctx *c, const smhv_heightmap *hm, co
 	rc = check_reach_options(opt, "reach_map");
 	if (rc) return rc;
 	if (opt->origin_mode != SMHV_REACH_ORIGIN_POINT) return fail(SMHV_E_INVALID, "reach_map: origin mode %u (the per-call path takes SMHV_REACH_ORIGIN_POINT only)", opt->origin_mode);
-	if (hm && hm->ctx->device != c->device) return fail(SMHV_E_INVALID, "reach_map: the heightmap lives on device %d, the context on %d", hm->ctx->device, c->device);
+	rc = check_hm_device(hm, c->device, "reach_map", "context");
+	if (rc) return rc;
 	HIPCHK(hipSetDevice(c->device));
 	ReachRun r;
 	reach_run_params(hm, ropt, opt, &r);
@@ -151,14 +139,8 @@ extern "C" SMHV_API int smhv_reach_map(smhv_ctx *c, const smhv_heightmap *hm, co
 	const size_t cls_off = 256u, cls_bytes = classes ? (size_t)r.cls_stride : 0u, img_off = cls_off + ((cls_bytes + 255u) & ~(size_t)255u);
 	const size_t img_bytes = rgba_inout ? (size_t)r.img_stride : 0u, bytes = img_off + img_bytes;
 	std::lock_guard<std::mutex> lk(c->fire_mu);
-	if (c->fire_cap < bytes) {
-		if (c->d_fire) (void)hipFree(c->d_fire);
-		if (c->h_fire) (void)hipHostFree(c->h_fire);
-		c->d_fire = c->h_fire = nullptr; c->fire_cap = 0;
-		HIPCHK(hipMalloc((void **)&c->d_fire, bytes));
-		HIPCHK(hipHostMalloc((void **)&c->h_fire, bytes));
-		c->fire_cap = bytes;
-	}
+	rc = ctx_stage_reserve(c, bytes);
+	if (rc) return rc;
 	r.out = (smhv_reach_result *)c->d_fire;
 	r.cls = classes ? c->d_fire + cls_off : nullptr;
 	r.img = rgba_inout ? c->d_fire + img_off : nullptr;

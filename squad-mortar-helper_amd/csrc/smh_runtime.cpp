@@ -790,13 +790,36 @@ static void hm_release(smhv_heightmap *hm) {
 	delete hm;
 }
 
+// A batch's or a pipeline's reference of the heightmap its enqueued work reads: `hm` takes the slot and the previous one goes (if
+// that was the last reference, its release waits for the device, as every release of a heightmap does).
+static void hm_rebind(smhv_heightmap **slot, const smhv_heightmap *hm) {
+	smhv_heightmap *h = const_cast<smhv_heightmap *>(hm);
+	if (*slot == h) return;
+	hm_retain(h);
+	smhv_heightmap *old = *slot;
+	*slot = h;
+	hm_release(old);
+}
+
+static inline float view_scale(float s) { return s == 0.0f ? 1.0f : s; }   // a zero viewport scale means 1
+
 static smhv_firing_options firing_opts(const smhv_firing_options *opt) {
 	smhv_firing_options o{};
 	o.size = sizeof o;
 	if (opt) { o.flags = opt->flags; o.viewport_scale[0] = opt->viewport_scale[0]; o.viewport_scale[1] = opt->viewport_scale[1];
 	           o.viewport_top_left[0] = opt->viewport_top_left[0]; o.viewport_top_left[1] = opt->viewport_top_left[1]; }
-	if (o.viewport_scale[0] == 0.0f) o.viewport_scale[0] = 1.0f;     // a zero scale means 1
-	if (o.viewport_scale[1] == 0.0f) o.viewport_scale[1] = 1.0f;
+	o.viewport_scale[0] = view_scale(o.viewport_scale[0]);
+	o.viewport_scale[1] = view_scale(o.viewport_scale[1]);
+	return o;
+}
+
+// the firing options of a render's viewport (the labels and the reach map solve in the window the image was drawn in)
+static smhv_firing_options firing_opts_of_render(const smhv_render_options *ropt) {
+	smhv_firing_options o{};
+	o.size = sizeof o;
+	o.flags = (ropt->flags & SMHV_RENDER_BOUNDS_OFFSET) ? SMHV_FIRING_BOUNDS_OFFSET : 0u;
+	o.viewport_scale[0] = ropt->viewport_scale[0]; o.viewport_scale[1] = ropt->viewport_scale[1];
+	o.viewport_top_left[0] = ropt->viewport_top_left[0]; o.viewport_top_left[1] = ropt->viewport_top_left[1];
 	return o;
 }
 
@@ -809,23 +832,62 @@ static void firing_run_params(const smhv_heightmap *hm, const smhv_firing_option
 	}
 	// (every run's and call's block is built here: a zero scale means 1 also for a batch nobody called set_firing on)
 	r->flags = o->flags;
-	r->sw = o->viewport_scale[0] == 0.0f ? 1.0f : o->viewport_scale[0];
-	r->sh = o->viewport_scale[1] == 0.0f ? 1.0f : o->viewport_scale[1];
+	r->sw = view_scale(o->viewport_scale[0]);
+	r->sh = view_scale(o->viewport_scale[1]);
 	r->tx = o->viewport_top_left[0]; r->ty = o->viewport_top_left[1];
 }
 
 static void firing_bind(smhv_batch *b, smhv_heightmap *hm, const smhv_firing_options *opt) {
 	b->fire_opt = firing_opts(opt);
-	if (b->fire_hm == hm) return;
-	hm_retain(hm);
-	smhv_heightmap *old = b->fire_hm;
-	b->fire_hm = hm;
-	hm_release(old);
+	hm_rebind(&b->fire_hm, hm);
 }
 
 static int check_firing_options(const smhv_firing_options *opt) {
 	if (opt && opt->size != 0u && opt->size < sizeof(smhv_firing_options)) return fail(SMHV_E_INVALID, "smhv_firing_options.size %u < %zu", opt->size, sizeof(smhv_firing_options));
 	if (opt && (opt->flags & ~SMHV_FIRING_BOUNDS_OFFSET)) return fail(SMHV_E_INVALID, "unknown firing flags 0x%x", opt->flags);
+	return SMHV_OK;
+}
+
+// ---- argument checks and plumbing that the entry points of every family share (`what`: the entry point's name in the message) ----
+static int check_frames(const smhv_batch *b, uint32_t first, uint32_t n, const char *what) {
+	if (n == 0u || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "%s: frames [%u, %u + %u) of a batch of %u", what, first, first, n, b->max_frames);
+	return SMHV_OK;
+}
+
+// `thing` (a heightmap, a feed) and its `owner` (the batch, the context, the pipeline) live on one device
+static int check_device(int thing_device, int device, const char *what, const char *thing, const char *owner) {
+	if (thing_device != device) return fail(SMHV_E_INVALID, "%s: the %s lives on device %d, the %s on %d", what, thing, thing_device, owner, device);
+	return SMHV_OK;
+}
+static int check_hm_device(const smhv_heightmap *hm, int device, const char *what, const char *owner) {
+	return hm ? check_device(hm->ctx->device, device, what, "heightmap", owner) : SMHV_OK;
+}
+
+// a text or tint pass draws into the images of the batch's most recent render: its window is that render's
+static int check_window_is_last_render(const smhv_batch *b, const smhv_render_options *ropt, const char *what) {
+	if (ropt->out_w != b->render_w || ropt->out_h != b->render_h)
+		return fail(SMHV_E_STATE, "%s: a window of %u x %u, the batch's most recent render is %u x %u", what, ropt->out_w, ropt->out_h, b->render_w, b->render_h);
+	return SMHV_OK;
+}
+
+// The context's staging block (d_fire / h_fire), at least `bytes` long; the caller holds fire_mu.  A failure leaves no block.
+static int ctx_stage_reserve(smhv_ctx *c, size_t bytes) {
+	if (c->fire_cap < bytes) {
+		if (c->d_fire) (void)hipFree(c->d_fire);
+		if (c->h_fire) (void)hipHostFree(c->h_fire);
+		c->d_fire = c->h_fire = nullptr; c->fire_cap = 0;
+		HIPCHK(hipMalloc((void **)&c->d_fire, bytes));
+		HIPCHK(hipHostMalloc((void **)&c->h_fire, bytes));
+		c->fire_cap = bytes;
+	}
+	return SMHV_OK;
+}
+
+// rows [first, first + n) of a batch's result slab to the host, after everything enqueued on the device has finished
+static int batch_read_rows(smhv_batch *b, const void *src, size_t row_bytes, uint32_t first, uint32_t n, void *out) {
+	HIPCHK(hipSetDevice(b->ctx->device));
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(out, (const uint8_t *)src + (size_t)first * row_bytes, row_bytes * n, hipMemcpyDeviceToHost));
 	return SMHV_OK;
 }
 
@@ -2455,6 +2517,17 @@ extern "C" SMHV_API int smhv_find_minimap(smhv_ctx *c, uint32_t rect[4], int *fo
 	return SMHV_OK;
 }
 
+// A debug view of the current frame: its size (the bottom right quadrant's or the map's), and the image of this moment drawn into
+// device memory on the context's stream -- smhv_get_debug_view's, the map of a per-call render with layers, smhv_feed_frame_view's Map.
+static void debug_view_size(const Geom &g, int which, uint32_t *w, uint32_t *h) {
+	const bool brq = which == SMHV_VIEW_OCR_INPUT || which == SMHV_VIEW_FIND_SCALES_INPUT || which == SMHV_VIEW_CROPPED_BRQ;
+	*w = brq ? g.qw : g.rw; *h = brq ? g.qh : g.rh;
+}
+static hipError_t ctx_debug_view(smhv_ctx *c, int which, uint8_t *d_rgba) {
+	Buffers bf = make_buffers(c->fb, c->frame_ptr, 0);
+	return launch_debug_view(c->fb->g, bf, 0, which, c->isolated ? 1 : 0, d_rgba, c->s_main);
+}
+
 extern "C" SMHV_API int smhv_get_debug_view(smhv_ctx *c, int which, uint8_t *rgba, uint32_t *w, uint32_t *h) {
 	TraitTimer tt_(c, SMHV_T_GET_DEBUG_VIEW);
 	if (!c) return fail(SMHV_E_INVALID, "null context");
@@ -2462,17 +2535,14 @@ extern "C" SMHV_API int smhv_get_debug_view(smhv_ctx *c, int which, uint8_t *rgb
 	if (which < 0 || which > SMHV_VIEW_CROPPED_BRQ) return fail(SMHV_E_INVALID, "unknown debug view %d", which);
 	if (!c->have_frame || !c->fb) return fail(SMHV_E_INVALID, "get_debug_view called before load_frame");
 	HIPCHK(hipSetDevice(c->device));
-	smhv_batch *b = c->fb;
-	const Geom &g = b->g;
-	const bool brq = which == SMHV_VIEW_OCR_INPUT || which == SMHV_VIEW_FIND_SCALES_INPUT || which == SMHV_VIEW_CROPPED_BRQ;
-	const uint32_t vw = brq ? g.qw : g.rw, vh = brq ? g.qh : g.rh;
+	uint32_t vw, vh;
+	debug_view_size(c->fb->g, which, &vw, &vh);
 	if (w) *w = vw;
 	if (h) *h = vh;
 	if (!rgba) return SMHV_OK;
 	uint8_t *d_tmp = nullptr;
 	HIPCHK(hipMalloc((void **)&d_tmp, (size_t)vw * vh * 4));
-	Buffers bf = make_buffers(b, c->frame_ptr, 0);
-	hipError_t e = launch_debug_view(g, bf, 0, which, c->isolated ? 1 : 0, d_tmp, c->s_main);
+	hipError_t e = ctx_debug_view(c, which, d_tmp);
 	if (e == hipSuccess) e = hipMemcpyAsync(rgba, d_tmp, (size_t)vw * vh * 4, hipMemcpyDeviceToHost, c->s_main);
 	if (e == hipSuccess) e = hipStreamSynchronize(c->s_main);
 	(void)hipFree(d_tmp);
@@ -3171,7 +3241,8 @@ extern "C" SMHV_API int smhv_batch_set_firing(smhv_batch *b, smhv_heightmap *hm,
 	CTX_OPEN(b->ctx);
 	int rc = check_firing_options(opt);
 	if (rc) return rc;
-	if (hm && hm->ctx->device != b->ctx->device) return fail(SMHV_E_INVALID, "batch_set_firing: the heightmap lives on device %d, the batch on %d", hm->ctx->device, b->ctx->device);
+	rc = check_hm_device(hm, b->ctx->device, "batch_set_firing", "batch");
+	if (rc) return rc;
 	firing_bind(b, hm, opt);
 	return SMHV_OK;
 }
@@ -3181,24 +3252,17 @@ extern "C" SMHV_API int smhv_pipeline_set_firing(smhv_pipeline *p, smhv_heightma
 	CTX_OPEN(p->ctx);
 	int rc = check_firing_options(opt);
 	if (rc) return rc;
-	if (hm && hm->ctx->device != p->ctx->device) return fail(SMHV_E_INVALID, "pipeline_set_firing: the heightmap lives on device %d, the pipeline on %d", hm->ctx->device, p->ctx->device);
+	rc = check_hm_device(hm, p->ctx->device, "pipeline_set_firing", "pipeline");
+	if (rc) return rc;
 	p->fire_opt = firing_opts(opt);
-	if (p->fire_hm != hm) {
-		hm_retain(hm);
-		smhv_heightmap *old = p->fire_hm;
-		p->fire_hm = hm;
-		hm_release(old);                                      // (the slots' batches keep their own references of what they ran with)
-	}
+	hm_rebind(&p->fire_hm, hm);                               // (the slots' batches keep their own references of what they ran with)
 	return SMHV_OK;
 }
 
 extern "C" SMHV_API int smhv_batch_read_firing(smhv_batch *b, uint32_t first, uint32_t n, smhv_firing_result *out) {
 	if (!b || !out || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_read_firing: bad arguments");
 	if (!b->d_firing) return fail(SMHV_E_STATE, "batch_read_firing: no run of this batch had SMHV_STAGE_FIRING");
-	HIPCHK(hipSetDevice(b->ctx->device));
-	HIPCHK(hipDeviceSynchronize());
-	HIPCHK(hipMemcpy(out, b->d_firing + first, sizeof(smhv_firing_result) * n, hipMemcpyDeviceToHost));
-	return SMHV_OK;
+	return batch_read_rows(b, b->d_firing, sizeof(smhv_firing_result), first, n, out);
 }
 
 extern "C" SMHV_API int smhv_batch_firing_ptr(smhv_batch *b, void **d_firing) {
@@ -3215,7 +3279,8 @@ extern "C" SMHV_API int smhv_firing_solutions(smhv_ctx *c, const smhv_line *line
 	int rc = check_firing_options(opt);
 	if (rc) return rc;
 	if (n == 0) return SMHV_OK;
-	if (hm && hm->ctx->device != c->device) return fail(SMHV_E_INVALID, "firing_solutions: the heightmap lives on device %d, the context on %d", hm->ctx->device, c->device);
+	rc = check_hm_device(hm, c->device, "firing_solutions", "context");
+	if (rc) return rc;
 	HIPCHK(hipSetDevice(c->device));
 	const smhv_firing_options o = firing_opts(opt);
 	FiringRun r;
@@ -3223,14 +3288,8 @@ extern "C" SMHV_API int smhv_firing_solutions(smhv_ctx *c, const smhv_line *line
 	const uint32_t mm0[4] = {0, 0, 0, 0};
 	const size_t in_bytes = ((sizeof(smhv_line) * (size_t)n + 255u) & ~(size_t)255u), bytes = in_bytes + sizeof(smhv_firing) * (size_t)n;
 	std::lock_guard<std::mutex> lk(c->fire_mu);
-	if (c->fire_cap < bytes) {
-		if (c->d_fire) (void)hipFree(c->d_fire);
-		if (c->h_fire) (void)hipHostFree(c->h_fire);
-		c->d_fire = c->h_fire = nullptr; c->fire_cap = 0;
-		HIPCHK(hipMalloc((void **)&c->d_fire, bytes));
-		HIPCHK(hipHostMalloc((void **)&c->h_fire, bytes));
-		c->fire_cap = bytes;
-	}
+	rc = ctx_stage_reserve(c, bytes);
+	if (rc) return rc;
 	memcpy(c->h_fire, lines, sizeof(smhv_line) * (size_t)n);
 	HIPCHK(hipMemcpyAsync(c->d_fire, c->h_fire, sizeof(smhv_line) * (size_t)n, hipMemcpyHostToDevice, c->s_main));
 	HIPCHK(launch_firing_lines(r, (const smhv_line *)c->d_fire, n, mpx ? 1u : 0u, mpx ? *mpx : 0.0, minimap ? 1u : 0u, minimap ? minimap : mm0,
@@ -3260,7 +3319,8 @@ extern "C" SMHV_API int smhv_heightmap_overlay(smhv_ctx *c, const smhv_heightmap
 	if (!hm || !rgba) return fail(SMHV_E_INVALID, "heightmap_overlay: null argument");
 	rc = check_firing_options(opt);
 	if (rc) return rc;
-	if (hm->ctx->device != c->device) return fail(SMHV_E_INVALID, "heightmap_overlay: the heightmap lives on device %d, the context on %d", hm->ctx->device, c->device);
+	rc = check_hm_device(hm, c->device, "heightmap_overlay", "context");
+	if (rc) return rc;
 	HIPCHK(hipSetDevice(c->device));
 	const smhv_firing_options o = firing_opts(opt);
 	smhv_batch *b = c->fb;
@@ -3274,402 +3334,7 @@ extern "C" SMHV_API int smhv_heightmap_overlay(smhv_ctx *c, const smhv_heightmap
 	return copy_image_d2h(c, 2, rgba, b->d_overlay, g.ui_pitch, (size_t)g.m_xoff * 4, (size_t)g.rw * 4, g.rh, c->s_main);
 }
 
-// ------------------------------------------------------------------------------------------------
-// map view: public entry points (smh_vision_hip.h; device code in smh_render.hip, k_render_map)
-// ------------------------------------------------------------------------------------------------
-#define SMH_RENDER_MAX_DIM 16384u
-static const float SMH_MAX_ZOOM = 4.0f;          // src/ui/map.rs:128-129
-static const uint32_t SMH_ZOOM_LEVELS = 10u;
-
-// MapViewport::calc (src/ui/map.rs:21-77), restated in f32.  This translation unit is compiled with -ffp-contract=off: every
-// operation below is one f32 operation.
-extern "C" SMHV_API int smhv_map_viewport_calc(float region_w, float region_h, float map_w, float map_h, uint32_t zoom, const float zoom_pos[2],
-                                               const float pan_pos[2], smhv_render_options *opt) {
-	if (!opt) return fail(SMHV_E_INVALID, "map_viewport_calc: null options");
-	const float map_ar = map_w / map_h, win_ar = region_w / region_h;
-	float size[2];
-	if (win_ar > map_ar) { size[0] = region_h * map_ar; size[1] = region_h; }
-	else { const float inv_ar = map_h / map_w; size[0] = region_w; size[1] = region_w * inv_ar; }
-	float tl[2] = {(region_w - size[0]) / 2.0f, (region_h - size[1]) / 2.0f};
-	if (zoom != 0u) {
-		const float zx = zoom_pos ? zoom_pos[0] : 0.0f, zy = zoom_pos ? zoom_pos[1] : 0.0f;
-		const float px = pan_pos ? pan_pos[0] : 0.0f, py = pan_pos ? pan_pos[1] : 0.0f;
-		const float level = (float)(zoom > 255u ? 255u : zoom);                     // (the app's level is a u8)
-		float amount = fminf(level / (float)SMH_ZOOM_LEVELS, 1.0f) * SMH_MAX_ZOOM;
-		tl[0] -= zx * size[0] * amount;
-		tl[1] -= zy * size[1] * amount;
-		tl[0] += px * (size[0] / map_w);
-		tl[1] += py * (size[1] / map_h);
-		amount += 1.0f;
-		size[0] *= amount;
-		size[1] *= amount;
-	}
-	opt->quad[0] = tl[0]; opt->quad[1] = tl[1];
-	opt->quad[2] = tl[0] + size[0]; opt->quad[3] = tl[1] + size[1];
-	opt->viewport_scale[0] = size[0] / map_w; opt->viewport_scale[1] = size[1] / map_h;
-	opt->viewport_top_left[0] = tl[0]; opt->viewport_top_left[1] = tl[1];
-	return SMHV_OK;
-}
-
-static int check_render_options(const smhv_render_options *opt, const smhv_heightmap *hm, const char *what) {
-	if (!opt) return fail(SMHV_E_INVALID, "%s: null options", what);
-	if (opt->size != sizeof(smhv_render_options)) return fail(SMHV_E_INVALID, "%s: smhv_render_options.size %u != %zu", what, opt->size, sizeof(smhv_render_options));
-	if (opt->flags & ~(SMHV_RENDER_HEIGHTMAP | SMHV_RENDER_MARKERS | SMHV_RENDER_BOUNDS_OFFSET)) return fail(SMHV_E_INVALID, "%s: unknown render flags 0x%x", what, opt->flags);
-	if (opt->out_w == 0u || opt->out_h == 0u || opt->out_w > SMH_RENDER_MAX_DIM || opt->out_h > SMH_RENDER_MAX_DIM)
-		return fail(SMHV_E_INVALID, "%s: window %u x %u (1 .. %u each)", what, opt->out_w, opt->out_h, SMH_RENDER_MAX_DIM);
-	if ((opt->flags & SMHV_RENDER_HEIGHTMAP) && !hm) return fail(SMHV_E_INVALID, "%s: SMHV_RENDER_HEIGHTMAP needs a heightmap", what);
-	for (int i = 0; i < 4; ++i)
-		if (!std::isfinite(opt->quad[i])) return fail(SMHV_E_INVALID, "%s: quad[%d] is not finite", what, i);
-	return SMHV_OK;
-}
-
-// The launch arguments of a render of frames [first, first + n) of `b` with the records at `res` (frame `first`'s), after
-// everything that can fail without the device has been checked; grows the slab.  Nothing is enqueued before this returns SMHV_OK.
-static int render_prepare(smhv_batch *b, uint32_t first, uint32_t n, const smhv_frame_result *res, const smhv_heightmap *hm, const smhv_render_options *opt,
-                          RenderRun *r) {
-	const Geom &g = b->g;
-	const bool use_hm = (opt->flags & SMHV_RENDER_HEIGHTMAP) != 0u;
-	const uint32_t *lut = nullptr;
-	if (use_hm) {
-		if (hm->ctx->device != b->ctx->device) return fail(SMHV_E_INVALID, "render: the heightmap lives on device %d, the batch on %d", hm->ctx->device, b->ctx->device);
-		int rc = hm_lut(hm, &lut);
-		if (rc) return rc;
-	}
-	const uint64_t stride = (uint64_t)opt->out_w * opt->out_h * 4u;
-	const uint64_t need = stride * (uint64_t)b->max_frames;       // the whole batch: rendering it in parts keeps the earlier parts
-	(void)first; (void)n;
-	if (!b->ev_render) HIPCHK(hipEventCreateWithFlags(&b->ev_render, hipEventDisableTiming));
-	if (b->render_cap < need) {
-		if (b->d_render) {
-			HIPCHK(wait_event(b->ev_render));                    // the previous render has left the old slab
-			(void)hipFree(b->d_render);
-			b->d_render = nullptr; b->render_cap = 0;
-		}
-		hipError_t e = hipMalloc((void **)&b->d_render, (size_t)need);
-		if (e != hipSuccess) { b->d_render = nullptr; return fail(SMHV_E_HIP, "render slab (%llu bytes): %s", (unsigned long long)need, hipGetErrorString(e)); }
-		b->render_cap = (size_t)need;
-	}
-	b->render_w = opt->out_w; b->render_h = opt->out_h;
-	memset(r, 0, sizeof *r);
-	r->ui = b->d_ui + (size_t)first * g.ui_stride;
-	r->out = b->d_render + (size_t)first * stride;
-	r->aux = b->d_aux + first;
-	r->res = res;
-	r->out_stride = stride;
-	if (use_hm) {
-		r->hm = hm->d; r->lut = lut; r->hm_w = hm->w; r->hm_h = hm->h;
-		r->lut16 = (const uint16_t *)(lut + SMH_HM_LUT_ENTRIES + 4u);
-		r->b0x = (float)hm->bounds[0]; r->b0y = (float)hm->bounds[1];
-	}
-	r->flags = opt->flags;
-	r->out_w = opt->out_w; r->out_h = opt->out_h;
-	r->ql = opt->quad[0]; r->qt = opt->quad[1]; r->qr = opt->quad[2]; r->qb = opt->quad[3];
-	r->sw = opt->viewport_scale[0] == 0.0f ? 1.0f : opt->viewport_scale[0];
-	r->sh = opt->viewport_scale[1] == 0.0f ? 1.0f : opt->viewport_scale[1];
-	r->tx = opt->viewport_top_left[0]; r->ty = opt->viewport_top_left[1];
-	memcpy(&r->bg, opt->background, 4);
-	return SMHV_OK;
-}
-
-// the batch's reference of the heightmap its enqueued render reads (the previous one goes: if that was the last reference, its
-// release waits for the device, as every release of a heightmap does)
-static void render_bind(smhv_batch *b, const smhv_heightmap *hm) {
-	smhv_heightmap *h = const_cast<smhv_heightmap *>(hm);
-	if (b->render_hm == h) return;
-	hm_retain(h);
-	smhv_heightmap *old = b->render_hm;
-	b->render_hm = h;
-	hm_release(old);
-}
-
-extern "C" SMHV_API int smhv_batch_render(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_render_options *opt, void *stream) {
-	if (!b) return fail(SMHV_E_INVALID, "batch_render: null batch");
-	CTX_OPEN(b->ctx);
-	int rc = check_render_options(opt, hm, "batch_render");
-	if (rc) return rc;
-	if (n == 0u || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_render: frames [%u, %u + %u) of a batch of %u", first, first, n, b->max_frames);
-	if (!b->ui_written) return fail(SMHV_E_STATE, "batch_render: no run of this batch has produced a ui_map (SMHV_STAGE_UI_MAP)");
-	HIPCHK(hipSetDevice(b->ctx->device));
-	const bool use_hm = (opt->flags & SMHV_RENDER_HEIGHTMAP) != 0u;
-	RenderRun r;
-	rc = render_prepare(b, first, n, b->d_results + first, use_hm ? hm : nullptr, opt, &r);
-	if (rc) return rc;
-	render_bind(b, use_hm ? hm : nullptr);
-	hipStream_t s = (hipStream_t)stream;
-	rc = batch_materialize_ui(b, s);                           // the RGBA slab is made when it is read
-	if (rc) return rc;
-	// at most 65,535 frames per launch (the grid's third dimension)
-	for (uint32_t done = 0; done < n;) {
-		const uint32_t k = std::min(n - done, 65535u);
-		RenderRun part = r;
-		part.ui += (size_t)done * b->g.ui_stride; part.out += (size_t)done * r.out_stride; part.aux += done; part.res += done;
-		HIPCHK(launch_render_map(b->g, part, k, s));
-		done += k;
-	}
-	HIPCHK(hipEventRecord(b->ev_render, s));
-	return SMHV_OK;
-}
-
-extern "C" SMHV_API int smhv_batch_render_ptr(smhv_batch *b, void **d_images, uint64_t *stride) {
-	if (!b || !d_images) return fail(SMHV_E_INVALID, "batch_render_ptr: null argument");
-	if (!b->d_render) return fail(SMHV_E_STATE, "batch_render_ptr: this batch has not rendered");
-	*d_images = b->d_render;
-	if (stride) *stride = (uint64_t)b->render_w * b->render_h * 4u;
-	return SMHV_OK;
-}
-
-extern "C" SMHV_API int smhv_batch_render_size(smhv_batch *b, uint32_t *out_w, uint32_t *out_h) {
-	if (!b || !out_w || !out_h) return fail(SMHV_E_INVALID, "batch_render_size: null argument");
-	if (!b->d_render) return fail(SMHV_E_STATE, "batch_render_size: this batch has not rendered");
-	*out_w = b->render_w; *out_h = b->render_h;
-	return SMHV_OK;
-}
-
-extern "C" SMHV_API int smhv_batch_read_render(smhv_batch *b, uint32_t frame, uint8_t *rgba) {
-	if (!b || !rgba || frame >= b->max_frames) return fail(SMHV_E_INVALID, "batch_read_render: bad arguments");
-	if (!b->d_render) return fail(SMHV_E_STATE, "batch_read_render: this batch has not rendered");
-	const size_t stride = (size_t)b->render_w * b->render_h * 4u;
-	if (((size_t)frame + 1u) * stride > b->render_cap) return fail(SMHV_E_INVALID, "batch_read_render: frame %u lies beyond the render slab", frame);
-	HIPCHK(hipSetDevice(b->ctx->device));
-	HIPCHK(hipDeviceSynchronize());
-	HIPCHK(hipMemcpy(rgba, b->d_render + (size_t)frame * stride, stride, hipMemcpyDeviceToHost));
-	return SMHV_OK;
-}
-
-// The current frame: frame 0 of the single-frame batch's ui slab (crop_to_map's pass), the rectangle of crop_to_map's walk (the
-// minimap's own record slot, 3), the caller's lines through the context's pinned staging; drawn into that batch's render slab on
-// the context's stream and copied out.
-extern "C" SMHV_API int smhv_render_map(smhv_ctx *c, const smhv_heightmap *hm, const smhv_render_options *opt, const smhv_line *lines, uint32_t n_lines,
-                                        uint8_t *rgba) {
-	int rc = require_open(c, "render_map");
-	if (rc) return rc;
-	CTX_OPEN(c);
-	if (!rgba || (n_lines && !lines)) return fail(SMHV_E_INVALID, "render_map: null argument");
-	if (n_lines > SMHV_RENDER_MAX_LINES) return fail(SMHV_E_INVALID, "render_map: %u lines (at most %u)", n_lines, SMHV_RENDER_MAX_LINES);
-	rc = check_render_options(opt, hm, "render_map");
-	if (rc) return rc;
-	HIPCHK(hipSetDevice(c->device));
-	smhv_batch *b = c->fb;
-	const bool use_hm = (opt->flags & SMHV_RENDER_HEIGHTMAP) != 0u;
-	std::lock_guard<std::mutex> lk(c->fire_mu);
-	RenderRun r;
-	rc = render_prepare(b, 0, 1, b->d_results + 3, use_hm ? hm : nullptr, opt, &r);
-	if (rc) return rc;
-	const size_t line_bytes = sizeof(smhv_line) * (size_t)SMHV_RENDER_MAX_LINES;
-	if (c->fire_cap < line_bytes) {
-		if (c->d_fire) (void)hipFree(c->d_fire);
-		if (c->h_fire) (void)hipHostFree(c->h_fire);
-		c->d_fire = c->h_fire = nullptr; c->fire_cap = 0;
-		HIPCHK(hipMalloc((void **)&c->d_fire, line_bytes));
-		HIPCHK(hipHostMalloc((void **)&c->h_fire, line_bytes));
-		c->fire_cap = line_bytes;
-	}
-	if (n_lines && (opt->flags & SMHV_RENDER_MARKERS)) {
-		memcpy(c->h_fire, lines, sizeof(smhv_line) * (size_t)n_lines);
-		HIPCHK(hipMemcpyAsync(c->d_fire, c->h_fire, sizeof(smhv_line) * (size_t)n_lines, hipMemcpyHostToDevice, c->s_main));
-		r.lines = (const smhv_line *)c->d_fire; r.n_lines = n_lines;
-	} else
-		r.flags &= ~SMHV_RENDER_MARKERS;                      // (no explicit lines: none are drawn, whatever the spare record holds)
-	HIPCHK(launch_render_map(b->g, r, 1, c->s_main));
-	HIPCHK(hipEventRecord(b->ev_render, c->s_main));
-	std::lock_guard<std::mutex> lk2(c->mu);                   // (staging slot 2: the batch read-back's)
-	return copy_image_d2h(c, 2, rgba, b->d_render, (size_t)r.out_stride / opt->out_h, 0, (size_t)opt->out_w * 4, opt->out_h, c->s_main);
-}
-
-// ---- the map view with layers (smh_vision_hip.h, "map view: layers"; k_render_map_layers) ----
-static int check_render_layers(const smhv_render_layers *ly, const char *what) {
-	if (!ly) return fail(SMHV_E_INVALID, "%s: null layers", what);
-	if (ly->size != sizeof(smhv_render_layers)) return fail(SMHV_E_INVALID, "%s: smhv_render_layers.size %u != %zu", what, ly->size, sizeof(smhv_render_layers));
-	if (ly->flags & ~SMHV_LAYER_MINIMAP_BOUNDS) return fail(SMHV_E_INVALID, "%s: unknown layer flags 0x%x", what, ly->flags);
-	if (ly->map_source > (uint32_t)SMHV_VIEW_CROPPED_BRQ) return fail(SMHV_E_INVALID, "%s: unknown map source %u", what, ly->map_source);
-	if (ly->n_prims > SMHV_RENDER_MAX_PRIMS) return fail(SMHV_E_INVALID, "%s: %u prims (at most %u)", what, ly->n_prims, SMHV_RENDER_MAX_PRIMS);
-	if (ly->n_prims && !ly->prims) return fail(SMHV_E_INVALID, "%s: %u prims and a null pointer", what, ly->n_prims);
-	for (uint32_t i = 0; i < ly->n_prims; ++i) {
-		const smhv_render_prim &p = ly->prims[i];
-		if ((p.kind & ~(0xFFu | SMHV_PRIM_FOREGROUND | SMHV_PRIM_SHIFT1)) || (p.kind & 0xFFu) > SMHV_PRIM_RECT)
-			return fail(SMHV_E_INVALID, "%s: prim %u has the unknown kind 0x%x", what, i, p.kind);
-		if (p.rgba[3] != 255u) return fail(SMHV_E_INVALID, "%s: prim %u has alpha %u (255 only)", what, i, p.rgba[3]);
-	}
-	return SMHV_OK;
-}
-
-// The prims of a call on their way to the device: the list is split in paint order -- those below the marker lines, then the
-// foreground ones, each part in list order -- into the batch's pinned staging and copied on `s`.  Waits (host) for the previous
-// call's copy to have read the staging.  Fills y->prims, n_below, n_fg.
-static int render_upload_prims(smhv_batch *b, const smhv_render_layers *ly, RenderLayersRun *y, hipStream_t s) {
-	if (ly->n_prims == 0u) return SMHV_OK;
-	const size_t cap = sizeof(smhv_render_prim) * (size_t)SMHV_RENDER_MAX_PRIMS;
-	if (!b->h_prims) HIPCHK(hipHostMalloc((void **)&b->h_prims, cap));
-	if (!b->d_prims) HIPCHK(hipMalloc((void **)&b->d_prims, cap));
-	if (!b->ev_prims) HIPCHK(hipEventCreateWithFlags(&b->ev_prims, hipEventDisableTiming));
-	else HIPCHK(wait_event(b->ev_prims));
-	uint32_t k = 0;
-	for (uint32_t pass = 0; pass < 2u; ++pass) {
-		for (uint32_t i = 0; i < ly->n_prims; ++i)
-			if (((ly->prims[i].kind & SMHV_PRIM_FOREGROUND) != 0u) == (pass == 1u)) b->h_prims[k++] = ly->prims[i];
-		if (pass == 0u) y->n_below = k;
-	}
-	y->n_fg = k - y->n_below;
-	y->prims = b->d_prims;
-	HIPCHK(hipMemcpyAsync(b->d_prims, b->h_prims, sizeof(smhv_render_prim) * (size_t)k, hipMemcpyHostToDevice, s));
-	HIPCHK(hipEventRecord(b->ev_prims, s));
-	return SMHV_OK;
-}
-
-extern "C" SMHV_API int smhv_batch_render_layers(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_render_options *opt,
-                                                 const smhv_render_layers *layers, void *stream) {
-	if (!b) return fail(SMHV_E_INVALID, "batch_render_layers: null batch");
-	CTX_OPEN(b->ctx);
-	int rc = check_render_options(opt, hm, "batch_render_layers");
-	if (rc) return rc;
-	rc = check_render_layers(layers, "batch_render_layers");
-	if (rc) return rc;
-	if (n == 0u || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_render_layers: frames [%u, %u + %u) of a batch of %u", first, first, n, b->max_frames);
-	if (!b->ui_written) return fail(SMHV_E_STATE, "batch_render_layers: no run of this batch has produced a ui_map (SMHV_STAGE_UI_MAP)");
-	const Geom &g = b->g;
-	RenderLayersRun y{};
-	y.flags = layers->flags;
-	y.src_mode = SMH_RND_SRC_UI; y.src_w = g.rw; y.src_h = g.rh;
-	switch ((int)layers->map_source) {
-	case SMHV_VIEW_NONE: break;
-	case SMHV_VIEW_OCR_INPUT:
-	case SMHV_VIEW_FIND_SCALES_INPUT: {
-		const bool ocr = layers->map_source == (uint32_t)SMHV_VIEW_OCR_INPUT;
-		if (!(ocr ? b->ocr_written : b->scales_written))
-			return fail(SMHV_E_STATE, "batch_render_layers: no run of this batch has produced the %s image", ocr ? "OCR input (SMHV_STAGE_OCR)" : "scales input (SMHV_STAGE_SCALES with anchors)");
-		y.src_mode = SMH_RND_SRC_GRAY; y.src = (ocr ? b->d_ocr : b->d_scales) + (size_t)first * g.ocr_stride;
-		y.src_pitch = g.ocr_pitch; y.src_stride = g.ocr_stride; y.src_xoff = g.q_xoff; y.src_w = g.qw; y.src_h = g.qh;
-		break;
-	}
-	case SMHV_VIEW_LSD_INPUT:
-		if (!b->mask_written) return fail(SMHV_E_STATE, "batch_render_layers: no run of this batch has produced the marker mask (SMHV_STAGE_MARKERS)");
-		y.src_mode = SMH_RND_SRC_GRAY; y.src = b->d_mask + (size_t)first * g.mask_stride;
-		y.src_pitch = g.mask_pitch; y.src_stride = g.mask_stride; y.src_xoff = g.m_xoff;
-		break;
-	default:                                                   // SMHV_VIEW_LSD_PREPROCESS, SMHV_VIEW_CROPPED_BRQ: the colour ui_map
-		if (b->ui_gray) return fail(SMHV_E_STATE, "batch_render_layers: the batch's ui_map is grayscale, map source %u needs the colour one", layers->map_source);
-		if (layers->map_source == (uint32_t)SMHV_VIEW_CROPPED_BRQ) {
-			y.src_mode = SMH_RND_SRC_CROPPED; y.src_w = g.rw / 2u; y.src_h = g.rh / 2u;
-			if (y.src_w == 0u || y.src_h == 0u) return fail(SMHV_E_STATE, "batch_render_layers: the map has no bottom right quarter");
-		} else y.src_mode = SMH_RND_SRC_PREPROCESS;
-		break;
-	}
-	HIPCHK(hipSetDevice(b->ctx->device));
-	const bool use_hm = (opt->flags & SMHV_RENDER_HEIGHTMAP) != 0u;
-	RenderRun r;
-	rc = render_prepare(b, first, n, b->d_results + first, use_hm ? hm : nullptr, opt, &r);
-	if (rc) return rc;
-	hipStream_t s = (hipStream_t)stream;
-	if (layers->map_source == (uint32_t)SMHV_VIEW_LSD_INPUT) {  // the mask as bytes is made when it is read
-		rc = batch_materialize_mask(b, s);
-		if (rc) return rc;
-	}
-	rc = batch_materialize_ui(b, s);                           // ... and so is the RGBA ui slab
-	if (rc) return rc;
-	rc = render_upload_prims(b, layers, &y, s);
-	if (rc) return rc;
-	render_bind(b, use_hm ? hm : nullptr);
-	for (uint32_t done = 0; done < n;) {                       // at most 65,535 frames per launch (the grid's third dimension)
-		const uint32_t k = std::min(n - done, 65535u);
-		RenderRun part = r;
-		part.ui += (size_t)done * g.ui_stride; part.out += (size_t)done * r.out_stride; part.aux += done; part.res += done;
-		RenderLayersRun yp = y;
-		if (yp.src) yp.src += (size_t)done * y.src_stride;
-		HIPCHK(launch_render_map_layers(g, part, yp, k, s));
-		done += k;
-	}
-	HIPCHK(hipEventRecord(b->ev_render, s));
-	return SMHV_OK;
-}
-
-extern "C" SMHV_API int smhv_render_map_layers(smhv_ctx *c, const smhv_heightmap *hm, const smhv_render_options *opt, const smhv_render_layers *layers,
-                                               const smhv_line *lines, uint32_t n_lines, uint8_t *rgba) {
-	int rc = require_open(c, "render_map_layers");
-	if (rc) return rc;
-	CTX_OPEN(c);
-	if (!rgba || (n_lines && !lines)) return fail(SMHV_E_INVALID, "render_map_layers: null argument");
-	if (n_lines > SMHV_RENDER_MAX_LINES) return fail(SMHV_E_INVALID, "render_map_layers: %u lines (at most %u)", n_lines, SMHV_RENDER_MAX_LINES);
-	rc = check_render_options(opt, hm, "render_map_layers");
-	if (rc) return rc;
-	rc = check_render_layers(layers, "render_map_layers");
-	if (rc) return rc;
-	HIPCHK(hipSetDevice(c->device));
-	smhv_batch *b = c->fb;
-	const Geom &g = b->g;
-	const bool use_hm = (opt->flags & SMHV_RENDER_HEIGHTMAP) != 0u;
-	std::lock_guard<std::mutex> lk(c->fire_mu);
-	RenderRun r;
-	rc = render_prepare(b, 0, 1, b->d_results + 3, use_hm ? hm : nullptr, opt, &r);
-	if (rc) return rc;
-	RenderLayersRun y{};
-	y.flags = layers->flags;
-	y.src_mode = SMH_RND_SRC_UI; y.src_w = g.rw; y.src_h = g.rh;
-	uint8_t *d_view = nullptr;
-	if (layers->map_source != (uint32_t)SMHV_VIEW_NONE) {
-		// U = smhv_get_debug_view's image of this moment: drawn by its kernel into device memory and sampled there
-		const int which = (int)layers->map_source;
-		const bool brq = which == SMHV_VIEW_OCR_INPUT || which == SMHV_VIEW_FIND_SCALES_INPUT || which == SMHV_VIEW_CROPPED_BRQ;
-		y.src_w = brq ? g.qw : g.rw; y.src_h = brq ? g.qh : g.rh;
-		HIPCHK(hipMalloc((void **)&d_view, (size_t)y.src_w * y.src_h * 4u));
-		Buffers bf = make_buffers(b, c->frame_ptr, 0);
-		hipError_t e = launch_debug_view(g, bf, 0, which, c->isolated ? 1 : 0, d_view, c->s_main);
-		if (e != hipSuccess) { (void)hipFree(d_view); return fail(SMHV_E_HIP, "render_map_layers: debug view: %s", hipGetErrorString(e)); }
-		y.src_mode = SMH_RND_SRC_RGBA; y.src = d_view; y.src_pitch = (uint64_t)y.src_w * 4u;
-	}
-	const auto run = [&]() -> int {
-		const size_t line_bytes = sizeof(smhv_line) * (size_t)SMHV_RENDER_MAX_LINES;
-		if (c->fire_cap < line_bytes) {
-			if (c->d_fire) (void)hipFree(c->d_fire);
-			if (c->h_fire) (void)hipHostFree(c->h_fire);
-			c->d_fire = c->h_fire = nullptr; c->fire_cap = 0;
-			HIPCHK(hipMalloc((void **)&c->d_fire, line_bytes));
-			HIPCHK(hipHostMalloc((void **)&c->h_fire, line_bytes));
-			c->fire_cap = line_bytes;
-		}
-		if (n_lines && (opt->flags & SMHV_RENDER_MARKERS)) {
-			memcpy(c->h_fire, lines, sizeof(smhv_line) * (size_t)n_lines);
-			HIPCHK(hipMemcpyAsync(c->d_fire, c->h_fire, sizeof(smhv_line) * (size_t)n_lines, hipMemcpyHostToDevice, c->s_main));
-			r.lines = (const smhv_line *)c->d_fire; r.n_lines = n_lines;
-		} else
-			r.flags &= ~SMHV_RENDER_MARKERS;                  // (no explicit lines: none are drawn, whatever the spare record holds)
-		int rc2 = render_upload_prims(b, layers, &y, c->s_main);
-		if (rc2) return rc2;
-		HIPCHK(launch_render_map_layers(g, r, y, 1, c->s_main));
-		HIPCHK(hipEventRecord(b->ev_render, c->s_main));
-		std::lock_guard<std::mutex> lk2(c->mu);               // (staging slot 2: the batch read-back's)
-		return copy_image_d2h(c, 2, rgba, b->d_render, (size_t)r.out_stride / opt->out_h, 0, (size_t)opt->out_w * 4, opt->out_h, c->s_main);
-	};
-	rc = run();
-	if (d_view) {
-		if (rc) (void)hipStreamSynchronize(c->s_main);         // (whatever was enqueued has left the view before it goes)
-		(void)hipFree(d_view);
-	}
-	return rc;
-}
-
-extern "C" SMHV_API int smhv_debug_render_form(uint32_t form) {
-	if (form > 3u) return fail(SMHV_E_INVALID, "render form %u (0 = the rule, 1 = gathers, 2 = LDS staging, 3 = the colour table in LDS)", form);
-	render_set_form(form);
-	return SMHV_OK;
-}
-
-extern "C" SMHV_API int smhv_debug_render_rule(uint32_t map_w, uint32_t map_h, float sw, float sh, uint32_t hm_w, uint32_t hm_h, float *ratio, float *switch_ratio,
-                                               uint32_t *lds_texels, uint32_t *form) {
-	if (!map_w || !map_h || !hm_w || !hm_h) return fail(SMHV_E_INVALID, "render_rule: zero dimension");
-	Geom g{};
-	g.rw = map_w; g.rh = map_h;
-	RenderRun r{};
-	r.sw = sw == 0.0f ? 1.0f : sw; r.sh = sh == 0.0f ? 1.0f : sh; r.hm_w = hm_w; r.hm_h = hm_h;
-	float ra = 0.0f;
-	uint32_t tx = 0;
-	const uint32_t f = render_rule(g, r, &tx, &ra);
-	if (ratio) *ratio = ra;
-	if (switch_ratio) *switch_ratio = render_switch_ratio();
-	if (lds_texels) *lds_texels = tx;
-	if (form) *form = f;
-	return SMHV_OK;
-}
-
+#include "smh_render.inc"
 #include "smh_feed.inc"
 #include "smh_labels.inc"
 #include "smh_debugtext.inc"

@@ -63,14 +63,15 @@ extern "C" SMHV_API int smhv_batch_video(smhv_batch *b, uint32_t source, uint32_
 	if (!b) return fail(SMHV_E_INVALID, "batch_video: null batch");
 	CTX_OPEN(b->ctx);
 	if (source != SMHV_VIDEO_RENDER && source != SMHV_VIDEO_UI_MAP) return fail(SMHV_E_INVALID, "batch_video: unknown source %u", source);
-	if (n == 0u || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_video: frames [%u, %u + %u) of a batch of %u", first, first, n, b->max_frames);
+	int rc = check_frames(b, first, n, "batch_video");
+	if (rc) return rc;
 	const Geom &g = b->g;
 	const bool render = source == SMHV_VIDEO_RENDER;
 	if (render && !b->d_render) return fail(SMHV_E_STATE, "batch_video: this batch has not rendered");
 	if (!render && !b->ui_written) return fail(SMHV_E_STATE, "batch_video: no run of this batch has produced a ui_map (SMHV_STAGE_UI_MAP)");
 	YuvDesc d;
 	YuvOutRun run;
-	int rc = yuv_out_prepare("batch_video", n, render ? b->render_w : g.rw, render ? b->render_h : g.rh, pixels, d_dst, layout, &d, &run);
+	rc = yuv_out_prepare("batch_video", n, render ? b->render_w : g.rw, render ? b->render_h : g.rh, pixels, d_dst, layout, &d, &run);
 	if (rc) return rc;
 	HIPCHK(hipSetDevice(b->ctx->device));
 	hipStream_t s = (hipStream_t)stream;
