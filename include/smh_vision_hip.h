@@ -1204,6 +1204,124 @@ SMHV_API int smhv_batch_reach_ptr(smhv_batch *b, void **d_reach);
 SMHV_API int smhv_reach_map(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_reach_options *opt, const double *mpx,
                             const uint32_t minimap[4], uint8_t *rgba_inout, uint8_t *classes, smhv_reach_result *result);
 
+/* ---- terrain clearance: does a shell's arc clear the heightmap on its way ----------------------------------------------------
+ * The firing solutions and the reach map read the heightmap at the two end points only.  This pass looks at what lies between them:
+ * it samples the heightmap along the line and holds the high-angle arc (the one mortar_mils' elevation belongs to) and the straight
+ * sight line against the terrain.  The reference computes no such thing; the arithmetic is "firing solutions"' alone.  Every
+ * operation is one IEEE f64 operation, left to right, unfused; V^2, V^4, g are the constants of "firing solutions".
+ * A verdict exists only on the heightmap branch of "firing solutions": a minimap rectangle, a heightmap, and all four rounded end-point
+ *   coordinates inside it.  Everything else (the scales branch too: it has no terrain) is status NONE, a record of zeros.
+ * The rule, direction 0 (firing from P0 at P1), with that branch's own values: (x0, y0), (x1, y1) = the heightmap coordinates in f64,
+ *   W x H the heightmap, d = sqrt(dx*dx + dy*dy), h0 = height(P0), h1 = height(P1), alt = h1 - h0, S = opt->samples:
+ *   1. disc = V^4 - g * (g * (d * d) + 2.0 * alt * V^2).  !(disc >= 0): OUT_OF_RANGE.  d == 0.0: CLEAR with no samples (zero counts,
+ *      first_blocked = S, min_margin = 0, min_at = 0).
+ *   2. q = (V^2 + sqrt(disc)) / (g * d), the tangent of the high angle.
+ *   3. For each interior sample k = 1 .. S - 1, t = (double)k / (double)S:
+ *        texel   sx = x0 + (x1 - x0) * t, sy = y0 + (y1 - y0) * t, each rounded half away from zero `as i32` and then clamped into
+ *                [0, W - 1] and [0, H - 1]; v = the texel there.  (Each axis depends on its own end coordinates and k alone.)
+ *        terrain z = ((double)v / 65535.0) * zscale - h0, zscale = (double)scale[2] / 0.1953125: metres over the origin.
+ *        arc     x = d * t; a = x * q - ((g * (x * x)) * (1.0 + q * q)) / (2.0 * V^2).
+ *        margin  m = a - z.  The sample blocks the arc iff m < opt->margin_m.
+ *        sight   l = alt * t.  The sample blocks the line of sight iff l < z.
+ *   4. BLOCKED iff some sample blocks the arc, else CLEAR.  first_blocked = the least blocking k (S: none), n_blocked = how many
+ *      block the arc, los_blocked = how many block the sight line.  min_margin = the least m, min_at its k: best starts at +inf and
+ *      is replaced only when m < best, so a NaN never wins and ties go to the lowest k; min_at is 0 while nothing has replaced it, and
+ *      min_margin is reported as 0 when S == 1.
+ *   An OUT_OF_RANGE line has no arc: first_blocked = S, n_blocked = 0, min_margin = 0, min_at = 0; its los_blocked is counted as above.
+ *   Direction 1 is the same rule on the line (P1, P0): end coordinates swapped, h0 := h1, alt := -alt.
+ * Profile (optional), direction 0: SMHV_CLEAR_MAX_SAMPLES + 1 floats per line, entry k = 0 .. S is (float)(((double)v / 65535.0) *
+ *   zscale) at sample k's texel -- entries 0 and S at the end points' own rounded texels -- and the entries past S are 0.  A line
+ *   without a verdict (NONE), or beyond the record's n_lines, is all zeros.  A frame is SMHV_MAX_LINES such rows.
+ * Dense (the clearance map): origin and target per window pixel are exactly the reach map's -- origin_mode, line, origin, the "no
+ *   origin" rule, the viewport and the heightmap coordinates of "reach map" -- and the rule above, direction 0, gives one byte per
+ *   pixel: the status, | SMHV_CLEAR_LOS_BLOCKED wherever the status is not NONE and some sample blocks the sight line (out-of-range
+ *   pixels included).  Paint (SMHV_CLEAR_PAINT) goes over the render slab by the reach map's integer blend: the palette entry of the
+ *   status (out_of_range, clear, blocked), then on a pixel with the LOS bit los[4]; a weight of 0 leaves the pixel as it is.  Bytes
+ *   (SMHV_CLEAR_BYTES): out_w * out_h per frame, tightly packed, into caller memory.  Summary: one smhv_clearance_map_result per
+ *   frame, cleared on the stream ahead of the kernel: valid = 1 iff the frame had an origin (else zeros), origin, count[s - 1] =
+ *   window pixels of status s = 1 .. 3, los_blocked = window pixels with the LOS bit. */
+#define SMHV_CLEAR_MAX_SAMPLES 256u
+#define SMHV_CLEAR_PAINT 1u            /* smhv_clearance_options.flags: tint the render slab (the map; per call: implied by rgba_inout) */
+#define SMHV_CLEAR_BYTES 2u            /*   ... write the status bytes (the map; per call: implied by bytes) */
+#define SMHV_CLEAR_NONE 0u             /* status */
+#define SMHV_CLEAR_OUT_OF_RANGE 1u
+#define SMHV_CLEAR_CLEAR 2u
+#define SMHV_CLEAR_BLOCKED 3u
+#define SMHV_CLEAR_LOS_BLOCKED 0x80u   /* the map's byte: | this */
+typedef struct {
+	uint32_t size;                       /*  0: sizeof(smhv_clearance_options) == 64 */
+	uint32_t flags;                      /*  4: SMHV_CLEAR_PAINT | SMHV_CLEAR_BYTES (the map only; 0: the summary alone) */
+	uint32_t samples;                    /*  8: S, 1 .. SMHV_CLEAR_MAX_SAMPLES */
+	uint32_t origin_mode;                /* 12: the map: SMHV_REACH_ORIGIN_* */
+	uint32_t line;                       /* 16: the map, _LINE_P0 / _LINE_P1: which line of the record, < SMHV_MAX_LINES */
+	uint32_t reserved0;                  /* 20 */
+	float origin[2];                     /* 24: the map, _POINT: the origin, map-ROI coordinates */
+	double margin_m;                     /* 32: metres the arc must keep over the terrain; finite, >= 0 */
+	uint8_t out_of_range[4];             /* 40: the palette: R, G, B and the blend weight a */
+	uint8_t clear[4];                    /* 44 */
+	uint8_t blocked[4];                  /* 48 */
+	uint8_t los[4];                      /* 52 */
+	uint32_t reserved[2];                /* 56 */
+} smhv_clearance_options;
+typedef struct {
+	uint32_t status;                     /*  0: SMHV_CLEAR_NONE / _OUT_OF_RANGE / _CLEAR / _BLOCKED */
+	uint32_t first_blocked;              /*  4: the least k that blocks the arc; S when there is none */
+	uint32_t n_blocked;                  /*  8 */
+	uint32_t los_blocked;                /* 12: samples that block the sight line (a count) */
+	double min_margin;                   /* 16 */
+	uint32_t min_at;                     /* 24 */
+	uint32_t reserved;                   /* 28 */
+} smhv_clearance_dir;                    /* 32 bytes */
+typedef struct { smhv_clearance_dir dir[2]; } smhv_clearance;   /* 64 bytes: [0] from p0 at p1, [1] from p1 at p0 */
+typedef struct {
+	uint32_t n_lines, reserved;          /* == the record's n_lines; lines beyond it are zero */
+	smhv_clearance line[SMHV_MAX_LINES];
+} smhv_clearance_result;
+typedef struct {
+	uint32_t valid;                      /*  0 */
+	uint32_t reserved;                   /*  4 */
+	float origin[2];                     /*  8 */
+	uint32_t count[3];                   /* 16: statuses 1 .. 3 */
+	uint32_t los_blocked;                /* 28 */
+} smhv_clearance_map_result;             /* 32 bytes */
+/* Host only.  Fills *opt: size, flags = PAINT, samples = 64, origin_mode = POINT at (0, 0), margin_m = 0 and the palette --
+ * out_of_range and clear (0, 0, 0, 0), blocked (230, 40, 40, 110), los (0, 0, 0, 70). */
+SMHV_API int smhv_clearance_defaults(smhv_clearance_options *opt);
+/* The clearance of the detected lines of frames [first, first + n), asynchronously on `stream`, from the batch's records (n_lines,
+ * the lines, the minimap rectangle): a plain batch after smhv_batch_run, or a pipeline slot's batch after smhv_pipeline_wait, for
+ * both searches.  hm (NULL: none -- NONE everywhere), fopt (NULL: defaults) as smhv_firing_solutions takes them; of opt, samples and
+ * margin_m apply (flags are checked).  d_profiles (device memory, NULL: none): n * SMHV_MAX_LINES * (SMHV_CLEAR_MAX_SAMPLES + 1)
+ * floats, the call's first frame first.  The results go to the batch's clearance slab (allocated by the first call).
+ * SMHV_E_INVALID: a wrong size, unknown flags, samples 0 or above SMHV_CLEAR_MAX_SAMPLES, a margin_m that is negative or not finite,
+ * what smhv_firing_solutions rejects in fopt, n == 0, a range beyond the batch's capacity, a heightmap on another device.  A failed
+ * call enqueues nothing.  The batch keeps a reference of hm as smhv_batch_render does. */
+SMHV_API int smhv_batch_clearance(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_firing_options *fopt,
+                                  const smhv_clearance_options *opt, void *d_profiles, void *stream);
+/* The batch's clearance slab: read is a synchronising host copy, ptr the device address (SMHV_E_STATE before the first
+ * smhv_batch_clearance) */
+SMHV_API int smhv_batch_read_clearance(smhv_batch *b, uint32_t first, uint32_t n, smhv_clearance_result *out);
+SMHV_API int smhv_batch_clearance_ptr(smhv_batch *b, void **d_clearance);
+/* The same for explicit lines, stateless like smhv_firing_solutions: n lines in map-ROI coordinates, minimap = {left, right, top,
+ * bottom} (NULL: none), hm (NULL: none), fopt (NULL: defaults).  out receives n records; profiles (host, NULL: none) n *
+ * (SMHV_CLEAR_MAX_SAMPLES + 1) floats.  Runs on the context's stream. */
+SMHV_API int smhv_clearance_lines(smhv_ctx *ctx, const smhv_line *lines, uint32_t n, const uint32_t minimap[4], const smhv_heightmap *hm,
+                                  const smhv_firing_options *fopt, const smhv_clearance_options *opt, smhv_clearance *out, float *profiles);
+/* The clearance map of frames [first, first + n), asynchronously on `stream`; everything smhv_batch_reach says about ropt, hm, PAINT
+ * (behind the batch's previous render, the most recent render's window), the records and its errors holds here, with
+ * smhv_clearance_options in place of smhv_reach_options (its errors as smhv_batch_clearance lists them, an unknown origin_mode and
+ * line >= SMHV_MAX_LINES besides) and SMHV_CLEAR_BYTES with d_bytes == NULL refused.  The summaries go to the batch's clearance-map
+ * slab (allocated by the first call). */
+SMHV_API int smhv_batch_clearance_map(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_render_options *ropt,
+                                      const smhv_clearance_options *opt, void *d_bytes, void *stream);
+SMHV_API int smhv_batch_read_clearance_map(smhv_batch *b, uint32_t first, uint32_t n, smhv_clearance_map_result *out);
+SMHV_API int smhv_batch_clearance_map_ptr(smhv_batch *b, void **d_clearance_map);
+/* The per-call path, stateless like smhv_reach_map: minimap = {left, right, top, bottom} (NULL: none), hm (NULL: none); origin_mode
+ * must be POINT.  rgba_inout (host, out_w * out_h * 4 bytes) is tinted in place; bytes (host, out_w * out_h) receives the status
+ * bytes; either may be NULL, not both; result (optional) receives the summary.  opt->flags is checked for unknown bits and
+ * otherwise not used.  Runs on the context's stream. */
+SMHV_API int smhv_clearance_map(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_clearance_options *opt,
+                                const uint32_t minimap[4], uint8_t *rgba_inout, uint8_t *bytes, smhv_clearance_map_result *result);
+
 #ifdef __cplusplus
 }
 #endif

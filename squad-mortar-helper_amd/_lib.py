@@ -144,6 +144,38 @@ class ReachResult(C.Structure):
                 ("reserved", C.c_uint32 * 2)]
 
 
+CLEAR_MAX_SAMPLES = 256
+CLEAR_PROFILE = CLEAR_MAX_SAMPLES + 1                                  # floats of a line's profile row
+CLEAR_PAINT, CLEAR_BYTES = 1, 2                                        # smhv_clearance_options.flags
+CLEAR_NONE, CLEAR_OUT_OF_RANGE, CLEAR_CLEAR, CLEAR_BLOCKED, CLEAR_LOS_BLOCKED = 0, 1, 2, 3, 0x80   # the status; the map's byte
+
+
+class ClearanceOptionsStruct(C.Structure):
+    """smhv_clearance_options: how the terrain between the ends of a line of fire is sampled and painted (64 bytes)."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("samples", C.c_uint32), ("origin_mode", C.c_uint32), ("line", C.c_uint32),
+                ("reserved0", C.c_uint32), ("origin", C.c_float * 2), ("margin_m", C.c_double), ("out_of_range", C.c_uint8 * 4), ("clear", C.c_uint8 * 4),
+                ("blocked", C.c_uint8 * 4), ("los", C.c_uint8 * 4), ("reserved", C.c_uint32 * 2)]
+
+
+class ClearanceDir(C.Structure):
+    """smhv_clearance_dir: the verdict of one direction of a line (32 bytes)."""
+    _fields_ = [("status", C.c_uint32), ("first_blocked", C.c_uint32), ("n_blocked", C.c_uint32), ("los_blocked", C.c_uint32), ("min_margin", C.c_double),
+                ("min_at", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Clearance(C.Structure):
+    _fields_ = [("dir", ClearanceDir * 2)]
+
+
+class ClearanceResult(C.Structure):
+    _fields_ = [("n_lines", C.c_uint32), ("reserved", C.c_uint32), ("line", Clearance * MAX_LINES)]
+
+
+class ClearanceMapResult(C.Structure):
+    """smhv_clearance_map_result: a frame's summary of its clearance map (32 bytes)."""
+    _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("origin", C.c_float * 2), ("count", C.c_uint32 * 3), ("los_blocked", C.c_uint32)]
+
+
 TEXT_MAX_RUNS, TEXT_MAX_BYTES, TEXT_MAX_LINES, TEXT_MAP_COORDS = 64, 64, 8, 1
 MAX_PROBES = 16
 DEBUG_DRAW_PROBES, DEBUG_MINIMAP_CAPTION = 1, 2   # smhv_debug_options.flags
@@ -352,6 +384,19 @@ SIGNATURES = {
     "smhv_batch_reach_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "smhv_reach_map": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(ReachOptionsStruct), C.POINTER(C.c_double),
                                  C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.POINTER(ReachResult)]),
+    "smhv_clearance_defaults": (C.c_int, [C.POINTER(ClearanceOptionsStruct)]),
+    "smhv_batch_clearance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(FiringOptions), C.POINTER(ClearanceOptionsStruct), C.c_void_p,
+                                       C.c_void_p]),
+    "smhv_batch_read_clearance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ClearanceResult)]),
+    "smhv_batch_clearance_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smhv_clearance_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(FiringOptions),
+                                       C.POINTER(ClearanceOptionsStruct), C.POINTER(Clearance), C.c_void_p]),
+    "smhv_batch_clearance_map": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(ClearanceOptionsStruct),
+                                           C.c_void_p, C.c_void_p]),
+    "smhv_batch_read_clearance_map": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ClearanceMapResult)]),
+    "smhv_batch_clearance_map_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smhv_clearance_map": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(ClearanceOptionsStruct), C.POINTER(C.c_uint32), C.c_void_p,
+                                     C.c_void_p, C.POINTER(ClearanceMapResult)]),
     "smhv_debug_render_form": (C.c_int, [C.c_uint32]),
     "smhv_debug_render_rule": (C.c_int, [C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -317,6 +317,73 @@ class FrameBatch:
         L.check(self._lib.smhv_batch_reach_ptr(self._b, C.byref(d)))
         return d.value or 0
 
+    def clearance(self, clearance, first=0, n=None, heightmap=None, fit_to_minimap=True, viewport=None, profiles_ptr=None, profiles=False, stream=None):
+        """The terrain clearance of the detected lines of frames [first, first + n) on `stream` (smhv_batch_clearance): clearance = a
+        ClearanceOptions (samples, margin_m); heightmap, fit_to_minimap, viewport as the firing solutions take them.  With
+        profiles and profiles_ptr None a torch float32 tensor [n, MAX_LINES, CLEAR_PROFILE] is allocated, filled and returned (the
+        call then returns after the device has finished); with profiles_ptr (device memory of that size) the call is asynchronous
+        and returns None, as it does without profiles.  read_clearance() waits for the records."""
+        n = self.max_frames - first if n is None else n
+        co = clearance.struct()
+        fo = L.firing_options(fit_to_minimap, viewport)
+        out = None
+        if profiles and profiles_ptr is None:
+            import torch
+            out = torch.zeros((n, L.MAX_LINES, L.CLEAR_PROFILE), dtype=torch.float32, device="cuda")
+            torch.cuda.synchronize()
+            profiles_ptr = out.data_ptr()
+        L.check(self._lib.smhv_batch_clearance(self._b, first, n, heightmap._hm if heightmap is not None else None, C.byref(fo), C.byref(co),
+                                               C.c_void_p(int(profiles_ptr)) if profiles_ptr else None, C.c_void_p(int(stream)) if stream else None))
+        if out is not None:
+            torch.cuda.synchronize()
+        return out
+
+    def read_clearance(self, first=0, n=None):
+        """Synchronising host copy of the clearance slab -> a ctypes array of n ClearanceResult."""
+        n = self.max_frames - first if n is None else n
+        out = (L.ClearanceResult * n)()
+        L.check(self._lib.smhv_batch_read_clearance(self._b, first, n, out))
+        return out
+
+    def clearance_ptr(self):
+        """Device address of the clearance slab (one smhv_clearance_result per frame)."""
+        d = C.c_void_p()
+        L.check(self._lib.smhv_batch_clearance_ptr(self._b, C.byref(d)))
+        return d.value or 0
+
+    def clearance_map(self, options, clearance, first=0, n=None, heightmap=None, bytes_ptr=None, stream=None):
+        """The clearance map of frames [first, first + n) on `stream` (smhv_batch_clearance_map): options = a RenderOptions (the
+        window and the viewport; with paint the most recent render's), clearance = a ClearanceOptions.  With clearance.bytes and
+        bytes_ptr None a torch uint8 tensor [n, out_h, out_w] is allocated, filled and returned (the call then returns after the
+        device has finished); with bytes_ptr (device memory, n * out_h * out_w bytes) the call is asynchronous and returns None,
+        as it does without bytes."""
+        n = self.max_frames - first if n is None else n
+        co = clearance.struct()
+        out = None
+        if clearance.bytes and bytes_ptr is None:
+            import torch
+            out = torch.zeros((n, int(options.out_h), int(options.out_w)), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            bytes_ptr = out.data_ptr()
+        L.check(self._lib.smhv_batch_clearance_map(self._b, first, n, heightmap._hm if heightmap is not None else None, C.byref(options), C.byref(co),
+                                                   C.c_void_p(int(bytes_ptr)) if bytes_ptr else None, C.c_void_p(int(stream)) if stream else None))
+        if out is not None:
+            torch.cuda.synchronize()
+        return out
+
+    def read_clearance_map(self, first=0, n=None):
+        """Synchronising host copy of the clearance-map slab -> a ctypes array of n ClearanceMapResult."""
+        n = self.max_frames - first if n is None else n
+        out = (L.ClearanceMapResult * n)()
+        L.check(self._lib.smhv_batch_read_clearance_map(self._b, first, n, out))
+        return out
+
+    def clearance_map_ptr(self):
+        """Device address of the clearance-map slab (one smhv_clearance_map_result per frame)."""
+        d = C.c_void_p()
+        L.check(self._lib.smhv_batch_clearance_map_ptr(self._b, C.byref(d)))
+        return d.value or 0
+
     def probe(self, options, points, first=0, n=None, stream=None):
         """The vision debugger's numbers of frames [first, first + n) at `points` = [(mx, my)] window positions (at most
         MAX_PROBES) through the viewport of `options` (a RenderOptions), on `stream` (smhv_batch_probe): no pixels.  Asynchronous;

@@ -164,6 +164,51 @@ __device__ __forceinline__ uint32_t reach_class(double meters, double alt_delta)
 	return disc >= 0.0 ? SMHV_REACH_BAND0 + k : SMHV_REACH_OUT_OF_RANGE;
 }
 
+// the paint of the reach map and of the clearance map: palette entry pal (R, G, B, a as a little-endian word) over pixel px, alpha kept
+__device__ __forceinline__ uint32_t reach_blend(uint32_t px, uint32_t pal) {
+	const uint32_t a = pal >> 24, na = 255u - a;
+	const uint32_t r = ((px & 255u) * na + (pal & 255u) * a + 127u) / 255u;
+	const uint32_t g = (((px >> 8) & 255u) * na + ((pal >> 8) & 255u) * a + 127u) / 255u;
+	const uint32_t b = (((px >> 16) & 255u) * na + ((pal >> 16) & 255u) * a + 127u) / 255u;
+	return (px & 0xFF000000u) | (b << 16) | (g << 8) | r;
+}
+
+// ---- terrain clearance (k_clear_lines, k_clear_map: smh_clear.hip): the header's "terrain clearance", one function per step of its
+// rule, so the per-line and the dense kernel run the same operations.
+// The heightmap coordinate of a translated point on one axis, as firing_line() and reach_axis() compute it.
+__device__ __forceinline__ double clear_coord(float p, float r0, double rlen, uint32_t n) { return (((double)p - (double)r0) / rlen) * (double)n; }
+// (double)v / 65535.0 * zscale.  The quotient of a 16-bit v is formed without the division's instruction sequence: q0 = v * r with
+// r = RN(1 / 65535), rem = v - q0 * 65535 exactly (one fma), q = q0 + rem * r (one more).  That is the IEEE quotient, bit for bit, for
+// every one of the 65,536 inputs (tests/test_clearance_host.py runs them all through the host's fma) at 3 instructions in place of 11;
+// the texel's height is what every sample of the march computes first.
+#define SMH_RCP_65535 0x1.000100010001p-16
+__device__ __forceinline__ double clear_height(uint16_t v, double zscale) {
+	const double n = (double)v, q0 = n * SMH_RCP_65535;
+	return fma(fma(-q0, 65535.0, n), SMH_RCP_65535, q0) * zscale;
+}
+// sample k's rounded, clamped texel coordinate on one axis: c0, c1 = the end coordinates, t = (double)k / (double)S
+__device__ __forceinline__ uint32_t clear_texel(double c0, double c1, double t, uint32_t n) {
+	const int32_t i = round_i32(c0 + (c1 - c0) * t);
+	return (uint32_t)min(max(i, 0), (int32_t)n - 1);
+}
+// What a line's samples are held against: d, alt, disc, q and 1 + q * q (the rule's steps 1 and 2)
+struct ClearArc { double d, alt, disc, q, qq1; };
+__device__ __forceinline__ ClearArc clear_arc(double d, double alt) {
+	ClearArc c;
+	c.d = d; c.alt = alt;
+	c.disc = SMH_MORTAR_V4 - SMH_MORTAR_G * (SMH_MORTAR_G * (d * d) + 2.0 * alt * SMH_MORTAR_V2);
+	c.q = (SMH_MORTAR_V2 + sqrt(c.disc)) / (SMH_MORTAR_G * d);
+	c.qq1 = 1.0 + c.q * c.q;
+	return c;
+}
+// One sample (step 3): z = the terrain over the origin there -> the margin m; *los = the sample blocks the sight line
+__device__ __forceinline__ double clear_sample(const ClearArc &c, double t, double z, bool *los) {
+	const double x = c.d * t;
+	const double a = x * c.q - ((SMH_MORTAR_G * (x * x)) * c.qq1) / (2.0 * SMH_MORTAR_V2);
+	*los = c.alt * t < z;
+	return a - z;
+}
+
 // The frame's firing slab from its finished record: lane l (< 64) takes line l.  Called by one wave after a wave barrier behind
 // lane 0's header writes (the record is read back: n_lines, m/px, the minimap rectangle and the line's own fields).
 __device__ __forceinline__ void firing_frame_tail(const Buffers *bp, uint32_t f, uint32_t lane) {

@@ -261,6 +261,41 @@ struct ReachRun {
 	uint32_t per_call, has_mpx, has_mm;  // 1: mpx / has_mpx, mm / has_mm are the call's and aux, res are not read
 	uint32_t pal[10];                    // out_of_range, band[0 .. 7], ring: R, G, B, a as a little-endian word
 };
+// smhv_batch_clearance / smhv_clearance_lines (k_clear_lines: smh_clear.hip): the terrain clearance of the lines of n frames, or of
+// explicit lines.  Launch arguments, taken by value at the launch.
+#define SMH_CLEAR_PROFILE (SMHV_CLEAR_MAX_SAMPLES + 1u)   // floats of a line's profile row
+struct ClearLinesRun {
+	FiringRun fr;                        // the heightmap and the viewport, as the firing solutions take them (`out` is not used)
+	const smhv_frame_result *res;        // batch, per frame: n_lines, the lines, the minimap rectangle (as firing_frame_tail reads them)
+	const smhv_line *lines;              // per call: the explicit lines
+	smhv_clearance_result *out;          // batch: the clearance slab, at the first frame of the call
+	smhv_clearance *out_lines;           // per call: one record per line
+	float *profiles;                     // SMH_CLEAR_PROFILE floats per line, SMHV_MAX_LINES lines per frame (per call: per line); null: none
+	double margin_m;
+	uint32_t samples;                    // S
+	uint32_t n_lines;                    // per call: of `lines`
+	uint32_t mm[4];                      // per call: the minimap rectangle (valid iff has_mm)
+	uint32_t per_call, has_mm;
+};
+// smhv_batch_clearance_map / smhv_clearance_map (k_clear_map: smh_clear.hip): the clearance map of n frames, in k_reach's tiles.
+#define SMH_CLEAR_KC 32u                 // samples whose texel coordinates a workgroup stages in LDS at a time
+struct ClearMapRun {
+	FiringRun fr;
+	const FrameAux *aux;                 // batch, per frame: open
+	const smhv_frame_result *res;        // batch, per frame: the minimap rectangle, the lines (the origin)
+	smhv_clearance_map_result *out;      // the clearance-map slab, at the first frame of the call; cleared ahead of the launch
+	uint8_t *img;                        // PAINT: the render slab, at the first frame of the call
+	uint8_t *bytes;                      // BYTES: out_w * out_h bytes per frame
+	uint64_t img_stride, bytes_stride;   // out_w * out_h * 4, out_w * out_h
+	double margin_m;
+	float origin[2];                     // SMHV_REACH_ORIGIN_POINT
+	uint32_t mm[4];                      // per call: the minimap rectangle (valid iff has_mm)
+	uint32_t out_w, out_h;
+	uint32_t samples;                    // S
+	uint32_t origin_mode, line;
+	uint32_t per_call, has_mm;           // 1: mm / has_mm are the call's and aux, res are not read
+	uint32_t pal[4];                     // out_of_range, clear, blocked, los: R, G, B, a as a little-endian word
+};
 // smhv_batch_probe / smhv_batch_render_debug / smhv_render_map_debug (k_probe, k_debug_plan, k_debug_draw: smh_debugtext.hip): the
 // vision debugger's numbers and the debug text of n frames.  Launch arguments, taken by value at the launch.
 #define SMH_DBG_ITEMS (SMHV_TEXT_MAX_RUNS + 1u + 4u * SMHV_MAX_PROBES)   // a frame's item list: the runs, the caption, four per probe
@@ -539,6 +574,10 @@ hipError_t launch_heightmap_lut16(const uint32_t *lut, uint16_t *lut16, uint32_t
 hipError_t launch_labels(const LabelRun &r, uint32_t n, hipStream_t s);
 // the reach map (smh_reach.hip): k_reach<paint, classes> over n frames (at most 65,535: the grid's third dimension)
 hipError_t launch_reach(const ReachRun &r, uint32_t n, bool paint, bool classes, hipStream_t s);
+// terrain clearance (smh_clear.hip): k_clear_lines over n frames x SMHV_MAX_LINES lines (per call: n = 1, r.n_lines lines), and
+// k_clear_map<paint, bytes> over n frames (at most 65,535 each: a grid dimension)
+hipError_t launch_clear_lines(const ClearLinesRun &r, uint32_t n, hipStream_t s);
+hipError_t launch_clear_map(const ClearMapRun &r, uint32_t n, bool paint, bool bytes, hipStream_t s);
 // the vision debugger and the debug text (smh_debugtext.hip): k_probe over n frames; with r.img also k_debug_plan and k_debug_draw
 hipError_t launch_debug_text(const Geom &g, const DebugRun &r, uint32_t n, hipStream_t s);
 void render_set_form(uint32_t form);

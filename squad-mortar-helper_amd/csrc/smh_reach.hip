@@ -26,14 +26,6 @@ namespace smh {
 
 #define RCH_CNT 12u   // s_cnt: classes 1 .. 9, the ring pixels, the source mask, spare
 
-__device__ __forceinline__ uint32_t reach_blend(uint32_t px, uint32_t pal) {
-	const uint32_t a = pal >> 24, na = 255u - a;
-	const uint32_t r = ((px & 255u) * na + (pal & 255u) * a + 127u) / 255u;
-	const uint32_t g = (((px >> 8) & 255u) * na + ((pal >> 8) & 255u) * a + 127u) / 255u;
-	const uint32_t b = (((px >> 16) & 255u) * na + ((pal >> 16) & 255u) * a + 127u) / 255u;
-	return (px & 0xFF000000u) | (b << 16) | (g << 8) | r;
-}
-
 template <bool PAINT, bool CLASSES>
 __global__ void __launch_bounds__(256) k_reach(const ReachRun r) {
 	__shared__ ReachAxis s_col[SMH_REACH_TW + 1u], s_row[SMH_REACH_TH + 1u];

@@ -273,6 +273,10 @@ struct smhv_batch {
 	// smhv_batch_reach: the reach slab (allocated by the first call) and the heightmap the last call read
 	smhv_reach_result *d_reach = nullptr;
 	smhv_heightmap *reach_hm = nullptr;
+	// smhv_batch_clearance / smhv_batch_clearance_map: their slabs (allocated by the first call) and the heightmaps the last calls read
+	smhv_clearance_result *d_clear = nullptr;
+	smhv_clearance_map_result *d_clear_map = nullptr;
+	smhv_heightmap *clear_hm = nullptr, *clear_map_hm = nullptr;
 	// smhv_batch_probe / smhv_batch_render_debug: the probe slab, the item lists and the string pool of the draw (allocated by the
 	// first call), the runs' and points' way to the device (one pinned block, one device block: the runs, then the points), the
 	// event of the most recent copy and the event behind the most recent call's kernels (they read the device block)
@@ -676,7 +680,7 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	(void)hipDeviceSynchronize();
 	void *ptrs[] = {b->d_ui, b->d_ui_luma, b->d_ui_form, b->d_mask, b->d_bits, b->d_tiled, b->d_occ, b->d_ocr, b->d_scales, b->d_aux, b->d_results, b->d_anchors, b->d_bars, b->d_farm,
 	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run, b->d_overlay, b->d_render, b->d_prims, b->d_labels,
-	                b->d_label_cull, b->d_label_extra, b->d_probes, b->d_dbg_items, b->d_dbg_pool, b->d_dbg_stage, b->d_reach};
+	                b->d_label_cull, b->d_label_extra, b->d_probes, b->d_dbg_items, b->d_dbg_pool, b->d_dbg_stage, b->d_reach, b->d_clear, b->d_clear_map};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	if (b->h_prims) (void)hipHostFree(b->h_prims);
@@ -699,6 +703,8 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	hm_release(b->render_hm);
 	hm_release(b->label_hm);
 	hm_release(b->reach_hm);
+	hm_release(b->clear_hm);
+	hm_release(b->clear_map_hm);
 	if (b->ev_render) (void)hipEventDestroy(b->ev_render);
 	if (b->ev) {
 		for (int r = 0; r < smhv_batch::TIMING_RING; ++r)
@@ -3339,3 +3345,4 @@ extern "C" SMHV_API int smhv_heightmap_overlay(smhv_ctx *c, const smhv_heightmap
 #include "smh_labels.inc"
 #include "smh_debugtext.inc"
 #include "smh_reach.inc"
+#include "smh_clear.inc"

@@ -227,6 +227,41 @@ def reach_thresholds():
     return [float(v) for v in out]
 
 
+# ---- terrain clearance (smhv_batch_clearance / smhv_clearance_lines / smhv_batch_clearance_map / smhv_clearance_map) ------------------
+class ClearanceOptions:
+    """What a clearance call computes: samples = S, how many steps the line of fire is cut into (1 .. 256); margin_m = metres the arc
+    must keep over the terrain.  The map only: origin = (x, y) in map-ROI coordinates, or ("p0", i) / ("p1", i): that end of each
+    frame's line i (a batch only); paint / bytes = tint the render slab / write the status bytes; palette = None (the library's,
+    smhv_clearance_defaults) or dict(out_of_range=rgba, clear=rgba, blocked=rgba, los=rgba), a = the blend weight."""
+
+    def __init__(self, samples=64, margin_m=0.0, origin=(0.0, 0.0), paint=True, bytes=False, palette=None):
+        self.samples = int(samples)
+        self.margin_m = float(margin_m)
+        self.origin = origin
+        self.paint = bool(paint)
+        self.bytes = bool(bytes)
+        self.palette = palette
+
+    def struct(self):
+        """-> smhv_clearance_options."""
+        o = L.ClearanceOptionsStruct()
+        L.check(L.load().smhv_clearance_defaults(C.byref(o)))
+        o.flags = (L.CLEAR_PAINT if self.paint else 0) | (L.CLEAR_BYTES if self.bytes else 0)
+        o.samples = self.samples
+        o.margin_m = self.margin_m
+        if isinstance(self.origin[0], str):
+            o.origin_mode = {"p0": L.REACH_ORIGIN_LINE_P0, "p1": L.REACH_ORIGIN_LINE_P1}[self.origin[0]]
+            o.line = int(self.origin[1])
+        else:
+            o.origin_mode = L.REACH_ORIGIN_POINT
+            o.origin[0], o.origin[1] = float(self.origin[0]), float(self.origin[1])
+        if self.palette is not None:
+            for k in range(4):
+                for name in ("out_of_range", "clear", "blocked", "los"):
+                    getattr(o, name)[k] = int(self.palette[name][k])
+        return o
+
+
 # ---- debug text and the vision debugger (smhv_batch_probe / smhv_batch_render_debug / smhv_render_map_debug) ------------------------
 def text_run(x, y, text, rgba=(255, 255, 255, 255), map_coords=False):
     """One smhv_text_run as a tuple (x, y, (r, g, b, a), flags, bytes): `text` a str (encoded as Latin-1) or bytes, '\\n' starts a

@@ -305,6 +305,37 @@ class HipVision:
                                          image.ctypes.data if image is not None else None, cls.ctypes.data if cls is not None else None, C.byref(res)))
         return cls, res
 
+    def clearance_lines(self, lines, clearance, minimap=None, heightmap=None, fit_to_minimap=True, viewport=None, profiles=False):
+        """The terrain clearance of explicit lines in map-ROI coordinates (smhv_clearance_lines; stateless like firing_solutions):
+        lines: float32 [n, 4]; clearance = a ClearanceOptions (samples, margin_m); minimap, heightmap, fit_to_minimap, viewport as
+        firing_solutions takes them.  -> (a ctypes array of n Clearance, float32 [n, CLEAR_PROFILE] or None)."""
+        ln = np.ascontiguousarray(np.asarray(lines, np.float32).reshape(-1, 4))
+        n = ln.shape[0]
+        out = (L.Clearance * n)()
+        prof = np.zeros((n, L.CLEAR_PROFILE), np.float32) if profiles else None
+        co = clearance.struct()
+        opt = L.firing_options(fit_to_minimap, viewport)
+        mm = (C.c_uint32 * 4)(*[int(v) for v in minimap]) if minimap is not None else None
+        L.check(self._lib.smhv_clearance_lines(self._ctx, ln.ctypes.data if n else None, n, mm, heightmap._hm if heightmap is not None else None,
+                                               C.byref(opt), C.byref(co), out if n else None, prof.ctypes.data if prof is not None and n else None))
+        return out, prof
+
+    def clearance_map(self, options, clearance, minimap=None, heightmap=None, image=None, bytes=True):
+        """The clearance map of one window (smhv_clearance_map; stateless like reach_map): options = a RenderOptions (the window and
+        the viewport), clearance = a ClearanceOptions with a point origin; minimap = (left, right, top, bottom), heightmap: the
+        frame's, or None.  image: uint8 [out_h, out_w, 4], tinted in place; bytes: return the status bytes.
+        -> (uint8 [out_h, out_w] or None, ClearanceMapResult)."""
+        co = clearance.struct()
+        h, w = int(options.out_h), int(options.out_w)
+        if image is not None and (image.dtype != np.uint8 or image.shape != (h, w, 4) or not image.flags["C_CONTIGUOUS"]):
+            raise L.VisionError(L.E_INVALID, "clearance_map: image must be a contiguous uint8 [%d, %d, 4]" % (h, w))
+        out = np.empty((max(h, 1), max(w, 1)), np.uint8) if bytes else None
+        res = L.ClearanceMapResult()
+        mm = (C.c_uint32 * 4)(*[int(v) for v in minimap]) if minimap is not None else None
+        L.check(self._lib.smhv_clearance_map(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(options), C.byref(co), mm,
+                                             image.ctypes.data if image is not None else None, out.ctypes.data if out is not None else None, C.byref(res)))
+        return out, res
+
     def probe(self, viewport, points, out_w=1, out_h=1):
         """The vision debugger's numbers of the current frame at `points` = [(mx, my)] window positions through `viewport` (a
         MapViewport) -> a ctypes array of MAX_PROBES Probe.  The per-call path has no probe-only entry point: this is
