@@ -161,8 +161,12 @@ SMHV_API int smhv_trait_times(smhv_ctx *ctx, uint64_t ns[SMHV_TRAIT_CALLS], uint
 #define SMHV_STAGE_MINIMAP 0x10u /* find_minimap (not a Vision trait method; the caller's next step, not in STAGE_ALL) */
 #define SMHV_STAGE_EXACT_STATS 0x20u /* diagnostic: cast every ray of every visited pixel, so that `ray_steps` equals the
                                         reference's sample count.  Without it the LSD skips angular sectors that provably
-                                        cannot hold an acceptable ray (lines, rounds and every other output are identical;
-                                        ray_steps then counts only the samples actually taken). */
+                                        cannot hold an acceptable ray -- a sector is cast only if it sees a white pixel
+                                        50 - T .. 50 steps away, T = max_gap: a ray without one is aborted before it is long
+                                        enough; a library built with -DSMH_CULL_CHAIN also asks for one 50 - 2T - 1 ..
+                                        50 - T - 1 steps away, by the same argument (lines, rounds and every other output
+                                        are identical; ray_steps then counts only the samples actually taken, by the
+                                        sectors that were not skipped). */
 
 #define SMHV_STAGE_LSD_HELPERS 0x40u /* tuning (smhv_batch_run; a depth-1 pipeline sets it itself): workgroups of k_lsd that have finished their own frame help
                                        the frames still being searched (ray-cast candidates ahead of the owner; results are

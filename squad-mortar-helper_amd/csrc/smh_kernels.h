@@ -135,7 +135,8 @@ struct Buffers {
 	smhv_frame_result *results;
 	const smhv_anchors *anchors;   // device copy, may be null
 	// k_lsd sector culling table for this max_gap (null: cast every ray), SMH_CULL_TAB_WORDS words:
-	//   [SMH_CULL_CELLS words] cell (row oy + R) * 4 + j: mask of the annulus pixels among offsets ox = -R + 32 j + [0, 32)
+	//   [SMH_CULL_CELLS words] cell (row oy + R) * 4 + j: mask of the OUTER annulus' pixels among offsets ox = -R + 32 j + [0, 32)
+	//   [SMH_CULL_CELLS words] -DSMH_CULL_CHAIN only: the same of the MIDDLE annulus (all zero where the threshold has none: the cull is then not chained)
 	//   [(2R+1)^2 bytes, row-major] unit range of each annulus pixel: first_unit | (n_units - 1) << 6, 0xFF = every unit
 	const uint32_t *cull_tab;
 	// x/y offsets of every ray after 32 j additions of its direction, j = 0..SMH_RAY_OFF_BATCHES (float2 [3600][SMH_RAY_OFF_BATCHES + 1];
@@ -352,13 +353,18 @@ __host__ __device__ inline uint64_t occ_stride(const Geom &g) { return (uint64_t
 #define SMH_RAY_OFF_BATCHES 168u     // 5376 steps: longer than the diagonal of the largest supported ROI (4096 x 3300)
 
 // Sector culling table as k_build_sector_table writes it: (2R+1)^2 entries, entry (oy+R)*(2R+1) + (ox+R) = bit mask of the
-// 64-ray units that can sample the pixel at offset (ox, oy) from floor(start point) at a step in [50 - T, 50].  The host
-// condenses it into the per-word cells of Buffers::cull_tab.
+// 64-ray units that can sample the pixel at offset (ox, oy) from floor(start point), and the annuli it lies in -- steps
+// [50 - T, 50] and [50 - 2T - 1, 50 - T - 1] (smh_cull_rule.h: smh_cull_entry).  The host condenses it into the per-word
+// cells of Buffers::cull_tab: one mask per annulus the build scans (SMH_CULL_ANNULI: the outer one; with -DSMH_CULL_CHAIN the
+// middle one too), one unit code per pixel.
+#include "smh_cull_rule.h"
 #define SMH_SECTOR_R 52
 #define SMH_SECTOR_DIM (2 * SMH_SECTOR_R + 1)
 #define SMH_SECTOR_ENTRIES (SMH_SECTOR_DIM * SMH_SECTOR_DIM)
 #define SMH_CULL_CELLS (SMH_SECTOR_DIM * 4)
-#define SMH_CULL_TAB_WORDS (SMH_CULL_CELLS + (SMH_SECTOR_ENTRIES + 3) / 4)
+#define SMH_CULL_TAB_WORDS (SMH_CULL_ANNULI * SMH_CULL_CELLS + (SMH_SECTOR_ENTRIES + 3) / 4)
+#define SMH_CULL_CODES(tab) ((const uint8_t *)((tab) + SMH_CULL_ANNULI * SMH_CULL_CELLS))
+#define SMH_CULL_MID_CELL(tab, cell) (SMH_CULL_ANNULI == 2 ? (tab)[(SMH_CULL_ANNULI - 1) * SMH_CULL_CELLS + (cell)] : 0u)   // (no middle mask in a build without the chain)
 
 // ---- the frame-granular line search of a pipeline (k_lsd_service, smh_service.inc; round 4) -------------------------------
 // A batch-granular search launch lasts as long as its slowest frame, and the slot cannot be resubmitted before.  A pipeline of

@@ -64,7 +64,7 @@ __device__ RayDir g_ray_table[SMH_LSD_RAYS] = {
 #define LSD_CACHE_MARGIN 72                         // rows around a candidate kept in the GLOBAL mode's LDS row cache (pass 1 walks 64 samples)
 #define LSD_A_BATCHES 2u                            // 32-sample batches walked in phase A before a ray is queued
 #define LSD_WIN_WORDS_CAP 27400u                   // 1080p whole ROI in ROWS mode = 824 rows x 33 words + 4 = 27196 words;
-// with the candidate list, the ray queue, LsdShared and the sector culling table (12.7 KB) a workgroup takes 146 KB.
+// with the candidate list, the ray queue, LsdShared and the sector culling table (14.4 KB) a workgroup takes 148 KB.
 // That and the 96-VGPR cap on the kernels (amdgpu_waves_per_eu(5, 5): 4 waves x 96 of a SIMD's 512 registers, 48 bytes
 // of scratch) leave room for ONE streaming workgroup of the other pipelined step (k_map_pass: 10.5 KB of LDS, one
 // 96-VGPR wave per SIMD) on the same CU: k_lsd keeps its VALU busy 14 % of the time, so the HBM passes run underneath
@@ -232,6 +232,25 @@ __device__ __forceinline__ uint32_t win2_raw(const Win &m, float x, float y) {
 }
 __device__ __forceinline__ uint32_t win2_word(const Win &m, int wq, int yi) { return *(const LdsWord *)(m.w2 + __mul24(yi, (int)(4u * LSD_W2_PITCH)) + (wq << 2)); }
 __device__ __forceinline__ uint32_t win2_bit(const Win &m, int xi, int yi) { return (win2_word(m, xi >> 5, yi) >> ((uint32_t)xi & 31u)) & 1u; }
+
+// How a search culls (smh_cull_rule.h): 0 every ray is cast (no table: exact statistics; or a threshold the argument does
+// not cover), 1 the outer annulus alone, 2 chained with the middle annulus.  Wave-uniform.
+__device__ __forceinline__ uint32_t cull_mode_for(const uint32_t *tab, float max_gap) {
+	if (tab == nullptr || !(max_gap > 0.0f && max_gap <= 49.0f)) return 0u;
+	return smh_cull_chained((uint32_t)ceilf(max_gap)) ? 2u : 1u;
+}
+// The units a cell's white annulus pixels `hit` can be seen by (codes: the unit codes of the cell's 32 pixels), unfolded:
+// a range that wraps past the last unit continues above bit LSD_GROUPS (cull_fold).
+__device__ __forceinline__ unsigned long long cull_units_of(uint32_t hit, const uint8_t *codes) {
+	unsigned long long acc = 0ull;
+	while (hit) {
+		const uint32_t code = codes[__builtin_ctz(hit)];
+		hit &= hit - 1u;
+		acc |= code == 0xFFu ? ~0ull : ((2ull << (code >> 6)) - 1ull) << (code & 63u);   // first <= 56, n <= 4
+	}
+	return acc;
+}
+__device__ __forceinline__ unsigned long long cull_fold(unsigned long long acc) { return (acc | (acc >> LSD_GROUPS)) & ((1ull << LSD_GROUPS) - 1ull); }
 
 // (not on the hot path: the cache test is a run-time one here)
 __device__ __forceinline__ uint32_t win_bit(const Win &m, int xi, int yi) {
@@ -475,6 +494,7 @@ struct LsdShared {
 	uint32_t nlive;                          // live units of the group, listed (in no particular order) in ulist
 	unsigned short ulist[LSD_UNITS];
 	unsigned long long live[LSD_C];          // units (64-ray sectors) of each candidate that have to be cast
+	unsigned long long live_mid[LSD_C];      // (the chained cull: the units that see white in the middle annulus, until they are ANDed into live)
 	float lines[SMH_LSD_MAX_LINES][4];
 	// prox_line() of each accepted line (smh_proximity.h): slope of the signed distance along x, unit direction
 	float prox_a[SMH_LSD_MAX_LINES];
@@ -856,7 +876,7 @@ __device__ __forceinline__ void cache_cover(const Geom &g, FrameView &v, uint32_
 __device__ __forceinline__ void group_reset(LsdShared &sh, uint32_t nc, bool cull) {
 	const uint32_t tid = threadIdx.x;
 	if (tid < nc * LSD_GROUPS) { sh.unit_key[tid] = 0ull; sh.unit_kmax[tid] = 0u; }
-	if (tid < LSD_C) { sh.cand_best[tid] = 0ull; sh.cand_steps[tid] = 0u; sh.cand_kmax[tid] = 0u; sh.live[tid] = cull ? 0ull : ~0ull; }
+	if (tid < LSD_C) { sh.cand_best[tid] = 0ull; sh.cand_steps[tid] = 0u; sh.cand_kmax[tid] = 0u; sh.live[tid] = cull ? 0ull : ~0ull; sh.live_mid[tid] = 0ull; }
 	if (tid == 0) { sh.qtail = 0u; sh.unit_next = LSD_NW; sh.nlive = 0u; sh.cached = 0u;
 #ifdef SMH_LSD_PROFILE
 		sh.exp_far = 0u; sh.exp_units = 0u;
@@ -868,7 +888,7 @@ __device__ __forceinline__ void group_reset(LsdShared &sh, uint32_t nc, bool cul
 // sector culling, unit list and the ray engine for the candidates whose bit in sh.cached is clear.  On return (after a
 // barrier) sh.cand_pt holds every start point and sh.cand_best / cand_end / cand_steps the results of the cast ones.
 template <int MODE>
-__device__ __forceinline__ void cast_group(const Win &m, LsdShared &sh, uint32_t *queue, const uint32_t *cull_tab, uint32_t nc, bool cull, float max_gap,
+__device__ __forceinline__ void cast_group(const Win &m, LsdShared &sh, uint32_t *queue, const uint32_t *cull_tab, uint32_t nc, uint32_t cull, float max_gap,
                                            unsigned long long *prof_t = nullptr) {
 	const uint32_t tid = threadIdx.x;
 #ifdef SMH_LSD_PROFILE
@@ -900,31 +920,31 @@ __device__ __forceinline__ void cast_group(const Win &m, LsdShared &sh, uint32_t
 #endif
 	const uint32_t cached = sh.cached;
 	if (cull) {
-		// ---- sector culling: which 64-ray units can see a white pixel at a distance in [50 - T, 50]? ----
+		// ---- sector culling: which 64-ray units can see a white pixel in the outer annulus and one in the middle annulus
+		// (smh_cull_rule.h)? ----
 		// One thread per (candidate, row, 32-pixel word) cell of the (2R+1)-row neighbourhood: the mask word,
-		// funnel-shifted so that bit 0 is offset -R from floor(start point), is ANDed with the annulus mask of
-		// the cell; every white annulus pixel left contributes its unit range (a byte code per pixel).
+		// funnel-shifted so that bit 0 is offset -R from floor(start point), is ANDed with each annulus' mask of
+		// the cell; every white annulus pixel left contributes its unit range (a byte code per pixel).  The cell's two
+		// masks are read with the window words, not after them.
 		for (uint32_t id = tid; id < nc * SMH_CULL_CELLS; id += LSD_BS) {
 			const uint32_t c = id / SMH_CULL_CELLS, cell = id - c * SMH_CULL_CELLS;
 			if ((cached >> c) & 1u) continue;
+			const uint32_t m_out = cull_tab[cell], m_mid = SMH_CULL_MID_CELL(cull_tab, cell);
 			const int fx = (int)floorf(sh.cand_pt[c][0]), fy = (int)floorf(sh.cand_pt[c][1]);
 			const int yi = fy + (int)(cell >> 2) - SMH_SECTOR_R;
 			if ((uint32_t)yi >= m.h) continue;
 			const int b0 = fx - SMH_SECTOR_R + (int)((cell & 3u) << 5) + m.xbias;   // view bit coordinate of the cell's bit 0
 			const uint32_t lo = win_word(m, b0 >> 5, yi), hi = win_word(m, (b0 >> 5) + 1, yi);
-			uint32_t hit = __builtin_amdgcn_alignbit(hi, lo, (uint32_t)b0 & 31u) & cull_tab[cell];
-			if (hit) {
-				const uint8_t *codes = (const uint8_t *)(cull_tab + SMH_CULL_CELLS) + (cell >> 2) * SMH_SECTOR_DIM + ((cell & 3u) << 5);
-				unsigned long long acc = 0ull;
-				while (hit) {                           // white annulus pixels of this word: their unit ranges
-					const uint32_t code = codes[__builtin_ctz(hit)];
-					hit &= hit - 1u;
-					acc |= code == 0xFFu ? ~0ull : ((2ull << (code >> 6)) - 1ull) << (code & 63u);   // first <= 56, n <= 4
-				}
-				atomicOr(&sh.live[c], (acc | (acc >> LSD_GROUPS)) & ((1ull << LSD_GROUPS) - 1ull));   // units wrap at 57
-			}
+			const uint32_t px32 = __builtin_amdgcn_alignbit(hi, lo, (uint32_t)b0 & 31u);
+			const uint8_t *codes = SMH_CULL_CODES(cull_tab) + (cell >> 2) * SMH_SECTOR_DIM + ((cell & 3u) << 5);
+			if (px32 & m_out) atomicOr(&sh.live[c], cull_fold(cull_units_of(px32 & m_out, codes)));   // units wrap at 57
+			if (cull == 2u && (px32 & m_mid)) atomicOr(&sh.live_mid[c], cull_fold(cull_units_of(px32 & m_mid, codes)));
 		}
 		__syncthreads();
+		if (cull == 2u) {                               // (uniform)
+			if (tid < nc && !((cached >> tid) & 1u)) sh.live[tid] = smh_cull_live(sh.live[tid], sh.live_mid[tid], true);
+			__syncthreads();
+		}
 	}
 	if (tid < nc * LSD_GROUPS) {                    // list the units that have to be cast
 		const uint32_t c = tid / LSD_GROUPS;
@@ -976,7 +996,7 @@ __device__ void lsd_frame(const Geom &g, const Buffers &b, uint32_t f, float max
 	}
 
 	// sector culling needs the table for this max_gap (absent in exact-statistics mode) and a gap threshold below 50
-	const bool cull = b.cull_tab != nullptr && max_gap > 0.0f && max_gap <= 49.0f;
+	const uint32_t cull = cull_mode_for(b.cull_tab, max_gap);
 	const uint32_t *ring = co ? b.co.req + (size_t)f * SMH_LSD_REQ_CAP : nullptr;
 	const LsdCacheEntry *ctab = co ? b.co.cache + (size_t)f * SMH_LSD_CACHE_SLOTS : nullptr;
 	if (tid == 0) { sh.req_tail = 0u; sh.posted_hi = 0u; sh.posted_new = 0u; sh.helpers_seen = 0u; sh.head_seen = 0u; if (co) st_relaxed(&co->mode1, (uint32_t)MODE + 1u); }
@@ -1177,7 +1197,7 @@ __device__ void lsd_frame(const Geom &g, const Buffers &b, uint32_t f, float max
 template <int MODE>
 __device__ void lsd_help(const Geom &g, const Buffers &b, uint32_t n_frames, float max_gap, uint32_t *smem, LsdShared &sh, uint32_t *cull_tab, bool have_cull_tab) {
 	const uint32_t tid = threadIdx.x;
-	const bool cull = b.cull_tab != nullptr && max_gap > 0.0f && max_gap <= 49.0f;
+	const uint32_t cull = cull_mode_for(b.cull_tab, max_gap);
 	if (cull && !have_cull_tab) for (uint32_t i = tid; i < SMH_CULL_TAB_WORDS; i += LSD_BS) cull_tab[i] = b.cull_tab[i];
 	uint32_t *queue = smem + LSD_WIN_WORDS_CAP + LSD_LIST_CAP;
 	uint32_t idle = 0;
@@ -1310,7 +1330,7 @@ __global__ void __launch_bounds__(LSD_BS) __attribute__((amdgpu_waves_per_eu(5, 
 		bool record = mode == 0 && (b.rec_stages & SMH_REC_ON) != 0u && !mine && MODE == LSD_MODE_ROWS;
 		if (mine && lsd_mode_for(g, aux) != MODE) mine = false;
 		if (mine) {
-			const bool cull = mode == 0 && b.cull_tab != nullptr && max_gap > 0.0f && max_gap <= 49.0f;
+			const uint32_t cull = mode == 0 ? cull_mode_for(b.cull_tab, max_gap) : 0u;
 			if (cull) { for (uint32_t i = threadIdx.x; i < SMH_CULL_TAB_WORDS; i += LSD_BS) cull_tab[i] = b.cull_tab[i]; have_tab = true; }   // visible after the barrier in frame_setup
 			lsd_frame<MODE>(g, b, f, max_gap, mode, spx, spy, aux, smem, sh, cull_tab, (COOP && coop) ? &b.co.coop[f] : nullptr);
 			record = mode == 0 && (b.rec_stages & SMH_REC_ON) != 0u;
@@ -1345,46 +1365,21 @@ __global__ void __launch_bounds__(LSD_BS) __attribute__((amdgpu_waves_per_eu(5, 
 #include "smh_service.inc"
 
 // ------------------------------------------------------------------------------------------------
-// Sector culling for find_lines (k_lsd).  lsd.rs:94 keeps a candidate only if its longest ray has
-// len^2 > 2500, i.e. the ray's fatal gap starts at step K >= 51 (an aborted ray ends K-1 unit steps from its
-// start).  Such a ray has a WHITE sample at some step in [50 - T, 50]: T+1 consecutive non-white samples
-// there would have aborted it earlier (T = ceil(max_gap)); the same holds for a ray that leaves the image
-// after more than 50 steps.  So for a candidate only the angular sectors that can see a white pixel at a
-// distance in that range have to be ray-cast at all: the longest ray, if it is acceptable, lies in one of
-// them, and if none is acceptable the candidate is rejected whatever the other rays do.
-// The table maps a pixel offset (relative to floor(start point)) to the 64-ray units (6.4 degree sectors)
-// that could sample it at such a step, conservatively: the sample may sit anywhere in the pixel (0.71 px),
-// the start point anywhere in its pixel (0.71 px), plus 0.05 px for accumulated f32 rounding.
+// Sector culling for find_lines (every search kernel).  A ray that can make its candidate acceptable (len^2 > 2500) has a
+// WHITE sample in every window of T + 1 consecutive steps that ends by step 50, T = ceil(max_gap): a white-free window
+// would have aborted it before.  The build looks at the window [50 - T, 50]: only the 64-ray units that can see a white
+// pixel in that annulus have to be ray-cast at all.  The chained argument -- the window [50 - 2T - 1, 50 - T - 1] is
+// disjoint from it and speaks of the same ray, which lies in one unit, so a unit needs a white pixel in the outer annulus
+// AND one in the middle annulus -- holds as well and is compiled in with -DSMH_CULL_CHAIN (measured slower: the scan of the
+// second ring costs more than the units it saves).  The argument, the annuli and the conservative map from a pixel offset
+// to the units that can sample it are smh_cull_rule.h; this kernel tabulates smh_cull_entry over the (2R+1)^2 offsets from
+// floor(start point).
 // ------------------------------------------------------------------------------------------------
 __global__ void k_build_sector_table(unsigned long long *tab, uint32_t T) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= SMH_SECTOR_ENTRIES) return;
 	const int oy = (int)(i / SMH_SECTOR_DIM) - SMH_SECTOR_R, ox = (int)(i % SMH_SECTOR_DIM) - SMH_SECTOR_R;
-	const double rho = 0.7072 + 0.7072 + 0.05;
-	const double kmin = T >= 50u ? 0.0 : (double)(50u - T), kmax = 50.0;
-	const double r0 = sqrt((double)(ox * ox + oy * oy));
-	unsigned long long m = 0ull;
-	if (r0 >= kmin - rho && r0 <= kmax + rho) {
-		if (r0 <= rho) {
-			m = ~0ull;                                    // the start pixel's neighbourhood: every direction
-		} else {
-			const double PI = 3.14159265358979323846;
-			double phi = atan2((double)oy, (double)ox) * 180.0 / PI;   // ray i points at (cos, sin)(i/10 degrees), y down
-			if (phi < 0.0) phi += 360.0;
-			const double delta = asin(rho / r0 > 1.0 ? 1.0 : rho / r0) * 180.0 / PI + 0.2;   // + two ray steps
-			for (int u = 0; u < LSD_GROUPS_HOST; ++u) {
-				const double a0 = 6.4 * u, a1 = 6.4 * u + 6.3;   // rays 64u .. 64u+63
-				// intersects [phi - delta, phi + delta] modulo 360?
-				bool hit = false;
-				for (int wrap = -1; wrap <= 1 && !hit; ++wrap) {
-					const double lo = phi - delta + 360.0 * wrap, hi = phi + delta + 360.0 * wrap;
-					hit = !(hi < a0 || lo > a1);
-				}
-				if (hit) m |= 1ull << u;
-			}
-		}
-	}
-	tab[i] = m;
+	tab[i] = smh_cull_entry(T, ox, oy);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1601,7 +1596,7 @@ hipError_t launch_build_ray_offsets(float *d_off, hipStream_t s) {
 }
 
 hipError_t launch_build_sector_table(unsigned long long *d_tab, uint32_t T, hipStream_t s) {
-	static_assert(LSD_GROUPS == LSD_GROUPS_HOST && LSD_GROUPS <= 64, "sector masks are 64-bit");
+	static_assert(LSD_GROUPS == LSD_GROUPS_HOST && LSD_GROUPS == SMH_CULL_UNITS && LSD_GROUPS <= 62, "sector masks are 64-bit, and smh_cull_rule.h keeps two flags above the units");
 	hipLaunchKernelGGL(k_build_sector_table, dim3((SMH_SECTOR_ENTRIES + 255) / 256), dim3(256), 0, s, d_tab, T);
 	return hipGetLastError();
 }

@@ -296,7 +296,7 @@ __device__ __forceinline__ void tilec_win(Win &m, uint32_t rw, uint32_t rh, uint
 // point; mask samples taken (sum over the wave)
 // REUSE: `wwin` holds the window `tag` places (W_WIN_ROWS + SVC_WIN_EXTRA rows) and is filled only when it does not serve; else: filled for this candidate
 template <int MODE, bool REUSE = false>
-__device__ __forceinline__ void seq_cast_candidate(const Win &m, uint32_t *wwin, WinTag *tag, const uint32_t *cull_tab, bool cull, const RayDir *dirs, const float *ray_off, float max_gap,
+__device__ __forceinline__ void seq_cast_candidate(const Win &m, uint32_t *wwin, WinTag *tag, const uint32_t *cull_tab, uint32_t cull, const RayDir *dirs, const float *ray_off, float max_gap,
                                                    uint32_t px, uint32_t py, float &xs, float &ys, unsigned long long &wkey, float &ex0, float &ey0, uint32_t &steps_sum
 #ifdef SMH_LSD_WDEBUG
                                                    , unsigned long long *sprof, unsigned long long &slast, unsigned long long *uprof, uint32_t &n_units
@@ -597,7 +597,7 @@ __device__ void lsd_frame_seq(const Geom &g, const Buffers &b, uint32_t f, float
 	const uint32_t wy0 = v.wy0, wrows = v.wrows, wwords = v.wwords;
 	const int xorg = v.xorg;
 	const uint32_t WT = wrows * wwords;
-	const bool cull = b.cull_tab != nullptr && max_gap > 0.0f && max_gap <= 49.0f;
+	const uint32_t cull = cull_mode_for(b.cull_tab, max_gap);
 	if (lane == 0) { ws.n_lines = 0u; ws.rounds = 0u; ws.steps = 0ull; }
 	if (TEAM && lane < SEQ_DESK_ENTRIES) ws.rob[lane].state = H_FREE;
 	if (TEAM && lane == 0) { ws.rem_open = 0u; ws.rem_nr = 0u; if (REUSE) ws.frame_no += 1u; }   // (frame_no: what a helper keys its window by, svc_help)

@@ -149,7 +149,7 @@ __device__ __forceinline__ uint32_t opaque_lane() { uint32_t l = threadIdx.x & 6
 // TAGGED with `tag` (neither: k_lsd_tile's shared windows, filled for every candidate): the block's window may serve as it lies.  ROWS: the
 // rows a fill covers, from py - W_WIN_R on (the service's taller window: rows BELOW the needed region, for the scan's next rows).
 template <bool COMPACT = false, uint32_t ROWS = W_WIN_ROWS, bool TAGGED = false>
-__device__ __forceinline__ void cand_setup(const Win &m, uint32_t *wwin, const uint32_t *cull_tab, bool cull, uint32_t px, uint32_t py, float &xs, float &ys, unsigned long long &live,
+__device__ __forceinline__ void cand_setup(const Win &m, uint32_t *wwin, const uint32_t *cull_tab, uint32_t cull, uint32_t px, uint32_t py, float &xs, float &ys, unsigned long long &live,
                                            WinTag *tag = nullptr
 #ifdef SMH_LSD_WDEBUG
                                            , unsigned long long *cprof = nullptr                       // [0] window fill, [1] culling scan (cycles), [2] window fills
@@ -251,40 +251,54 @@ __device__ __forceinline__ void cand_setup(const Win &m, uint32_t *wwin, const u
 	const unsigned long long c_t1 = __builtin_amdgcn_s_memtime();
 	struct CullTimer { unsigned long long *p, t; __device__ ~CullTimer() { if (p) p[1] += __builtin_amdgcn_s_memtime() - t; } } c_timer{cprof, c_t1};
 #endif
-	if (cull) {   // the 64-ray units that can see a white pixel at a distance in [50 - T, 50] (see k_build_sector_table)
-		unsigned long long acc = 0ull;
+	if (cull) {   // the 64-ray units that can see a white pixel in the outer annulus (cull == 2: and one in the middle annulus; smh_cull_rule.h)
 		const int fx = (int)floorf(xs), fy = (int)floorf(ys);
-		// the mask words of all seven cell rounds are fetched before any of them is looked at (one wave per SIMD has nobody
-		// else to hide the LDS round trips behind)
+		// One wave per SIMD has nobody else to hide an LDS round trip behind, so the window words and the cell masks of all
+		// seven cell rounds are read in ONE.  No branch per round (each would get a wait of its own): a lane past the last cell
+		// takes the last cell again, and what it finds there is ORed in a second time.
 		constexpr int ROUNDS = (SMH_CULL_CELLS + 63) / 64;
-		uint32_t hits[ROUNDS];
+		const uint32_t sh = (uint32_t)(fx - SMH_SECTOR_R) & 31u;        // (the same for every cell: their columns are 32 apart)
+		uint32_t cells[ROUNDS], lo[ROUNDS], hi[ROUNDS], m_out[ROUNDS], m_mid[ROUNDS];
 #pragma unroll
 		for (int it = 0; it < ROUNDS; ++it) {
-			const uint32_t cell = lane + 64u * (uint32_t)it;
-			const int yi = fy + (int)(cell >> 2) - SMH_SECTOR_R;
-			uint32_t hit = 0;
-			if (cell < SMH_CULL_CELLS) {                                // (rows outside the image are zero in the window)
-				const int b0 = fx - SMH_SECTOR_R + (int)((cell & 3u) << 5);
-				const uint32_t lo = win2_word(mw, b0 >> 5, yi), hi = win2_word(mw, (b0 >> 5) + 1, yi);
-				hit = __builtin_amdgcn_alignbit(hi, lo, (uint32_t)b0 & 31u) & cull_tab[cell];
-			}
-			hits[it] = hit;
+			const uint32_t cell = 64 * it + 63 < SMH_CULL_CELLS ? lane + 64u * (uint32_t)it : min(lane + 64u * (uint32_t)it, (uint32_t)SMH_CULL_CELLS - 1u);
+			const int yi = fy + (int)(cell >> 2) - SMH_SECTOR_R;        // (rows outside the image are zero in the window)
+			const int wq = (fx - SMH_SECTOR_R + (int)((cell & 3u) << 5)) >> 5;
+			lo[it] = win2_word(mw, wq, yi); hi[it] = win2_word(mw, wq + 1, yi);
+			m_out[it] = cull_tab[cell]; m_mid[it] = SMH_CULL_MID_CELL(cull_tab, cell);
+			cells[it] = cell;
 		}
+		// The white annulus pixels' unit codes, a byte each in LDS: a lane walks the pixels of its cell, four look-ups per round
+		// trip, and the wave waits for the lane with the most.  (-DSMH_CULL_CHAIN: both annuli in one walk.  Measured, with
+		// the second ring's pixels the walk costs more than the units the chain saves, DESIGN.md section 5; a lane per pixel
+		// over the cells that hold any was slower still -- a candidate has some hundred such cells.)
+		const uint8_t *codes = SMH_CULL_CODES(cull_tab);
+		unsigned long long acc_o = 0ull, acc_m = 0ull;
 #pragma unroll
 		for (int it = 0; it < ROUNDS; ++it) {
-			uint32_t hit = hits[it];
-			if (hit) {
-				const uint32_t cell = lane + 64u * (uint32_t)it;
-				const uint8_t *codes = (const uint8_t *)(cull_tab + SMH_CULL_CELLS) + (cell >> 2) * SMH_SECTOR_DIM + ((cell & 3u) << 5);
-				while (hit) {
-					const uint32_t code = codes[__builtin_ctz(hit)];
-					hit &= hit - 1u;
-					acc |= code == 0xFFu ? ~0ull : ((2ull << (code >> 6)) - 1ull) << (code & 63u);
+			const uint32_t px32 = __builtin_amdgcn_alignbit(hi[it], lo[it], sh);   // the cell's 32 pixels
+			const uint32_t h_out = px32 & m_out[it], h_mid = cull == 2u ? px32 & m_mid[it] : 0u;
+			const uint8_t *c = codes + (cells[it] >> 2) * SMH_SECTOR_DIM + ((cells[it] & 3u) << 5);
+			uint32_t hit = h_out | h_mid;
+			while (hit) {                                               // four pixels per round trip (a marker line is three pixels thick)
+				uint32_t b[4], code[4];
+#pragma unroll
+				for (int k = 0; k < 4; ++k) {
+					b[k] = hit || k == 0 ? (uint32_t)__builtin_ctz(hit) : b[k - 1];   // (no pixel left: the last one again)
+					hit &= hit - 1u;                                    // (0 stays 0)
+				}
+#pragma unroll
+				for (int k = 0; k < 4; ++k) code[k] = c[b[k]];
+#pragma unroll
+				for (int k = 0; k < 4; ++k) {
+					const unsigned long long units = code[k] == 0xFFu ? ~0ull : ((2ull << (code[k] >> 6)) - 1ull) << (code[k] & 63u);   // first <= 56, n <= 4
+					if ((h_out >> b[k]) & 1u) acc_o |= units;
+					if ((h_mid >> b[k]) & 1u) acc_m |= units;
 				}
 			}
 		}
-		acc = wave_or64(acc);
-		live = (acc | (acc >> LSD_GROUPS)) & ((1ull << LSD_GROUPS) - 1ull);
+		const unsigned long long seen_outer = cull_fold(wave_or64(acc_o));
+		live = cull == 2u ? smh_cull_live(seen_outer, cull_fold(wave_or64(acc_m)), true) : seen_outer;
 	}
 }
 
@@ -1194,7 +1208,7 @@ __device__ void lsd_frame_wave(const Geom &g, const Buffers &b, uint32_t f, floa
 		if (MODE == LSD_MODE_TILE) return tile_word(m, (int)c, (int)(wy0 + r));
 		return m.p[wi];                                             // LSD_MODE_GLOBAL
 	};
-	const bool cull = b.cull_tab != nullptr && max_gap > 0.0f && max_gap <= 49.0f;
+	const uint32_t cull = cull_mode_for(b.cull_tab, max_gap);
 	const uint32_t epoch = b.co.epoch;
 	if (tid == 0) { ws.stuck = 0u; ws.lock = 0u; ws.head = 0u; ws.tail = 0u; ws.spec = 1u; ws.n_lines = 0u; ws.rounds = 0u; ws.frame_done = 0u; ws.steps = 0ull;
 	                ws.win_free = (1u << W_NWIN) - 1u; ws.farm_on = 0u; ws.farm_posted = 0u; ws.farm_retired = 0u;
@@ -1446,7 +1460,7 @@ __device__ void lsd_frame_help(const Buffers &b, float max_gap, uint32_t *smem, 
 	const uint32_t tid = threadIdx.x, lane = tid & 63u;
 	const Win &m = v.m;
 	uint32_t *wwins = smem + win_cap + 2u * list_cap;
-	const bool cull = b.cull_tab != nullptr && max_gap > 0.0f && max_gap <= 49.0f;
+	const uint32_t cull = cull_mode_for(b.cull_tab, max_gap);
 	const uint32_t epoch = b.co.epoch;
 	if (tid == 0) { ws.lock = 0u; ws.head = 0u; ws.tail = 0u; ws.win_free = (1u << W_NWIN) - 1u; ws.farm_posted = 0u; ws.frame_done = 0u; }
 	if (tid < W_ROB) { ws.rob[tid].state = W_FREE; ws.rob[tid].todo = 0ull; }
@@ -1613,7 +1627,7 @@ __global__ void __launch_bounds__(LSD_TILE_BS) __attribute__((amdgpu_waves_per_e
 #ifdef SMH_LSD_FAT
 	asm volatile("; register footprint experiment" ::: SMH_LSD_FAT);   // e.g. -DSMH_LSD_FAT='"v135"': 136 VGPRs allocated, at most 3 waves per SIMD
 #endif
-	const bool cull = b.cull_tab != nullptr && max_gap > 0.0f && max_gap <= 49.0f;
+	const uint32_t cull = cull_mode_for(b.cull_tab, max_gap);
 	const uint32_t f = blockIdx.x;
 	const FrameAux aux = b.aux[f];
 	const TileKernelArgs *ka = (const TileKernelArgs *)__builtin_amdgcn_kernarg_segment_ptr();   // (the kernel's own parameter list)

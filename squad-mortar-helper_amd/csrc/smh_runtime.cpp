@@ -413,12 +413,13 @@ static int sector_table_for(smhv_ctx *c, uint32_t max_gap, hipStream_t s, Buffer
 	(void)hipFree(d_dense);
 	if (e != hipSuccess) return fail(SMHV_E_HIP, "sector table: %s", hipGetErrorString(e));
 	std::vector<uint32_t> cells(SMH_CULL_TAB_WORDS, 0u);
-	uint8_t *codes = (uint8_t *)&cells[SMH_CULL_CELLS];
+	uint8_t *codes = (uint8_t *)&cells[SMH_CULL_ANNULI * SMH_CULL_CELLS];
 	for (uint32_t row = 0; row < SMH_SECTOR_DIM; ++row)
 		for (uint32_t col = 0; col < SMH_SECTOR_DIM; ++col) {
-			const unsigned long long m = dense[row * SMH_SECTOR_DIM + col] & ((1ull << 57) - 1ull);
+			const unsigned long long e = dense[row * SMH_SECTOR_DIM + col], m = e & ((1ull << SMH_CULL_UNITS) - 1ull);
 			if (!m) continue;
-			cells[row * 4 + (col >> 5)] |= 1u << (col & 31u);
+			if (e & SMH_CULL_IN_OUTER) cells[row * 4 + (col >> 5)] |= 1u << (col & 31u);
+			if (SMH_CULL_ANNULI == 2 && (e & SMH_CULL_IN_MIDDLE)) cells[(SMH_CULL_ANNULI - 1) * SMH_CULL_CELLS + row * 4 + (col >> 5)] |= 1u << (col & 31u);
 			codes[row * SMH_SECTOR_DIM + col] = unit_code(m);
 		}
 	uint32_t *d = nullptr;

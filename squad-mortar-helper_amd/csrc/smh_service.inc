@@ -6,7 +6,7 @@
 // on the reference's screenshots), the batch's slot is blocked until then, and the cheapest search -- one wave per frame, a
 // third of the task kernel's wave-time (smh_lsd_seq.inc) -- was unusable because its slowest frame takes four times as long.
 // Here the search is decoupled from the batch launch: ONE long-lived kernel per pipeline, whose waves pull (slot, frame) items
-// from a ring, each wave on its own -- a workgroup is only the unit that shares the 12.7 KB sector table -- and every frame
+// from a ring, each wave on its own -- a workgroup is only the unit that shares the 14.4 KB sector table -- and every frame
 // writes its own record and counts itself off against its submission.  Nothing waits for a slowest frame except the slot
 // that holds it.
 //
@@ -119,7 +119,7 @@ __device__ __attribute__((noinline)) void svc_help(const void *kargs, uint32_t o
 	if (!uniform_u32(ok)) return;
 	const uint32_t rw = ka->g.rw, rh = ka->g.rh, tile_cap = ka->p.tile_cap, list_cap = ka->p.list_cap;
 	const float max_gap = ka->p.max_gap;
-	const bool cull = ka->p.cull_tab != nullptr && max_gap > 0.0f && max_gap <= 49.0f;
+	const uint32_t cull = cull_mode_for(ka->p.cull_tab, max_gap);
 	const float *ray_off = ka->p.ray_off;
 	Win m;
 	if constexpr (COMPACT) tilec_win(m, rw, rh, opart + SVC_WS_WORDS, tile_cap); else tile_win(m, rw, rh, opart + SVC_WS_WORDS, tile_cap);
@@ -213,7 +213,7 @@ __device__ __attribute__((noinline)) void svc_help_remote(const void *kargs, uin
 	}
 	wave_lds_sync();
 	const float max_gap = ka->p.max_gap;
-	const bool cull = ka->p.cull_tab != nullptr && max_gap > 0.0f && max_gap <= 49.0f;
+	const uint32_t cull = cull_mode_for(ka->p.cull_tab, max_gap);
 	const float *ray_off = ka->p.ray_off;
 	Win m;
 	if constexpr (COMPACT) tilec_win(m, rw, rh, store, tile_cap); else tile_win(m, rw, rh, store, tile_cap);

@@ -104,6 +104,7 @@ if os.environ.get("SVC_RATE_WPROF"):
     for r in recs:
         acc += np.array([r.meters[20 + k] for k in range(9)])
     prof = dict(zip(("list_build", "dispatch", "setup", "units", "verdict", "u_first_batches", "u_long_rays", "u_end_points", "n_units"), (acc / N).tolist()))
+    prof["cycles_per_unit"] = prof["units"] / prof["n_units"] if prof["n_units"] else None   # (n_units: what tools/cull_chain_count.py predicts with no help)
     prof["rounds"] = float(np.mean([r.rounds for r in recs]))
     prof["s_window_fill"] = float(np.mean([r.meters[30] for r in recs]))
     prof["s_cull_scan"] = float(np.mean([r.meters[31] for r in recs]))

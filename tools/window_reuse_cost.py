@@ -66,6 +66,7 @@ def main():
     ap.add_argument("--variant", action="append", help="NAME=LIB: this tree over another build of the library")
     ap.add_argument("--wprof", action="append", help="NAME=LIB: a `make wprof` library of build NAME (parent, this or a variant)")
     ap.add_argument("--skip", default="", help="comma-separated: config4, full, config3")
+    ap.add_argument("--what", default="the search service's candidate window kept between candidates", help="the change under test, for the record's first line (other changes use this protocol: tools/cull_chain_count.py names one)")
     a = ap.parse_args()
     skip = set(x for x in a.skip.split(",") if x)
     parent = os.path.abspath(a.parent)
@@ -88,7 +89,7 @@ def main():
                       dict(SVC_RATE_WPROF="1", RATE_SEARCH="frame", RATE_FLAGS=flags))
             p, st = j["scan_profile_cycles_per_frame"], j["search_service"]
             rec[leg] = dict(s_window_fill=p["s_window_fill"], s_cull_scan=p["s_cull_scan"], setup=p["setup"], units=p["units"], verdict=p["verdict"], rounds=p["rounds"],
-                            window_fills=p.get("window_fills"), cast_by_owner=p.get("cast_by_owner"), search=st["cycles_per_frame_by_phase"]["search"],
+                            window_fills=p.get("window_fills"), cast_by_owner=p.get("cast_by_owner"), n_units=p.get("n_units"), cycles_per_unit=p.get("cycles_per_unit"), search=st["cycles_per_frame_by_phase"]["search"],
                             help_cycles_per_frame=st["help_cycles_per_frame"], frames_per_s=j["frames_per_s"], equal=j["slots_equal_plain_run"])
             print("wprof %s %s: %s" % (n, leg, json.dumps(rec[leg])), flush=True)
         state["wprof"][n] = rec
@@ -123,7 +124,7 @@ def main():
                 v[k] = "above in every round" if min(mine) > max(par) else ("below in every round" if max(mine) < min(par) else "ranges overlap")
         verdict[n] = v
     import torch
-    out = dict(what="the search service's candidate window kept between candidates, against the parent commit: one job, one box, %d interleaved rounds, every figure a child process" % a.rounds,
+    out = dict(what="%s, against the parent commit: one job, one box, %d interleaved rounds, every figure a child process" % (a.what, a.rounds),
                device=torch.cuda.get_device_name(0) if torch.cuda.is_available() else None, builds={n: os.path.relpath(lib, ROOT) for n, _, lib in builds},
                wprof_cycles_per_frame=state["wprof"], rounds=state["rounds"], summary=summary, verdict=verdict, config4_one_gpu=state["config4"], spent_s=SPENT, wall_s=round(time.time() - T0, 1))
     print(json.dumps(dict(verdict=verdict, summary=summary, config4=state["config4"])))
