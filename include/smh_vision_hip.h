@@ -206,7 +206,8 @@ typedef struct {
 #define SMHV_FRAME_OK 0u
 #define SMHV_FRAME_LSD_STUCK 1u
 
-/* per-frame OCR anchors for SMHV_STAGE_SCALES: OCR (Tesseract) is outside this library */
+/* per-frame OCR anchors for SMHV_STAGE_SCALES: OCR (Tesseract) is outside this library; where the labels are, the bars under them and the
+ * glyph crops to read: "scale labels" below (smhv_scale_labels_anchors makes these anchors from the numbers read) */
 typedef struct {
 	uint32_t n;                     /* 0..3                                                        */
 	uint32_t scales_start_y;        /* min(ocr.bottom), src/vision/mod.rs:182                      */
@@ -1325,6 +1326,83 @@ SMHV_API int smhv_batch_clearance_map_ptr(smhv_batch *b, void **d_clearance_map)
  * otherwise not used.  Runs on the context's stream. */
 SMHV_API int smhv_clearance_map(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_clearance_options *opt,
                                 const uint32_t minimap[4], uint8_t *rgba_inout, uint8_t *bytes, smhv_clearance_map_result *result);
+
+/* ---- scale labels: word boxes, the bar under each, glyph crops -----------------------------------------------------------------
+ * The reference's scales branch (src/vision/mod.rs:128-193) pulls the whole ocr_preprocess plane to the host, runs a full-page OCR
+ * over it (ocr::read, mod.rs:149) and filters the hits (mod.rs:161-186) into label anchors.  Reading digits stays on the host; all
+ * the branch needs from the OCR besides is geometry, and this pass finds it on the device: which blobs of the plane are words, their
+ * boxes, which of them have a scale bar `I-----I` beneath them and how wide that bar is.  The host reads three or four glyphs in at
+ * most eight 128 x 32 crops per frame and hands the numbers to smhv_scale_labels_anchors.  Every value of the rule is an integer.
+ * Per open frame, P = the frame's ocr_preprocess plane, qw x qh (brq_w x brq_h); a pixel is foreground when P != 255:
+ *   gap         g = max(1, round(4.0 / 640.0 * qw)) in f64, round half away from zero (f64::round, as max_scale_y_offset of
+ *               mpx_ratio.rs:12 is rounded): 1 at qw 180 and 197, 2 at 357, 4 at 657.
+ *   row runs    foreground pixels of one row belong to the same run when at most g non-foreground pixels lie between neighbours; a
+ *               run is [l, r], its first and last foreground pixel.  Two runs on adjacent rows touch when l1 <= r2 + 1 && l2 <= r1 + 1.
+ *   words       the connected components of the runs.  Box: left = min l, top = min y, right = max r + 1, bottom = max y + 1 (right
+ *               and bottom exclusive, as in the OCR hits the reference consumes).
+ *   candidates  boxes with 3 <= right - left <= SMHV_LABEL_CROP_W && 3 <= bottom - top <= SMHV_LABEL_CROP_H.
+ *   anchor      ((left + right) / 2, bottom), src/vision/mod.rs:181.
+ *   bar         find_scale_width (mpx_ratio.rs:3-67, exactly the rule smhv_calc_meters_to_px_ratio and SMHV_STAGE_SCALES apply: pixels
+ *               outside the image count as non-zero, None for y < 4, max_scale_y_offset rows are scanned) from the anchor on S0 =
+ *               find_scales_preprocess with start row 0.  The scan only reads rows at or below the anchor, and a row of
+ *               find_scales_preprocess is the same whatever start row at or above it the image was made with: the bar does not depend
+ *               on the start row, so it is the bar a later SMHV_STAGE_SCALES run finds from this anchor (scales_start_y <= its y).
+ *   proposals   candidates with a bar and bar_right > bar_left; width = bar_right - bar_left.  The u32 wrap the reference tolerates
+ *               (right < left: a filled dark block under a word) is not a proposal.
+ *   order, cap  ascending by (top, left, right, bottom); the first SMHV_MAX_SCALE_LABELS are written (label[] and their crops), n_found
+ *               counts all of them.  (Two proposals with the same box have the same anchor, bar and crop.)
+ *   header      n = min(n_found, SMHV_MAX_SCALE_LABELS), n_found, n_words = all words of the frame, candidates or not, n_runs,
+ *               flags.  A frame with more than SMHV_LABEL_MAX_RUNS runs has SMHV_LABELS_RUNS_OVERFLOW set, n = n_found = n_words = 0
+ *               and n_runs = the true count; nothing is written past any cap.  label[i] for i >= n is zero.  A closed frame's
+ *               record is all zeros.
+ *   crops       a frame has SMHV_MAX_SCALE_LABELS cells of SMHV_LABEL_CROP_W x SMHV_LABEL_CROP_H bytes, row-major; cell i < n
+ *               holds the pixels of P inside label[i]'s box, placed at the cell's top-left corner, every other byte of it 255.
+ *               Cells i >= n are not written.
+ * The three limits are conditions, not measurements; the reference's own sample screenshots have at most 296 runs, 4 proposals and
+ * boxes of 36 x 16 at 2560 x 1440. */
+#define SMHV_MAX_SCALE_LABELS 8u
+#define SMHV_LABEL_MAX_RUNS 4096u
+#define SMHV_LABEL_CROP_W 128u
+#define SMHV_LABEL_CROP_H 32u
+#define SMHV_LABELS_RUNS_OVERFLOW 1u   /* smhv_scale_label_frame.flags */
+typedef struct {
+	uint32_t left, top, right, bottom;   /*  0: the word's box, brq coordinates; right and bottom exclusive */
+	uint32_t bar_left, bar_y, bar_right; /* 16: find_scale_width's (left, y, right), the scales_debug line */
+	uint32_t width;                      /* 28: bar_right - bar_left */
+} smhv_scale_label;                      /* 32 bytes */
+typedef struct {
+	uint32_t n, n_found, n_words, n_runs; /*  0 */
+	uint32_t flags;                      /* 16: SMHV_LABELS_RUNS_OVERFLOW */
+	uint32_t reserved[3];                /* 20 */
+	smhv_scale_label label[SMHV_MAX_SCALE_LABELS];
+} smhv_scale_label_frame;                /* 288 bytes */
+#define SMHV_LABEL_CROP_BYTES (SMHV_LABEL_CROP_W * SMHV_LABEL_CROP_H)                /* a cell */
+#define SMHV_LABEL_FRAME_CROP_BYTES (SMHV_MAX_SCALE_LABELS * SMHV_LABEL_CROP_BYTES)  /* a frame's cells */
+/* The scale labels of frames [0, n), asynchronously on `stream`, behind a run of this batch over the same frames: a plain batch after
+ * smhv_batch_run, or a pipeline slot's batch after smhv_pipeline_wait.  d_frames: the frames that run was given, under
+ * smhv_batch_run's contract (S0 is made from their pixels, into a plane of this family's own that the first call allocates; the
+ * batch's scales plane, its ocr plane and its records are not touched).  The records go to the batch's label slab, the cells to its
+ * crop slab (both allocated by the first call).
+ * SMHV_E_STATE: the batch's last run had no SMHV_STAGE_OCR, or covered fewer than n frames.  SMHV_E_GEOMETRY: a quadrant wider or
+ * taller than 2048 pixels.  SMHV_E_INVALID: null or misaligned d_frames, n == 0 or beyond the batch's capacity.  A failed call
+ * enqueues nothing. */
+SMHV_API int smhv_batch_scale_labels(smhv_batch *b, const void *d_frames, uint32_t n, void *stream);
+/* The batch's label and crop slabs: read is a synchronising host copy of frames [first, first + n) -- out: n records, crops (NULL:
+ * none): n * SMHV_LABEL_FRAME_CROP_BYTES bytes; ptr the device addresses, either may be NULL (SMHV_E_STATE before the first
+ * smhv_batch_scale_labels). */
+SMHV_API int smhv_batch_read_scale_labels(smhv_batch *b, uint32_t first, uint32_t n, smhv_scale_label_frame *out, uint8_t *crops);
+SMHV_API int smhv_batch_scale_labels_ptr(smhv_batch *b, void **d_labels, void **d_crops);
+/* The per-call form, on the frame of the context's last smhv_ocr_preprocess (SMHV_E_STATE before it, or with the map closed): out
+ * receives the record, crops (NULL: none) SMHV_LABEL_FRAME_CROP_BYTES bytes, of which the cells i >= out->n are left as they are. */
+SMHV_API int smhv_scale_labels(smhv_ctx *ctx, smhv_scale_label_frame *out, uint8_t *crops);
+/* Host only: the label filter of src/vision/mod.rs:161-186 and the ladder of mpx_ratio.rs:91-125 on what the host has read.
+ * labels: n records in OCR order (the order of label[]), meters[i]: the number read in label i's crop, 0: "not a label" (what the
+ * reference skips: no trailing m, not a number, zero).  *out (optional) receives the anchors of a SMHV_STAGE_SCALES run: the first
+ * SMHV_MAX_SCALES distinct non-zero values in order, {meters, (left + right) / 2, bottom} each, and scales_start_y = the minimum
+ * bottom over the non-zero entries met up to and including the one that filled the list (the reference's loop breaks there);
+ * n = 0, scales_start_y = 0 when there is none.  *mpx, *has (optional): the mean of meters / width over those anchors, summed in
+ * order -- every anchor taken here has a bar, so this is the record's mpx after that run, bit for bit; *has = 0: no anchor. */
+SMHV_API int smhv_scale_labels_anchors(const smhv_scale_label *labels, uint32_t n, const uint32_t *meters, smhv_anchors *out, double *mpx, int *has);
 
 #ifdef __cplusplus
 }

@@ -176,6 +176,22 @@ class ClearanceMapResult(C.Structure):
     _fields_ = [("valid", C.c_uint32), ("reserved", C.c_uint32), ("origin", C.c_float * 2), ("count", C.c_uint32 * 3), ("los_blocked", C.c_uint32)]
 
 
+MAX_SCALE_LABELS, LABEL_MAX_RUNS, LABEL_CROP_W, LABEL_CROP_H = 8, 4096, 128, 32
+LABELS_RUNS_OVERFLOW = 1                                               # smhv_scale_label_frame.flags
+
+
+class ScaleLabel(C.Structure):
+    """smhv_scale_label: a word's box, the scale bar under it and the bar's width (32 bytes)."""
+    _fields_ = [("left", C.c_uint32), ("top", C.c_uint32), ("right", C.c_uint32), ("bottom", C.c_uint32), ("bar_left", C.c_uint32), ("bar_y", C.c_uint32),
+                ("bar_right", C.c_uint32), ("width", C.c_uint32)]
+
+
+class ScaleLabelFrame(C.Structure):
+    """smhv_scale_label_frame: a frame's scale labels (288 bytes)."""
+    _fields_ = [("n", C.c_uint32), ("n_found", C.c_uint32), ("n_words", C.c_uint32), ("n_runs", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3),
+                ("label", ScaleLabel * MAX_SCALE_LABELS)]
+
+
 TEXT_MAX_RUNS, TEXT_MAX_BYTES, TEXT_MAX_LINES, TEXT_MAP_COORDS = 64, 64, 8, 1
 MAX_PROBES = 16
 DEBUG_DRAW_PROBES, DEBUG_MINIMAP_CAPTION = 1, 2   # smhv_debug_options.flags
@@ -397,6 +413,12 @@ SIGNATURES = {
     "smhv_batch_clearance_map_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "smhv_clearance_map": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(ClearanceOptionsStruct), C.POINTER(C.c_uint32), C.c_void_p,
                                      C.c_void_p, C.POINTER(ClearanceMapResult)]),
+    "smhv_batch_scale_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "smhv_batch_read_scale_labels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ScaleLabelFrame), C.c_void_p]),
+    "smhv_batch_scale_labels_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "smhv_scale_labels": (C.c_int, [C.c_void_p, C.POINTER(ScaleLabelFrame), C.c_void_p]),
+    "smhv_scale_labels_anchors": (C.c_int, [C.POINTER(ScaleLabel), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(Anchors), C.POINTER(C.c_double),
+                                            C.POINTER(C.c_int)]),
     "smhv_debug_render_form": (C.c_int, [C.c_uint32]),
     "smhv_debug_render_rule": (C.c_int, [C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

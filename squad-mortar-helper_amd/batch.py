@@ -384,6 +384,26 @@ class FrameBatch:
         L.check(self._lib.smhv_batch_clearance_map_ptr(self._b, C.byref(d)))
         return d.value or 0
 
+    def scale_labels(self, frames_ptr, n, stream=0):
+        """The scale labels of frames [0, n) (smhv_batch_scale_labels), on `stream` behind this batch's run over the same frames
+        (frames_ptr: what that run was given; its stages must include STAGE_OCR).  Asynchronous; read_scale_labels() waits for it."""
+        L.check(self._lib.smhv_batch_scale_labels(self._b, C.c_void_p(frames_ptr), n, C.c_void_p(stream)))
+
+    def read_scale_labels(self, first=0, n=None, crops=True):
+        """Synchronising host copy of the label and crop slabs -> (a ctypes array of n ScaleLabelFrame, uint8 [n, MAX_SCALE_LABELS,
+        LABEL_CROP_H, LABEL_CROP_W] or None); of a frame's cells only the first ScaleLabelFrame.n are its own."""
+        n = self.max_frames - first if n is None else n
+        out = (L.ScaleLabelFrame * n)()
+        cells = np.empty((n, L.MAX_SCALE_LABELS, L.LABEL_CROP_H, L.LABEL_CROP_W), np.uint8) if crops else None
+        L.check(self._lib.smhv_batch_read_scale_labels(self._b, first, n, out, cells.ctypes.data if cells is not None else None))
+        return out, cells
+
+    def scale_labels_ptr(self):
+        """Device addresses of the label slab (one smhv_scale_label_frame per frame) and the crop slab."""
+        d, c = C.c_void_p(), C.c_void_p()
+        L.check(self._lib.smhv_batch_scale_labels_ptr(self._b, C.byref(d), C.byref(c)))
+        return d.value or 0, c.value or 0
+
     def probe(self, options, points, first=0, n=None, stream=None):
         """The vision debugger's numbers of frames [first, first + n) at `points` = [(mx, my)] window positions (at most
         MAX_PROBES) through the viewport of `options` (a RenderOptions), on `stream` (smhv_batch_probe): no pixels.  Asynchronous;

@@ -297,6 +297,19 @@ struct ClearMapRun {
 	uint32_t per_call, has_mm;           // 1: mm / has_mm are the call's and aux, res are not read
 	uint32_t pal[4];                     // out_of_range, clear, blocked, los: R, G, B, a as a little-endian word
 };
+// smhv_batch_scale_labels / smhv_scale_labels (k_scale_labels: smh_scalelabels.hip): the scale labels of n frames, one workgroup
+// each.  Launch arguments, taken by value at the launch.
+#define SMH_SL_MAX_DIM 2048u             // the quadrant's padded row and its height, at most: a row is two 16-byte loads per lane of a wave
+struct ScaleLabelsRun {
+	const FrameAux *aux;                 // per frame: open
+	const uint8_t *ocr;                  // P: the ocr_preprocess slab at the first frame of the call (pixel x of a row at byte q_xoff + x)
+	const uint8_t *s0;                   // S0: find_scales_preprocess with start row 0, the same layout
+	smhv_scale_label_frame *out;         // the label slab, at the first frame of the call
+	uint8_t *crops;                      // the crop slab: SMHV_LABEL_FRAME_CROP_BYTES per frame
+	uint64_t stride;                     // bytes between two frames' planes
+	uint32_t pitch, q_xoff, qw, qh;      // the planes' row pitch in bytes (a multiple of 64, at most SMH_SL_MAX_DIM), the quadrant
+	uint32_t gap;                        // g
+};
 // smhv_batch_probe / smhv_batch_render_debug / smhv_render_map_debug (k_probe, k_debug_plan, k_debug_draw: smh_debugtext.hip): the
 // vision debugger's numbers and the debug text of n frames.  Launch arguments, taken by value at the launch.
 #define SMH_DBG_ITEMS (SMHV_TEXT_MAX_RUNS + 1u + 4u * SMHV_MAX_PROBES)   // a frame's item list: the runs, the caption, four per probe
@@ -584,6 +597,9 @@ hipError_t launch_reach(const ReachRun &r, uint32_t n, bool paint, bool classes,
 // k_clear_map<paint, bytes> over n frames (at most 65,535 each: a grid dimension)
 hipError_t launch_clear_lines(const ClearLinesRun &r, uint32_t n, hipStream_t s);
 hipError_t launch_clear_map(const ClearMapRun &r, uint32_t n, bool paint, bool bytes, hipStream_t s);
+// scale labels (smh_scalelabels.hip): k_scale_labels over n frames; gap: the rule's g for a quadrant qw wide (host)
+hipError_t launch_scale_labels(const ScaleLabelsRun &r, uint32_t n, hipStream_t s);
+uint32_t scale_labels_gap(uint32_t qw);
 // the vision debugger and the debug text (smh_debugtext.hip): k_probe over n frames; with r.img also k_debug_plan and k_debug_draw
 hipError_t launch_debug_text(const Geom &g, const DebugRun &r, uint32_t n, hipStream_t s);
 void render_set_form(uint32_t form);

@@ -277,6 +277,11 @@ struct smhv_batch {
 	smhv_clearance_result *d_clear = nullptr;
 	smhv_clearance_map_result *d_clear_map = nullptr;
 	smhv_heightmap *clear_hm = nullptr, *clear_map_hm = nullptr;
+	// smhv_batch_scale_labels: the label slab, the crop slab and the family's own find_scales_preprocess plane with start row 0
+	// (allocated by the first call); what the batch's most recent run covered (its stages and frame count)
+	smhv_scale_label_frame *d_sl = nullptr;
+	uint8_t *d_sl_crops = nullptr, *d_sl_s0 = nullptr;
+	uint32_t run_stages = 0, run_n = 0;
 	// smhv_batch_probe / smhv_batch_render_debug: the probe slab, the item lists and the string pool of the draw (allocated by the
 	// first call), the runs' and points' way to the device (one pinned block, one device block: the runs, then the points), the
 	// event of the most recent copy and the event behind the most recent call's kernels (they read the device block)
@@ -338,7 +343,7 @@ struct smhv_ctx {
 	FrameAux *h_aux = nullptr;
 	uint32_t *h_bars = nullptr;
 	// per-frame state
-	bool cropped = false, map_open = false, isolated = false, mask_valid = false, scales_valid = false;
+	bool cropped = false, map_open = false, isolated = false, mask_valid = false, scales_valid = false, ocr_valid = false;
 	// sector culling tables of k_lsd, one per gap threshold T = ceil(max_gap) seen so far (built on first use)
 	static constexpr int SECTOR_CACHE = 8;
 	uint32_t sector_T[SECTOR_CACHE] = {};
@@ -681,7 +686,8 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	(void)hipDeviceSynchronize();
 	void *ptrs[] = {b->d_ui, b->d_ui_luma, b->d_ui_form, b->d_mask, b->d_bits, b->d_tiled, b->d_occ, b->d_ocr, b->d_scales, b->d_aux, b->d_results, b->d_anchors, b->d_bars, b->d_farm,
 	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run, b->d_overlay, b->d_render, b->d_prims, b->d_labels,
-	                b->d_label_cull, b->d_label_extra, b->d_probes, b->d_dbg_items, b->d_dbg_pool, b->d_dbg_stage, b->d_reach, b->d_clear, b->d_clear_map};
+	                b->d_label_cull, b->d_label_extra, b->d_probes, b->d_dbg_items, b->d_dbg_pool, b->d_dbg_stage, b->d_reach, b->d_clear, b->d_clear_map,
+	                b->d_sl, b->d_sl_crops, b->d_sl_s0};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	if (b->h_prims) (void)hipHostFree(b->h_prims);
@@ -1125,6 +1131,7 @@ static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint3
 	if (mflags & MAP_MASK) b->mask_written = true;             // (... and the slabs smhv_batch_render_layers can take as the map)
 	if (qflags & BRQ_OCR) b->ocr_written = true;
 	if (qflags & BRQ_SCALES) b->scales_written = true;
+	b->run_stages = stages; b->run_n = n;                       // (smhv_batch_scale_labels: was the ocr plane of these frames written)
 	STAGE_BEGIN(2, s);
 	if (qflags && !mflags) HIPCHK(launch_brq_pass(g, bf, n, qflags, 0, 1, s));
 	STAGE_END(2, s);
@@ -2148,6 +2155,7 @@ extern "C" SMHV_API int smhv_trait_times(smhv_ctx *c, uint64_t ns[SMHV_TRAIT_CAL
 
 static void reset_frame_state(smhv_ctx *c) {
 	c->have_frame = true; c->cropped = false; c->map_open = false; c->isolated = false; c->mask_valid = false; c->minimap_cached = false;
+	c->ocr_valid = false;
 }
 
 extern "C" SMHV_API int smhv_load_frame(smhv_ctx *c, const uint8_t *bgra, uint32_t w, uint32_t h) {
@@ -2343,6 +2351,7 @@ extern "C" SMHV_API int smhv_ocr_preprocess(smhv_ctx *c, const uint8_t **out, si
 	HIPCHK(launch_brq_pass(g, bf, 1, BRQ_OCR, 0, 0, s));
 	rc = copy_image_d2h(c, 1, c->h_ocr, b->d_ocr, g.ocr_pitch, g.q_xoff, g.qw, g.qh, s);
 	if (rc) return rc;
+	c->ocr_valid = true;
 	*out = c->h_ocr; *len = (size_t)g.qw * g.qh;
 	return SMHV_OK;
 }
@@ -3347,3 +3356,4 @@ extern "C" SMHV_API int smhv_heightmap_overlay(smhv_ctx *c, const smhv_heightmap
 #include "smh_debugtext.inc"
 #include "smh_reach.inc"
 #include "smh_clear.inc"
+#include "smh_scalelabels.inc"

@@ -110,6 +110,12 @@ def ocr_box_prims(boxes, brq_w, brq_h):
     return out
 
 
+def scale_label_prims(labels, brq_w, brq_h, confidence=100.0):
+    """The boxes of the scale labels the device found (ScaleLabel records) as the OCR overlay draws its hits: ocr_box_prims on
+    (left, top, right, bottom, confidence).  The device reads no glyphs, so the confidence -- the colour -- is the caller's."""
+    return ocr_box_prims([(lb.left, lb.top, lb.right, lb.bottom, confidence) for lb in labels], brq_w, brq_h)
+
+
 def scale_bar_prims(bars, brq_w, brq_h):
     """The Debug menu's scale overlay (debug.rs:306-320): bars = [(left, y, right, found)] as calc_meters_to_px_ratio(...,
     want_bars=True) returns them, moved by (brq_w, brq_h) (mod.rs:205-210); 2 px magenta lines above everything.  Bars that

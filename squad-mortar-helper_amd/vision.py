@@ -168,6 +168,14 @@ class HipVision:
             return r, [tuple(bars[i * 4:i * 4 + 4]) for i in range(len(sc))]
         return r
 
+    def scale_labels(self, crops=True):
+        """The scale labels of the frame ocr_preprocess last ran on (smhv_scale_labels): the words with a scale bar beneath
+        them -> (ScaleLabelFrame, uint8 [n, LABEL_CROP_H, LABEL_CROP_W] or None: the glyph crops of its n labels)."""
+        rec = L.ScaleLabelFrame()
+        cells = np.full((L.MAX_SCALE_LABELS, L.LABEL_CROP_H, L.LABEL_CROP_W), 255, np.uint8) if crops else None
+        L.check(self._lib.smhv_scale_labels(self._ctx, C.byref(rec), cells.ctypes.data if cells is not None else None))
+        return rec, (cells[:rec.n] if cells is not None else None)
+
     # -- trait: markers branch ----------------------------------------------------------------
     def isolate_map_markers(self):
         L.check(self._lib.smhv_isolate_map_markers(self._ctx))
@@ -411,6 +419,27 @@ def parse_ocr_labels(ocr_results, max_scales=3):
     return scales, start_y
 
 
+def scale_label_hits(labels, texts):
+    """The scale labels of a frame as OCR hits for parse_ocr_labels: labels = the n ScaleLabel records (a ScaleLabelFrame's
+    label[:n], or anything with left / top / right / bottom), texts = what the host read in their crops, one string each."""
+    if len(texts) != len(labels):
+        raise ValueError("%d texts for %d labels" % (len(texts), len(labels)))
+    return [dict(text=str(t), left=int(lb.left), top=int(lb.top), right=int(lb.right), bottom=int(lb.bottom)) for lb, t in zip(labels, texts)]
+
+
+def scale_labels_anchors(labels, meters):
+    """smhv_scale_labels_anchors: labels = n ScaleLabel records, meters = the number read in each crop (0: not a label) ->
+    (Anchors for a STAGE_SCALES run, meters per pixel or None)."""
+    n = len(labels)
+    if len(meters) != n:
+        raise ValueError("%d numbers for %d labels" % (len(meters), n))
+    arr = (L.ScaleLabel * max(n, 1))(*labels)
+    m = (C.c_uint32 * max(n, 1))(*[int(v) for v in meters])
+    an, mpx, has = L.Anchors(), C.c_double(), C.c_int()
+    L.check(L.load().smhv_scale_labels_anchors(arr, n, m, C.byref(an), C.byref(mpx), C.byref(has)))
+    return an, (mpx.value if has.value else None)
+
+
 class VisionState:
     """Caller contract of src/vision/mod.rs:36-240: load_frame, crop_to_map (None => frame skipped),
     then the markers branch and the scales branch CONCURRENTLY on two threads, each calling
@@ -471,10 +500,12 @@ class VisionState:
         except Exception:  # noqa: BLE001
             pass
 
-    def process(self, vision, frame, ocr_labels=None, debug_view=DebugView.NONE, ocr=None):
+    def process(self, vision, frame, ocr_labels=None, debug_view=DebugView.NONE, ocr=None, label_reader=None):
         """ocr_labels: [(meters, x, y)] label anchors, or `ocr`: a callable (image uint8[h,w], w, h) -> OCR hits
         (text/left/right/bottom) that plays the part of the reference's Tesseract call (`ocr::read`, mod.rs:169);
-        its hits go through parse_ocr_labels exactly like the reference filters them."""
+        its hits go through parse_ocr_labels exactly like the reference filters them.  Or `label_reader`: a callable
+        (crop uint8[32,128], box (left, top, right, bottom)) -> str that reads the glyphs of one scale label the device
+        found (HipVision.scale_labels); the labels with their texts are the hits parse_ocr_labels filters."""
         vision.load_frame(frame)
         cropped = vision.crop_to_map(self.grayscale_map, lazy=self.lazy_map)
         if cropped is None:
@@ -498,7 +529,15 @@ class VisionState:
             try:
                 vision.thread_ctx()
                 out["ocr"] = vision.ocr_preprocess()
-                if ocr is not None:
+                if label_reader is not None:
+                    rec, cells = vision.scale_labels()
+                    found = [rec.label[i] for i in range(rec.n)]
+                    texts = [label_reader(cells[i], (lb.left, lb.top, lb.right, lb.bottom)) for i, lb in enumerate(found)]
+                    out["scale_labels"] = rec
+                    labels, start_y = parse_ocr_labels(scale_label_hits(found, texts))
+                    if not labels:
+                        return
+                elif ocr is not None:
                     h_, w_ = out["ocr"].shape
                     labels, start_y = parse_ocr_labels(ocr(out["ocr"], w_, h_))
                     if not labels:
