@@ -1404,6 +1404,100 @@ SMHV_API int smhv_scale_labels(smhv_ctx *ctx, smhv_scale_label_frame *out, uint8
  * order -- every anchor taken here has a bar, so this is the record's mpx after that run, bit for bit; *has = 0: no anchor. */
 SMHV_API int smhv_scale_labels_anchors(const smhv_scale_label *labels, uint32_t n, const uint32_t *meters, smhv_anchors *out, double *mpx, int *has);
 
+/* ---- scale labels: text -- the glyphs of a label read on the device against the caller's glyph atlas ------------------------------
+ * A label is a handful of glyphs of one fixed font at the caller's resolution.  The library ships no glyph shapes: a caller who has
+ * read one frame's labels once (by eye, with an OCR engine, through label_reader=) turns them into templates with
+ * smhv_glyph_templates_from_label, and every later frame is read on the device.  The rule (csrc/smh_glyph_rule.h is its one text,
+ * for the kernel, the host helpers and a stand-alone check), integers only:
+ *   input      label i < n of a smhv_scale_label_frame and its cell; w = right - left, h = bottom - top.  Foreground is P != 255.  Only
+ *              columns [0, w) and rows [0, h) of the cell are looked at (w <= 128, h <= 32 by the candidates' limits).
+ *   glyphs     the maximal runs of columns that hold a foreground pixel, left to right.  A glyph's bitmap is its tight box: the run's
+ *              columns, from the first to the last non-empty row inside the run.  A label with more than SMHV_LABEL_MAX_GLYPHS glyphs
+ *              has SMHV_LABEL_TEXT_TOO_MANY set, n_glyphs = the true count, and nothing else: empty text, meters 0, every per-glyph
+ *              field 0.  A glyph wider than 32 columns is unmatched: character '?', best = second = 0xFFFF, tmpl = 0xFF.
+ *   template   smhv_glyph_template: bit x of rows[y] is foreground.  code is printable ASCII 0x21 .. 0x7E and not '?';
+ *              1 <= w, h <= 32; the box is tight (row 0, row h - 1, column 0 and column w - 1 are non-empty) and no bit lies outside
+ *              it (rows[y] for y >= h is 0).  An atlas holds 1 .. SMHV_ATLAS_MAX_TEMPLATES templates; several may share a code.
+ *   distance   of glyph G to template T: the minimum over (dx, dy) in {-1, 0, 1}^2 of the number of positions of the plane at which
+ *              G moved by (dx, dy) differs from T.  Both are anchored at their box's top-left corner; everything outside a box is
+ *              background.  (The shifts are taken dy-major, dx-minor; only the minimum is kept.)
+ *   choice     the winner is the template of least distance, ties to the lowest index; best = its distance.  second = the least
+ *              distance over the templates whose code differs from the winner's (0xFFFF: none).  The glyph is accepted when
+ *              best * accept_den <= accept_num * fg(winner) in u32 arithmetic, fg = the template's foreground count; the defaults are
+ *              1 and 3.  An accepted glyph prints the winner's code, any other '?' -- best, second and tmpl are kept either way.
+ *   meters     the filter of src/vision/mod.rs:161-173 on the text: p = rfind('m'); text[0, p) must parse as u32::from_str does (an
+ *              optional single '+', then one or more digits, no overflow); anything else -- no 'm', an empty prefix, another
+ *              character (a '?' among them), a value above 4294967295 -- is 0, and so is the value 0.  What follows the last 'm' is
+ *              ignored, as the reference ignores it.
+ *   frame      smhv_scale_labels_anchors' rule on the meters just read, labels in order: anchors, has, mpx (the mean of
+ *              meters / width summed in order in f64; 0.0 when has == 0).  A closed frame or a SMHV_LABELS_RUNS_OVERFLOW frame has
+ *              n = 0 labels: its record is all zeros.
+ * label[i] for i >= n, and every per-glyph field k >= min(n_glyphs, SMHV_LABEL_MAX_GLYPHS), is zero. */
+#define SMHV_LABEL_MAX_GLYPHS 16u
+#define SMHV_ATLAS_MAX_TEMPLATES 32u
+#define SMHV_LABEL_TEXT_TOO_MANY 1u      /* smhv_label_text_entry.flags */
+typedef struct {
+	uint8_t code, w, h, reserved;        /*  0 */
+	uint32_t rows[32];                   /*  4: bit x of rows[y] */
+} smhv_glyph_template;                   /* 132 bytes */
+typedef struct {
+	uint32_t accept_num, accept_den;     /* accepted: best * accept_den <= accept_num * fg(winner); defaults 1, 3 */
+} smhv_glyph_atlas_options;
+typedef struct {
+	char text[SMHV_LABEL_MAX_GLYPHS];    /*  0: a character per glyph, zero-padded (16 glyphs: no terminator) */
+	uint32_t n_glyphs;                   /* 16: the true count */
+	uint32_t flags;                      /* 20: SMHV_LABEL_TEXT_TOO_MANY */
+	uint32_t meters;                     /* 24: 0: not a label */
+	uint32_t reserved;                   /* 28 */
+	uint16_t best[SMHV_LABEL_MAX_GLYPHS];   /* 32 */
+	uint16_t second[SMHV_LABEL_MAX_GLYPHS]; /* 64 */
+	uint8_t tmpl[SMHV_LABEL_MAX_GLYPHS];    /* 96: the winner's index in the atlas */
+} smhv_label_text_entry;                    /* 112 bytes */
+typedef struct {
+	uint32_t n;                          /*  0: the labels of the frame (smhv_scale_label_frame.n) */
+	uint32_t has;                        /*  4: 1: anchors.n > 0, mpx is a number */
+	double mpx;                          /*  8 */
+	smhv_anchors anchors;                /* 16: 44 bytes */
+	uint32_t reserved;                   /* 60 */
+	smhv_label_text_entry label[SMHV_MAX_SCALE_LABELS]; /* 64 */
+} smhv_label_text_frame;                 /* 960 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(smhv_glyph_template) == 132 && sizeof(smhv_anchors) == 44, "glyph template / anchors layout");
+static_assert(sizeof(smhv_label_text_entry) == 112 && offsetof(smhv_label_text_entry, n_glyphs) == 16 && offsetof(smhv_label_text_entry, meters) == 24 &&
+              offsetof(smhv_label_text_entry, best) == 32 && offsetof(smhv_label_text_entry, second) == 64 && offsetof(smhv_label_text_entry, tmpl) == 96, "smhv_label_text_entry layout");
+static_assert(sizeof(smhv_label_text_frame) == 960 && offsetof(smhv_label_text_frame, mpx) == 8 && offsetof(smhv_label_text_frame, anchors) == 16 &&
+              offsetof(smhv_label_text_frame, label) == 64, "smhv_label_text_frame layout");
+#endif
+typedef struct smhv_glyph_atlas smhv_glyph_atlas;
+/* Host only: are these n templates an atlas (the conditions under "template", 1 <= n <= SMHV_ATLAS_MAX_TEMPLATES)?  SMHV_E_INVALID
+ * names the first template that is not. */
+SMHV_API int smhv_glyph_templates_check(const smhv_glyph_template *templates, uint32_t n);
+/* Host only, the learning helper: cuts one label by the rule (crop: its cell of SMHV_LABEL_CROP_BYTES bytes) and pairs glyph k with
+ * text[k]; out receives *n templates (room for SMHV_LABEL_MAX_GLYPHS).  SMHV_E_INVALID: the glyph count differs from strlen(text) or
+ * exceeds SMHV_LABEL_MAX_GLYPHS, a glyph is wider than 32 columns, a character is not allowed as a code, a box larger than a cell. */
+SMHV_API int smhv_glyph_templates_from_label(const uint8_t *crop, const smhv_scale_label *label, const char *text, smhv_glyph_template *out, uint32_t *n);
+/* A device-resident atlas, like smhv_heightmap: usable by every batch, pipeline slot and per-call path of its context's device until
+ * destroyed (destroy waits for the device).  options NULL: the defaults.  SMHV_E_INVALID: what smhv_glyph_templates_check rejects,
+ * accept_den == 0. */
+SMHV_API int smhv_glyph_atlas_create(smhv_ctx *ctx, const smhv_glyph_template *templates, uint32_t n, const smhv_glyph_atlas_options *options, smhv_glyph_atlas **out);
+SMHV_API void smhv_glyph_atlas_destroy(smhv_glyph_atlas *atlas);
+/* The texts of frames [0, n), asynchronously on `stream`, behind smhv_batch_scale_labels of this batch over at least n frames
+ * (SMHV_E_STATE otherwise) -- a plain batch, or a pipeline slot's batch after smhv_pipeline_wait.  The records go to the batch's text
+ * slab, the frames' anchors tightly packed to its label-anchor slab (both allocated by the first call).  SMHV_E_INVALID: null
+ * arguments, n == 0 or beyond the batch's capacity, an atlas of another device.  A failed call enqueues nothing. */
+SMHV_API int smhv_batch_label_text(smhv_batch *b, const smhv_glyph_atlas *atlas, uint32_t n, void *stream);
+/* read: a synchronising host copy of the records of frames [first, first + n); ptr: the device addresses of the text slab and of the
+ * smhv_anchors array, either may be NULL (SMHV_E_STATE before the first smhv_batch_label_text). */
+SMHV_API int smhv_batch_read_label_text(smhv_batch *b, uint32_t first, uint32_t n, smhv_label_text_frame *out);
+SMHV_API int smhv_batch_label_text_ptr(smhv_batch *b, void **d_text, void **d_anchors);
+/* The per-call form, after smhv_scale_labels on the same frame (SMHV_E_STATE otherwise). */
+SMHV_API int smhv_label_text(smhv_ctx *ctx, const smhv_glyph_atlas *atlas, smhv_label_text_frame *out);
+/* smhv_batch_run with the anchors the batch's last smhv_batch_label_text wrote (SMHV_E_STATE: none, or over fewer than n frames):
+ * where smhv_batch_run copies the caller's anchors from pinned staging, this copies the label-anchor slab device to device on the
+ * same stream; nothing else of the run differs, so the records equal those of smhv_batch_run given the same anchors by the host.
+ * The frames' meters never visit the host.  (Pipelines take host anchors only.) */
+SMHV_API int smhv_batch_run_label_anchors(smhv_batch *b, const void *d_frames, uint32_t n, uint32_t stages, int grayscale, uint32_t max_gap, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

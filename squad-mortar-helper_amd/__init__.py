@@ -19,6 +19,8 @@ from .render import ClearanceOptions  # noqa: F401
 from .render import scale_label_prims  # noqa: F401
 from .vision import scale_label_hits, scale_labels_anchors  # noqa: F401
 from ._lib import LABEL_CROP_H, LABEL_CROP_W, LABEL_MAX_RUNS, LABELS_RUNS_OVERFLOW, MAX_SCALE_LABELS, ScaleLabel, ScaleLabelFrame  # noqa: F401
+from .glyphs import GlyphAtlas, entry_text, glyph_templates_check, glyph_templates_from_label  # noqa: F401
+from ._lib import ATLAS_MAX_TEMPLATES, LABEL_MAX_GLYPHS, LABEL_TEXT_TOO_MANY, GlyphTemplate, LabelTextEntry, LabelTextFrame  # noqa: F401
 from .render import DebugOptions, ocr_text_runs, probe_points, probe_text, rust_debug_str, scale_text_runs, text_run  # noqa: F401
 from ._lib import DEBUG_DRAW_PROBES, DEBUG_MINIMAP_CAPTION, MAX_PROBES, TEXT_MAP_COORDS, TEXT_MAX_BYTES, TEXT_MAX_LINES, TEXT_MAX_RUNS  # noqa: F401
 from ._lib import LAYER_MINIMAP_BOUNDS, PRIM_FOREGROUND, PRIM_LINE, PRIM_RECT, PRIM_SHIFT1, RENDER_MAX_PRIMS  # noqa: F401

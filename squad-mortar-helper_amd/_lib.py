@@ -192,6 +192,33 @@ class ScaleLabelFrame(C.Structure):
                 ("label", ScaleLabel * MAX_SCALE_LABELS)]
 
 
+LABEL_MAX_GLYPHS, ATLAS_MAX_TEMPLATES = 16, 32
+LABEL_TEXT_TOO_MANY = 1                                                # smhv_label_text_entry.flags
+
+
+class GlyphTemplate(C.Structure):
+    """smhv_glyph_template: a glyph's code and its tight bitmap, bit x of rows[y] (132 bytes)."""
+    _fields_ = [("code", C.c_uint8), ("w", C.c_uint8), ("h", C.c_uint8), ("reserved", C.c_uint8), ("rows", C.c_uint32 * 32)]
+
+
+class GlyphAtlasOptions(C.Structure):
+    _fields_ = [("accept_num", C.c_uint32), ("accept_den", C.c_uint32)]
+
+
+class LabelTextEntry(C.Structure):
+    """smhv_label_text_entry: a label's text as the device read it (112 bytes)."""
+    _fields_ = [("text", C.c_char * LABEL_MAX_GLYPHS), ("n_glyphs", C.c_uint32), ("flags", C.c_uint32), ("meters", C.c_uint32), ("reserved", C.c_uint32),
+                ("best", C.c_uint16 * LABEL_MAX_GLYPHS), ("second", C.c_uint16 * LABEL_MAX_GLYPHS), ("tmpl", C.c_uint8 * LABEL_MAX_GLYPHS)]
+
+
+class LabelTextFrame(C.Structure):
+    """smhv_label_text_frame: a frame's label texts, its anchors and meters per pixel (960 bytes)."""
+    _fields_ = [("n", C.c_uint32), ("has", C.c_uint32), ("mpx", C.c_double), ("anchors", Anchors), ("reserved", C.c_uint32),
+                ("label", LabelTextEntry * MAX_SCALE_LABELS)]
+
+
+assert C.sizeof(GlyphTemplate) == 132 and C.sizeof(LabelTextEntry) == 112 and C.sizeof(LabelTextFrame) == 960
+
 TEXT_MAX_RUNS, TEXT_MAX_BYTES, TEXT_MAX_LINES, TEXT_MAP_COORDS = 64, 64, 8, 1
 MAX_PROBES = 16
 DEBUG_DRAW_PROBES, DEBUG_MINIMAP_CAPTION = 1, 2   # smhv_debug_options.flags
@@ -417,6 +444,15 @@ SIGNATURES = {
     "smhv_batch_read_scale_labels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ScaleLabelFrame), C.c_void_p]),
     "smhv_batch_scale_labels_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "smhv_scale_labels": (C.c_int, [C.c_void_p, C.POINTER(ScaleLabelFrame), C.c_void_p]),
+    "smhv_glyph_templates_check": (C.c_int, [C.POINTER(GlyphTemplate), C.c_uint32]),
+    "smhv_glyph_templates_from_label": (C.c_int, [C.c_void_p, C.POINTER(ScaleLabel), C.c_char_p, C.POINTER(GlyphTemplate), C.POINTER(C.c_uint32)]),
+    "smhv_glyph_atlas_create": (C.c_int, [C.c_void_p, C.POINTER(GlyphTemplate), C.c_uint32, C.POINTER(GlyphAtlasOptions), C.POINTER(C.c_void_p)]),
+    "smhv_glyph_atlas_destroy": (None, [C.c_void_p]),
+    "smhv_batch_label_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "smhv_batch_read_label_text": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(LabelTextFrame)]),
+    "smhv_batch_label_text_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "smhv_label_text": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(LabelTextFrame)]),
+    "smhv_batch_run_label_anchors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p]),
     "smhv_scale_labels_anchors": (C.c_int, [C.POINTER(ScaleLabel), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(Anchors), C.POINTER(C.c_double),
                                             C.POINTER(C.c_int)]),
     "smhv_debug_render_form": (C.c_int, [C.c_uint32]),

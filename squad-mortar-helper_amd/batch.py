@@ -404,6 +404,28 @@ class FrameBatch:
         L.check(self._lib.smhv_batch_scale_labels_ptr(self._b, C.byref(d), C.byref(c)))
         return d.value or 0, c.value or 0
 
+    def label_text(self, atlas, n, stream=0):
+        """The texts of the scale labels of frames [0, n) read against `atlas` (a GlyphAtlas; smhv_batch_label_text), on `stream`
+        behind scale_labels() over at least n frames.  Asynchronous; read_label_text() waits for it."""
+        L.check(self._lib.smhv_batch_label_text(self._b, atlas._a, n, C.c_void_p(stream)))
+
+    def read_label_text(self, first=0, n=None):
+        """Synchronising host copy of the text slab -> a ctypes array of n LabelTextFrame."""
+        n = self.max_frames - first if n is None else n
+        out = (L.LabelTextFrame * n)()
+        L.check(self._lib.smhv_batch_read_label_text(self._b, first, n, out))
+        return out
+
+    def label_text_ptr(self):
+        """Device addresses of the text slab (one smhv_label_text_frame per frame) and of the frames' smhv_anchors, tightly packed."""
+        d, a = C.c_void_p(), C.c_void_p()
+        L.check(self._lib.smhv_batch_label_text_ptr(self._b, C.byref(d), C.byref(a)))
+        return d.value or 0, a.value or 0
+
+    def run_label_anchors(self, frames_ptr, n, stages=L.STAGE_ALL, grayscale=True, max_gap=15, stream=0):
+        """run() with the anchors the last label_text() left on the device (smhv_batch_run_label_anchors): the meters never visit the host."""
+        L.check(self._lib.smhv_batch_run_label_anchors(self._b, C.c_void_p(frames_ptr), n, stages, int(bool(grayscale)), max_gap, C.c_void_p(stream)))
+
     def probe(self, options, points, first=0, n=None, stream=None):
         """The vision debugger's numbers of frames [first, first + n) at `points` = [(mx, my)] window positions (at most
         MAX_PROBES) through the viewport of `options` (a RenderOptions), on `stream` (smhv_batch_probe): no pixels.  Asynchronous;

@@ -310,6 +310,16 @@ struct ScaleLabelsRun {
 	uint32_t pitch, q_xoff, qw, qh;      // the planes' row pitch in bytes (a multiple of 64, at most SMH_SL_MAX_DIM), the quadrant
 	uint32_t gap;                        // g
 };
+// smhv_batch_label_text / smhv_label_text (k_label_text: smh_labeltext.hip): the texts of n frames' scale labels, one workgroup each.
+// Launch arguments, taken by value at the launch.
+struct GlyphAtlas;                       // smh_glyph_rule.h
+struct LabelTextRun {
+	const smhv_scale_label_frame *labels; // the label slab, at the first frame of the call
+	const uint8_t *crops;                // the crop slab: SMHV_LABEL_FRAME_CROP_BYTES per frame
+	const GlyphAtlas *atlas;             // device
+	smhv_label_text_frame *out;          // the text slab
+	smhv_anchors *anchors;               // the frames' anchors, tightly packed
+};
 // smhv_batch_probe / smhv_batch_render_debug / smhv_render_map_debug (k_probe, k_debug_plan, k_debug_draw: smh_debugtext.hip): the
 // vision debugger's numbers and the debug text of n frames.  Launch arguments, taken by value at the launch.
 #define SMH_DBG_ITEMS (SMHV_TEXT_MAX_RUNS + 1u + 4u * SMHV_MAX_PROBES)   // a frame's item list: the runs, the caption, four per probe
@@ -600,6 +610,8 @@ hipError_t launch_clear_map(const ClearMapRun &r, uint32_t n, bool paint, bool b
 // scale labels (smh_scalelabels.hip): k_scale_labels over n frames; gap: the rule's g for a quadrant qw wide (host)
 hipError_t launch_scale_labels(const ScaleLabelsRun &r, uint32_t n, hipStream_t s);
 uint32_t scale_labels_gap(uint32_t qw);
+// scale labels: text (smh_labeltext.hip): k_label_text over n frames
+hipError_t launch_label_text(const LabelTextRun &r, uint32_t n, hipStream_t s);
 // the vision debugger and the debug text (smh_debugtext.hip): k_probe over n frames; with r.img also k_debug_plan and k_debug_draw
 hipError_t launch_debug_text(const Geom &g, const DebugRun &r, uint32_t n, hipStream_t s);
 void render_set_form(uint32_t form);

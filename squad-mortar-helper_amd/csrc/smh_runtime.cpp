@@ -30,6 +30,7 @@
 
 #include "smh_consts.h"
 #include "smh_kernels.h"
+#include "smh_glyph_rule.h"
 
 using namespace smh;
 
@@ -282,6 +283,11 @@ struct smhv_batch {
 	smhv_scale_label_frame *d_sl = nullptr;
 	uint8_t *d_sl_crops = nullptr, *d_sl_s0 = nullptr;
 	uint32_t run_stages = 0, run_n = 0;
+	// smhv_batch_label_text: the text slab and the frames' anchors, tightly packed (allocated by the first call); how many frames the
+	// most recent smhv_batch_scale_labels and smhv_batch_label_text covered
+	smhv_label_text_frame *d_lt = nullptr;
+	smhv_anchors *d_lt_anchors = nullptr;
+	uint32_t sl_n = 0, lt_n = 0;
 	// smhv_batch_probe / smhv_batch_render_debug: the probe slab, the item lists and the string pool of the draw (allocated by the
 	// first call), the runs' and points' way to the device (one pinned block, one device block: the runs, then the points), the
 	// event of the most recent copy and the event behind the most recent call's kernels (they read the device block)
@@ -344,6 +350,7 @@ struct smhv_ctx {
 	uint32_t *h_bars = nullptr;
 	// per-frame state
 	bool cropped = false, map_open = false, isolated = false, mask_valid = false, scales_valid = false, ocr_valid = false;
+	bool labels_valid = false;          // smhv_scale_labels has run on the frame of the last ocr_preprocess (smhv_label_text)
 	// sector culling tables of k_lsd, one per gap threshold T = ceil(max_gap) seen so far (built on first use)
 	static constexpr int SECTOR_CACHE = 8;
 	uint32_t sector_T[SECTOR_CACHE] = {};
@@ -687,7 +694,7 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	void *ptrs[] = {b->d_ui, b->d_ui_luma, b->d_ui_form, b->d_mask, b->d_bits, b->d_tiled, b->d_occ, b->d_ocr, b->d_scales, b->d_aux, b->d_results, b->d_anchors, b->d_bars, b->d_farm,
 	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run, b->d_overlay, b->d_render, b->d_prims, b->d_labels,
 	                b->d_label_cull, b->d_label_extra, b->d_probes, b->d_dbg_items, b->d_dbg_pool, b->d_dbg_stage, b->d_reach, b->d_clear, b->d_clear_map,
-	                b->d_sl, b->d_sl_crops, b->d_sl_s0};
+	                b->d_sl, b->d_sl_crops, b->d_sl_s0, b->d_lt, b->d_lt_anchors};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	if (b->h_prims) (void)hipHostFree(b->h_prims);
@@ -1030,7 +1037,8 @@ static int batch_materialize_ui(smhv_batch *b, hipStream_t stream) {
 struct SvcPublish { SvcCtl *ctl; unsigned long long *ring; SvcSlot *slots; uint32_t slot, seq, ring_log2; const uint32_t *cull_tab; bool have_cull; hipStream_t s_pro; hipEvent_t ev_pro;
                     bool *published; };   // <- set once k_svc_publish has been enqueued (from then on the device WILL complete the submission)
 static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint32_t stages, int grayscale, uint32_t max_gap,
-                          const smhv_anchors *anchors, hipStream_t s, hipStream_t sl, const SvcPublish *svc = nullptr) {
+                          const smhv_anchors *anchors, hipStream_t s, hipStream_t sl, const SvcPublish *svc = nullptr, const smhv_anchors *d_anchors_src = nullptr) {
+	// d_anchors_src (smhv_batch_run_label_anchors): the anchors are n records in device memory, and `anchors` is NULL
 	if (!b || !d_frames || n == 0 || n > b->max_frames) return fail(SMHV_E_INVALID, "bad arguments (n=%u, capacity %u)", n, b ? b->max_frames : 0);
 	if ((uintptr_t)d_frames & 3u) return fail(SMHV_E_INVALID, "d_frames is not aligned to a pixel (4 bytes)");
 	CTX_OPEN(b->ctx);
@@ -1059,9 +1067,10 @@ static int batch_run_impl(smhv_batch *b, const void *d_frames, uint32_t n, uint3
 		int rc = sector_table_for(b->ctx, max_gap, s, &bf);
 		if (rc) return rc;
 	}
-	const bool scales = (stages & SMHV_STAGE_SCALES) && anchors;
+	const bool scales = (stages & SMHV_STAGE_SCALES) && (anchors || d_anchors_src);
 	const hipStream_t sb = (svc && svc->s_pro) ? svc->s_pro : s;   // where the anchor upload and the button test go
-	if (scales) {
+	if (scales && d_anchors_src) HIPCHK(hipMemcpyAsync(b->d_anchors, d_anchors_src, sizeof(smhv_anchors) * n, hipMemcpyDeviceToDevice, sb));
+	else if (scales) {
 		// Pinned staging for the anchor upload (a pageable source would make hipMemcpyAsync synchronous).  A staging
 		// buffer is reused once the copy that read it has completed; if none is free another one is allocated, so this call
 		// never waits for the device.
@@ -2155,7 +2164,7 @@ extern "C" SMHV_API int smhv_trait_times(smhv_ctx *c, uint64_t ns[SMHV_TRAIT_CAL
 
 static void reset_frame_state(smhv_ctx *c) {
 	c->have_frame = true; c->cropped = false; c->map_open = false; c->isolated = false; c->mask_valid = false; c->minimap_cached = false;
-	c->ocr_valid = false;
+	c->ocr_valid = false; c->labels_valid = false;
 }
 
 extern "C" SMHV_API int smhv_load_frame(smhv_ctx *c, const uint8_t *bgra, uint32_t w, uint32_t h) {
@@ -2351,7 +2360,7 @@ extern "C" SMHV_API int smhv_ocr_preprocess(smhv_ctx *c, const uint8_t **out, si
 	HIPCHK(launch_brq_pass(g, bf, 1, BRQ_OCR, 0, 0, s));
 	rc = copy_image_d2h(c, 1, c->h_ocr, b->d_ocr, g.ocr_pitch, g.q_xoff, g.qw, g.qh, s);
 	if (rc) return rc;
-	c->ocr_valid = true;
+	c->ocr_valid = true; c->labels_valid = false;
 	*out = c->h_ocr; *len = (size_t)g.qw * g.qh;
 	return SMHV_OK;
 }
@@ -3357,3 +3366,4 @@ extern "C" SMHV_API int smhv_heightmap_overlay(smhv_ctx *c, const smhv_heightmap
 #include "smh_reach.inc"
 #include "smh_clear.inc"
 #include "smh_scalelabels.inc"
+#include "smh_labeltext.inc"

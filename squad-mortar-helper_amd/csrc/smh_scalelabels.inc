@@ -58,7 +58,9 @@ extern "C" SMHV_API int smhv_batch_scale_labels(smhv_batch *b, const void *d_fra
 	HIPCHK(hipSetDevice(b->ctx->device));
 	rc = scale_labels_slabs(b);
 	if (rc) return rc;
-	return scale_labels_enqueue(b, (const uint8_t *)d_frames, n, (hipStream_t)stream);
+	rc = scale_labels_enqueue(b, (const uint8_t *)d_frames, n, (hipStream_t)stream);
+	if (rc == SMHV_OK) b->sl_n = n;                            // (smhv_batch_label_text: the labels of these frames are on their way)
+	return rc;
 }
 
 extern "C" SMHV_API int smhv_batch_read_scale_labels(smhv_batch *b, uint32_t first, uint32_t n, smhv_scale_label_frame *out, uint8_t *crops) {
@@ -101,6 +103,7 @@ extern "C" SMHV_API int smhv_scale_labels(smhv_ctx *c, smhv_scale_label_frame *o
 	HIPCHK(hipMemcpyAsync(c->h_fire, b->d_sl, sizeof(smhv_scale_label_frame), hipMemcpyDeviceToHost, s));
 	if (crops) HIPCHK(hipMemcpyAsync(c->h_fire + rec, b->d_sl_crops, SMHV_LABEL_FRAME_CROP_BYTES, hipMemcpyDeviceToHost, s));
 	HIPCHK(wait_stream(s));
+	b->sl_n = 1; c->labels_valid = true;                       // (smhv_label_text)
 	memcpy(out, c->h_fire, sizeof *out);
 	if (crops) memcpy(crops, c->h_fire + rec, (size_t)std::min(out->n, (uint32_t)SMHV_MAX_SCALE_LABELS) * SMHV_LABEL_CROP_BYTES);
 	return SMHV_OK;
@@ -110,27 +113,12 @@ extern "C" SMHV_API int smhv_scale_labels(smhv_ctx *c, smhv_scale_label_frame *o
 extern "C" SMHV_API int smhv_scale_labels_anchors(const smhv_scale_label *labels, uint32_t n, const uint32_t *meters, smhv_anchors *out, double *mpx, int *has) {
 	if ((n && (!labels || !meters)) || n > 65536u) return fail(SMHV_E_INVALID, "scale_labels_anchors: bad arguments");
 	smhv_anchors an;
-	memset(&an, 0, sizeof an);
-	uint32_t start_y = 0xFFFFFFFFu;
-	double sum = 0.0;
-	for (uint32_t i = 0; i < n && an.n < (uint32_t)SMHV_MAX_SCALES; ++i) {
-		if (meters[i] == 0u) continue;                        // not a label: `Ok(0) | Err(_) => continue`
-		start_y = std::min(start_y, labels[i].bottom);
-		bool seen = false;
-		for (uint32_t k = 0; k < an.n; ++k) seen = seen || an.scales[k][0] == meters[i];
-		if (seen) continue;
-		const uint32_t width = labels[i].bar_right - labels[i].bar_left;
-		if (labels[i].bar_right <= labels[i].bar_left) return fail(SMHV_E_INVALID, "scale_labels_anchors: label %u has no bar (%u .. %u)", i, labels[i].bar_left, labels[i].bar_right);
-		an.scales[an.n][0] = meters[i];
-		an.scales[an.n][1] = (labels[i].left + labels[i].right) / 2u;
-		an.scales[an.n][2] = labels[i].bottom;
-		const double ratio = (double)meters[i] / (double)width;
-		sum = an.n ? sum + ratio : ratio;
-		++an.n;
-	}
-	an.scales_start_y = an.n ? start_y : 0u;
+	double ratio = 0.0;
+	uint32_t bad = 0;
+	if (!label_anchors(labels, n, meters, &an, &ratio, &bad))  // (smh_glyph_rule.h: the text the device runs on the meters it reads)
+		return fail(SMHV_E_INVALID, "scale_labels_anchors: label %u has no bar (%u .. %u)", bad, labels[bad].bar_left, labels[bad].bar_right);
 	if (out) *out = an;
 	if (has) *has = an.n ? 1 : 0;
-	if (mpx) *mpx = an.n == 0u ? 0.0 : (an.n == 1u ? sum : sum / (double)an.n);
+	if (mpx) *mpx = ratio;
 	return SMHV_OK;
 }

@@ -176,6 +176,13 @@ class HipVision:
         L.check(self._lib.smhv_scale_labels(self._ctx, C.byref(rec), cells.ctypes.data if cells is not None else None))
         return rec, (cells[:rec.n] if cells is not None else None)
 
+    def label_text(self, atlas):
+        """The texts of the labels scale_labels() last found, read on the device against `atlas` (a GlyphAtlas; smhv_label_text)
+        -> LabelTextFrame."""
+        rec = L.LabelTextFrame()
+        L.check(self._lib.smhv_label_text(self._ctx, atlas._a, C.byref(rec)))
+        return rec
+
     # -- trait: markers branch ----------------------------------------------------------------
     def isolate_map_markers(self):
         L.check(self._lib.smhv_isolate_map_markers(self._ctx))
@@ -505,7 +512,8 @@ class VisionState:
         (text/left/right/bottom) that plays the part of the reference's Tesseract call (`ocr::read`, mod.rs:169);
         its hits go through parse_ocr_labels exactly like the reference filters them.  Or `label_reader`: a callable
         (crop uint8[32,128], box (left, top, right, bottom)) -> str that reads the glyphs of one scale label the device
-        found (HipVision.scale_labels); the labels with their texts are the hits parse_ocr_labels filters."""
+        found (HipVision.scale_labels); the labels with their texts are the hits parse_ocr_labels filters.  A GlyphAtlas in
+        the callable's place has the device read the glyphs (HipVision.label_text); its texts go the same way."""
         vision.load_frame(frame)
         cropped = vision.crop_to_map(self.grayscale_map, lazy=self.lazy_map)
         if cropped is None:
@@ -530,9 +538,16 @@ class VisionState:
                 vision.thread_ctx()
                 out["ocr"] = vision.ocr_preprocess()
                 if label_reader is not None:
-                    rec, cells = vision.scale_labels()
+                    from .glyphs import GlyphAtlas, entry_text
+                    on_device = isinstance(label_reader, GlyphAtlas)
+                    rec, cells = vision.scale_labels(crops=not on_device)
                     found = [rec.label[i] for i in range(rec.n)]
-                    texts = [label_reader(cells[i], (lb.left, lb.top, lb.right, lb.bottom)) for i, lb in enumerate(found)]
+                    if on_device:                            # the device reads the glyphs: no crop comes down
+                        text_rec = vision.label_text(label_reader)
+                        texts = [entry_text(text_rec.label[i]) for i in range(rec.n)]
+                        out["label_text"] = text_rec
+                    else:
+                        texts = [label_reader(cells[i], (lb.left, lb.top, lb.right, lb.bottom)) for i, lb in enumerate(found)]
                     out["scale_labels"] = rec
                     labels, start_y = parse_ocr_labels(scale_label_hits(found, texts))
                     if not labels:
