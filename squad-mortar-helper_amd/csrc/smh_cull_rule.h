@@ -14,8 +14,8 @@
 //
 // The build applies the OUTER annulus alone unless it is compiled with -DSMH_CULL_CHAIN: the chain leaves 17 % fewer units on the
 // benchmark's scene (tools/cull_chain_count.py), but the scan of the second ring of pixels costs the search service more than
-// those units do, so it is kept, checked and counted, and not used.  SMH_CULL_ANNULI is what the table
-// holds and the kernels scan.
+// those units do -- pixel by pixel, and by runs (below) as well -- so it is kept, checked and counted, and
+// not used.  SMH_CULL_ANNULI is what the table holds and the kernels scan.
 //
 // The table maps a pixel offset (ox, oy) from floor(start point) to the units that could sample it, conservatively: the
 // sample may sit anywhere in its pixel (0.71 px), the start point anywhere in its pixel (0.71 px), plus 0.05 px for
@@ -98,4 +98,81 @@ SMH_CR_FN unsigned long long smh_cull_entry(uint32_t T, int ox, int oy) {
 // The AND is per unit: both pixels have to be seen by the SAME unit, since both conditions speak of one ray.
 SMH_CR_FN unsigned long long smh_cull_live(unsigned long long seen_outer, unsigned long long seen_middle, bool chained) {
 	return chained ? seen_outer & seen_middle : seen_outer;
+}
+
+// ---- a row's white pixels by runs ------------------------------------------------------------------------------------------
+// The condensed table (smh_runtime.cpp, sector_table_for) gives every annulus pixel a byte: the smallest cyclic run of units that
+// covers the pixel's units m != 0 (a superset only casts more rays) as first | (n - 1) << 6 if it has n <= 4 units, else 0xFF =
+// every unit.
+SMH_CR_FN uint8_t smh_cull_unit_code(unsigned long long m) {
+	const uint32_t NU = SMH_CULL_UNITS;
+	m &= (1ull << NU) - 1ull;
+	uint32_t first = 0, cnt = NU, best_gap = 0;                             // complement of the longest cyclic zero gap
+	for (uint32_t st = 0; st < NU; ++st) {
+		if (!((m >> st) & 1ull)) continue;
+		uint32_t gap = 0;
+		while (gap < NU - 1 && !((m >> ((st + 1 + gap) % NU)) & 1ull)) ++gap;
+		if (gap > best_gap) { best_gap = gap; first = (st + 1 + gap) % NU; cnt = NU - gap; }
+	}
+	if (best_gap == 0 || cnt > 4) return 0xFF;
+	return (uint8_t)(first | ((cnt - 1) << 6));                             // first <= 56: never 0xFF
+}
+// What a byte code stands for, unfolded: a range that wraps past the last unit continues above bit SMH_CULL_UNITS, and the
+// reader folds what it has ORed together (cull_fold, smh_lsd.hip).
+SMH_CR_FN unsigned long long smh_cull_code_units(uint32_t code) {
+	return code == 0xFFu ? ~0ull : ((2ull << (code >> 6)) - 1ull) << (code & 63u);   // first <= 56, n <= 4
+}
+// A RUN is a maximal set of consecutive white pixels of one annulus in a row (the scans: within a 32-pixel cell).  The
+// directions from which a dilated row segment can be hit lie between the tangents to the discs about its two end pixels, so as
+// long as the segment does not pass beside the start pixel the units of all its pixels are the smallest cyclic interval of
+// units that contains the ranges of its two ends: two look-ups per run where the walk pixel by pixel takes one per pixel.
+// tests/cull_runs_check.cpp holds this against the pixels' own units for every threshold, row and run.  ca, cb: the byte
+// codes of the run's ends (in either order; the same code twice: a single pixel, whose own range comes back) -> the units,
+// unfolded like smh_cull_code_units.  The interval is built as its part below the last unit ORed with its part wrapped
+// to unit 0: it never needs more than 64 bits.
+SMH_CR_FN unsigned long long smh_cull_run_units(uint32_t ca, uint32_t cb) {
+	if (ca == 0xFFu || cb == 0xFFu) return ~0ull;
+	const int fa = (int)(ca & 63u), na = (int)(ca >> 6) + 1, fb = (int)(cb & 63u), nb = (int)(cb >> 6) + 1;
+	const int d = fb - fa + (fb < fa ? SMH_CULL_UNITS : 0);                 // where b's range starts, counted from a's start; ...
+	const int e = d ? SMH_CULL_UNITS - d : 0;                               // ... and a's from b's
+	const int la = d + nb > na ? d + nb : na, lb = e + na > nb ? e + na : nb;   // the interval from a's start on that holds both; from b's
+	const int f = la <= lb ? fa : fb, l = la <= lb ? la : lb;               // (a smallest interval starts where one of the two does)
+	if (l >= SMH_CULL_UNITS) return ~0ull;
+	const unsigned long long m = (1ull << l) - 1ull;
+	return (m << f) | (m >> (SMH_CULL_UNITS - f));                          // (f == 0: l < 57 leaves nothing to wrap)
+}
+// Where the run rule holds: an annulus whose lower step is >= SMH_CULL_RUN_MIN_LO.  Below that a run can pass beside the start
+// pixel, where the smallest interval about its ends may be the wrong one of the two (counter-examples at T = 24, the middle
+// annulus [1, 25], and at T = 48 and 49, the outer annulus from 2 and 1 on): such an annulus is walked pixel by pixel.
+#define SMH_CULL_RUN_MIN_LO 3
+SMH_CR_FN bool smh_cull_by_runs(uint32_t T, int a) {
+#ifdef SMH_NO_CULL_RUNS
+	(void)T; (void)a;
+	return false;                                                           // (the A/B switch: every annulus pixel by pixel)
+#else
+	int lo, hi;
+	return smh_cull_window(T, a, &lo, &hi) && lo >= SMH_CULL_RUN_MIN_LO;
+#endif
+}
+// How a search of threshold T culls, as the kernels carry it (wave-uniform): the low two bits 1 the outer annulus alone, 2
+// chained with the middle annulus; then which of the two is walked by runs.  (0: no culling -- the caller's decision.)
+#define SMH_CULL_MODE_RULE 3u
+#define SMH_CULL_MODE_RUNS_OUTER 4u
+#define SMH_CULL_MODE_RUNS_MIDDLE 8u
+SMH_CR_FN uint32_t smh_cull_mode(uint32_t T) {
+	return (smh_cull_chained(T) ? 2u : 1u) | (smh_cull_by_runs(T, 0) ? SMH_CULL_MODE_RUNS_OUTER : 0u) | (smh_cull_by_runs(T, 1) ? SMH_CULL_MODE_RUNS_MIDDLE : 0u);
+}
+// The starts and the ends of the runs of a cell's white annulus pixels `hit` (after the annulus mask): the i-th lowest start
+// pairs with the i-th lowest end.  Not by runs: every pixel is a run of its own.
+SMH_CR_FN uint32_t smh_cull_run_starts(uint32_t hit, bool by_runs) { return by_runs ? hit & ~(hit << 1) : hit; }
+SMH_CR_FN uint32_t smh_cull_run_ends(uint32_t hit, bool by_runs) { return by_runs ? hit & ~(hit >> 1) : hit; }
+// The units a cell's white annulus pixels can be seen by (codes: the byte codes of the cell's 32 pixels), unfolded.
+SMH_CR_FN unsigned long long smh_cull_word_units(uint32_t hit, const uint8_t *codes, bool by_runs) {
+	uint32_t s = smh_cull_run_starts(hit, by_runs), e = smh_cull_run_ends(hit, by_runs);
+	unsigned long long acc = 0ull;
+	while (s) {
+		acc |= smh_cull_run_units(codes[__builtin_ctz(s)], codes[__builtin_ctz(e)]);
+		s &= s - 1u; e &= e - 1u;
+	}
+	return acc;
 }

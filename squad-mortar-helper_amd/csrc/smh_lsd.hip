@@ -234,22 +234,13 @@ __device__ __forceinline__ uint32_t win2_word(const Win &m, int wq, int yi) { re
 __device__ __forceinline__ uint32_t win2_bit(const Win &m, int xi, int yi) { return (win2_word(m, xi >> 5, yi) >> ((uint32_t)xi & 31u)) & 1u; }
 
 // How a search culls (smh_cull_rule.h): 0 every ray is cast (no table: exact statistics; or a threshold the argument does
-// not cover), 1 the outer annulus alone, 2 chained with the middle annulus.  Wave-uniform.
+// not cover), else smh_cull_mode: the outer annulus alone or chained with the middle one, and which of them by runs.  Wave-uniform.
 __device__ __forceinline__ uint32_t cull_mode_for(const uint32_t *tab, float max_gap) {
 	if (tab == nullptr || !(max_gap > 0.0f && max_gap <= 49.0f)) return 0u;
-	return smh_cull_chained((uint32_t)ceilf(max_gap)) ? 2u : 1u;
+	return smh_cull_mode((uint32_t)ceilf(max_gap));
 }
-// The units a cell's white annulus pixels `hit` can be seen by (codes: the unit codes of the cell's 32 pixels), unfolded:
-// a range that wraps past the last unit continues above bit LSD_GROUPS (cull_fold).
-__device__ __forceinline__ unsigned long long cull_units_of(uint32_t hit, const uint8_t *codes) {
-	unsigned long long acc = 0ull;
-	while (hit) {
-		const uint32_t code = codes[__builtin_ctz(hit)];
-		hit &= hit - 1u;
-		acc |= code == 0xFFu ? ~0ull : ((2ull << (code >> 6)) - 1ull) << (code & 63u);   // first <= 56, n <= 4
-	}
-	return acc;
-}
+// (the units a cell's white annulus pixels can be seen by: smh_cull_word_units, unfolded -- a range that wraps past the last unit
+// continues above bit LSD_GROUPS)
 __device__ __forceinline__ unsigned long long cull_fold(unsigned long long acc) { return (acc | (acc >> LSD_GROUPS)) & ((1ull << LSD_GROUPS) - 1ull); }
 
 // (not on the hot path: the cache test is a run-time one here)
@@ -924,8 +915,9 @@ __device__ __forceinline__ void cast_group(const Win &m, LsdShared &sh, uint32_t
 		// (smh_cull_rule.h)? ----
 		// One thread per (candidate, row, 32-pixel word) cell of the (2R+1)-row neighbourhood: the mask word,
 		// funnel-shifted so that bit 0 is offset -R from floor(start point), is ANDed with each annulus' mask of
-		// the cell; every white annulus pixel left contributes its unit range (a byte code per pixel).  The cell's two
-		// masks are read with the window words, not after them.
+		// the cell; every run of white annulus pixels left contributes the unit interval about its two ends (a byte code per
+		// pixel; smh_cull_by_runs: or every pixel its own range).  The cell's two masks are read with the window words, not after them.
+		const bool chained = (cull & SMH_CULL_MODE_RULE) == 2u;
 		for (uint32_t id = tid; id < nc * SMH_CULL_CELLS; id += LSD_BS) {
 			const uint32_t c = id / SMH_CULL_CELLS, cell = id - c * SMH_CULL_CELLS;
 			if ((cached >> c) & 1u) continue;
@@ -937,11 +929,11 @@ __device__ __forceinline__ void cast_group(const Win &m, LsdShared &sh, uint32_t
 			const uint32_t lo = win_word(m, b0 >> 5, yi), hi = win_word(m, (b0 >> 5) + 1, yi);
 			const uint32_t px32 = __builtin_amdgcn_alignbit(hi, lo, (uint32_t)b0 & 31u);
 			const uint8_t *codes = SMH_CULL_CODES(cull_tab) + (cell >> 2) * SMH_SECTOR_DIM + ((cell & 3u) << 5);
-			if (px32 & m_out) atomicOr(&sh.live[c], cull_fold(cull_units_of(px32 & m_out, codes)));   // units wrap at 57
-			if (cull == 2u && (px32 & m_mid)) atomicOr(&sh.live_mid[c], cull_fold(cull_units_of(px32 & m_mid, codes)));
+			if (px32 & m_out) atomicOr(&sh.live[c], cull_fold(smh_cull_word_units(px32 & m_out, codes, (cull & SMH_CULL_MODE_RUNS_OUTER) != 0u)));   // units wrap at 57
+			if (chained && (px32 & m_mid)) atomicOr(&sh.live_mid[c], cull_fold(smh_cull_word_units(px32 & m_mid, codes, (cull & SMH_CULL_MODE_RUNS_MIDDLE) != 0u)));
 		}
 		__syncthreads();
-		if (cull == 2u) {                               // (uniform)
+		if (chained) {                                  // (uniform)
 			if (tid < nc && !((cached >> tid) & 1u)) sh.live[tid] = smh_cull_live(sh.live[tid], sh.live_mid[tid], true);
 			__syncthreads();
 		}
@@ -1367,11 +1359,12 @@ __global__ void __launch_bounds__(LSD_BS) __attribute__((amdgpu_waves_per_eu(5, 
 // ------------------------------------------------------------------------------------------------
 // Sector culling for find_lines (every search kernel).  A ray that can make its candidate acceptable (len^2 > 2500) has a
 // WHITE sample in every window of T + 1 consecutive steps that ends by step 50, T = ceil(max_gap): a white-free window
-// would have aborted it before.  The build looks at the window [50 - T, 50]: only the 64-ray units that can see a white
-// pixel in that annulus have to be ray-cast at all.  The chained argument -- the window [50 - 2T - 1, 50 - T - 1] is
-// disjoint from it and speaks of the same ray, which lies in one unit, so a unit needs a white pixel in the outer annulus
-// AND one in the middle annulus -- holds as well and is compiled in with -DSMH_CULL_CHAIN (measured slower: the scan of the
-// second ring costs more than the units it saves).  The argument, the annuli and the conservative map from a pixel offset
+// would have aborted it before.  The window [50 - T, 50]: only the 64-ray units that can see a white pixel in that annulus
+// have to be ray-cast at all.  The chained argument -- the window [50 - 2T - 1, 50 - T - 1] is disjoint from it and speaks
+// of the same ray, which lies in one unit, so a unit needs a white pixel in the outer annulus AND one in the middle annulus
+// -- holds as well and is compiled in with -DSMH_CULL_CHAIN (measured slower: the scan of the second ring costs more than the
+// units it saves, also by runs).
+// The argument, the annuli, the runs the scans take the pixels by and the conservative map from a pixel offset
 // to the units that can sample it are smh_cull_rule.h; this kernel tabulates smh_cull_entry over the (2R+1)^2 offsets from
 // floor(start point).
 // ------------------------------------------------------------------------------------------------

@@ -251,7 +251,7 @@ __device__ __forceinline__ void cand_setup(const Win &m, uint32_t *wwin, const u
 	const unsigned long long c_t1 = __builtin_amdgcn_s_memtime();
 	struct CullTimer { unsigned long long *p, t; __device__ ~CullTimer() { if (p) p[1] += __builtin_amdgcn_s_memtime() - t; } } c_timer{cprof, c_t1};
 #endif
-	if (cull) {   // the 64-ray units that can see a white pixel in the outer annulus (cull == 2: and one in the middle annulus; smh_cull_rule.h)
+	if (cull) {   // the 64-ray units that can see a white pixel in the outer annulus (chained: and one in the middle annulus; smh_cull_rule.h)
 		const int fx = (int)floorf(xs), fy = (int)floorf(ys);
 		// One wave per SIMD has nobody else to hide an LDS round trip behind, so the window words and the cell masks of all
 		// seven cell rounds are read in ONE.  No branch per round (each would get a wait of its own): a lane past the last cell
@@ -268,37 +268,53 @@ __device__ __forceinline__ void cand_setup(const Win &m, uint32_t *wwin, const u
 			m_out[it] = cull_tab[cell]; m_mid[it] = SMH_CULL_MID_CELL(cull_tab, cell);
 			cells[it] = cell;
 		}
-		// The white annulus pixels' unit codes, a byte each in LDS: a lane walks the pixels of its cell, four look-ups per round
-		// trip, and the wave waits for the lane with the most.  (-DSMH_CULL_CHAIN: both annuli in one walk.  Measured, with
-		// the second ring's pixels the walk costs more than the units the chain saves, DESIGN.md section 5; a lane per pixel
-		// over the cells that hold any was slower still -- a candidate has some hundred such cells.)
+		// The white annulus pixels' unit codes, a byte each in LDS.  A lane takes its cells' pixels by RUNS (smh_cull_rule.h: the
+		// units of a run are the interval about the codes of its two ends; an annulus the run rule does not hold for: every
+		// pixel a run of its own), the outer and the middle annulus' apart -- a pixel can lie in both.  A marker line leaves a
+		// cell one run per annulus, so the first run of either annulus of all seven cells is looked up in ONE round trip, four
+		// look-ups per cell; a lane without a run looks its cell's first pixel up and drops it.  The cells that hold more runs
+		// are walked after that, a run of either annulus per round trip, and the wave waits for the lane with the most.
+		// (-DSMH_CULL_CHAIN: the middle annulus' runs double the interval arithmetic below, which costs more than the units the
+		// chain saves -- as the walk of both annuli pixel by pixel did: DESIGN.md section 5.)
 		const uint8_t *codes = SMH_CULL_CODES(cull_tab);
+		const bool chained = (cull & SMH_CULL_MODE_RULE) == 2u, runs_o = (cull & SMH_CULL_MODE_RUNS_OUTER) != 0u, runs_m = (cull & SMH_CULL_MODE_RUNS_MIDDLE) != 0u;
 		unsigned long long acc_o = 0ull, acc_m = 0ull;
+		uint32_t s_o[ROUNDS], e_o[ROUNDS], s_m[ROUNDS], e_m[ROUNDS], code[ROUNDS][4];
 #pragma unroll
 		for (int it = 0; it < ROUNDS; ++it) {
 			const uint32_t px32 = __builtin_amdgcn_alignbit(hi[it], lo[it], sh);   // the cell's 32 pixels
-			const uint32_t h_out = px32 & m_out[it], h_mid = cull == 2u ? px32 & m_mid[it] : 0u;
+			const uint32_t h_out = px32 & m_out[it], h_mid = chained ? px32 & m_mid[it] : 0u;
+			s_o[it] = smh_cull_run_starts(h_out, runs_o); e_o[it] = smh_cull_run_ends(h_out, runs_o);
+			s_m[it] = smh_cull_run_starts(h_mid, runs_m); e_m[it] = smh_cull_run_ends(h_mid, runs_m);
 			const uint8_t *c = codes + (cells[it] >> 2) * SMH_SECTOR_DIM + ((cells[it] & 3u) << 5);
-			uint32_t hit = h_out | h_mid;
-			while (hit) {                                               // four pixels per round trip (a marker line is three pixels thick)
-				uint32_t b[4], code[4];
+			code[it][0] = c[s_o[it] ? (uint32_t)__builtin_ctz(s_o[it]) : 0u]; code[it][1] = c[e_o[it] ? (uint32_t)__builtin_ctz(e_o[it]) : 0u];
+			code[it][2] = c[s_m[it] ? (uint32_t)__builtin_ctz(s_m[it]) : 0u]; code[it][3] = c[e_m[it] ? (uint32_t)__builtin_ctz(e_m[it]) : 0u];
+		}
+		uint32_t more = 0u;
 #pragma unroll
-				for (int k = 0; k < 4; ++k) {
-					b[k] = hit || k == 0 ? (uint32_t)__builtin_ctz(hit) : b[k - 1];   // (no pixel left: the last one again)
-					hit &= hit - 1u;                                    // (0 stays 0)
-				}
+		for (int it = 0; it < ROUNDS; ++it) {
+			if (s_o[it]) acc_o |= smh_cull_run_units(code[it][0], code[it][1]);
+			if (s_m[it]) acc_m |= smh_cull_run_units(code[it][2], code[it][3]);
+			s_o[it] &= s_o[it] - 1u; e_o[it] &= e_o[it] - 1u;               // (0 stays 0)
+			s_m[it] &= s_m[it] - 1u; e_m[it] &= e_m[it] - 1u;
+			more |= s_o[it] | s_m[it];
+		}
+		if (__any(more != 0u)) {                                        // (uniform) a cell with two runs of one annulus: two lines side by side, a dotted one
 #pragma unroll
-				for (int k = 0; k < 4; ++k) code[k] = c[b[k]];
-#pragma unroll
-				for (int k = 0; k < 4; ++k) {
-					const unsigned long long units = code[k] == 0xFFu ? ~0ull : ((2ull << (code[k] >> 6)) - 1ull) << (code[k] & 63u);   // first <= 56, n <= 4
-					if ((h_out >> b[k]) & 1u) acc_o |= units;
-					if ((h_mid >> b[k]) & 1u) acc_m |= units;
+			for (int it = 0; it < ROUNDS; ++it) {
+				const uint8_t *c = codes + (cells[it] >> 2) * SMH_SECTOR_DIM + ((cells[it] & 3u) << 5);
+				uint32_t so = s_o[it], eo = e_o[it], sm = s_m[it], em = e_m[it];
+				while (so | sm) {
+					const uint32_t c0 = c[so ? (uint32_t)__builtin_ctz(so) : 0u], c1 = c[eo ? (uint32_t)__builtin_ctz(eo) : 0u];
+					const uint32_t c2 = c[sm ? (uint32_t)__builtin_ctz(sm) : 0u], c3 = c[em ? (uint32_t)__builtin_ctz(em) : 0u];
+					if (so) acc_o |= smh_cull_run_units(c0, c1);
+					if (sm) acc_m |= smh_cull_run_units(c2, c3);
+					so &= so - 1u; eo &= eo - 1u; sm &= sm - 1u; em &= em - 1u;
 				}
 			}
 		}
 		const unsigned long long seen_outer = cull_fold(wave_or64(acc_o));
-		live = cull == 2u ? smh_cull_live(seen_outer, cull_fold(wave_or64(acc_m)), true) : seen_outer;
+		live = chained ? smh_cull_live(seen_outer, cull_fold(wave_or64(acc_m)), true) : seen_outer;
 	}
 }
 

@@ -391,22 +391,6 @@ static void logf(smhv_ctx *c, int lvl, const char *fmt, ...) {
 	c->log(lvl, buf);
 }
 
-// Smallest cyclic run of 64-ray units covering mask m (a superset only casts more rays) as the byte code of
-// Buffers::cull_tab: first | (n - 1) << 6 for n <= 4, else 0xFF = every unit.  m != 0.
-static uint8_t unit_code(unsigned long long m) {
-	const uint32_t NU = 57;                                   // units per candidate
-	m &= (1ull << NU) - 1ull;
-	uint32_t first = 0, cnt = NU, best_gap = 0;               // complement of the longest cyclic zero gap
-	for (uint32_t st = 0; st < NU; ++st) {
-		if (!((m >> st) & 1ull)) continue;
-		uint32_t gap = 0;
-		while (gap < NU - 1 && !((m >> ((st + 1 + gap) % NU)) & 1ull)) ++gap;
-		if (gap > best_gap) { best_gap = gap; first = (st + 1 + gap) % NU; cnt = NU - gap; }
-	}
-	if (best_gap == 0 || cnt > 4) return 0xFF;
-	return (uint8_t)(first | ((cnt - 1) << 6));               // first <= 56: never 0xFF
-}
-
 // Device table for max_gap (nullptr => k_lsd casts every ray).  Built once per distinct threshold: the kernel
 // fills the dense (2R+1)^2 table, the host condenses it into per-word cells (smh_kernels.h, Buffers::cull_tab).
 static int sector_table_for(smhv_ctx *c, uint32_t max_gap, hipStream_t s, Buffers *bf) {
@@ -432,7 +416,7 @@ static int sector_table_for(smhv_ctx *c, uint32_t max_gap, hipStream_t s, Buffer
 			if (!m) continue;
 			if (e & SMH_CULL_IN_OUTER) cells[row * 4 + (col >> 5)] |= 1u << (col & 31u);
 			if (SMH_CULL_ANNULI == 2 && (e & SMH_CULL_IN_MIDDLE)) cells[(SMH_CULL_ANNULI - 1) * SMH_CULL_CELLS + row * 4 + (col >> 5)] |= 1u << (col & 31u);
-			codes[row * SMH_SECTOR_DIM + col] = unit_code(m);
+			codes[row * SMH_SECTOR_DIM + col] = smh_cull_unit_code(m);
 		}
 	uint32_t *d = nullptr;
 	HIPCHK(hipMalloc((void **)&d, sizeof(uint32_t) * cells.size()));
