@@ -52,9 +52,10 @@ def ray_lengths(img, px, py, max_gap):
     inside = (xi < w) & (yi < h)
     zero = np.zeros(n, bool)
     zero[inside] = img[yi[inside], xi[inside]] == 0
-    xe = np.where(zero, x - DX, xs).astype(f32); ye = np.where(zero, y - DY, ys).astype(f32)
-    ddx = (xs - xe).astype(f32); ddy = (ys - ye).astype(f32)
-    length = (ddx * ddx + ddy * ddy).astype(f32)
+    with np.errstate(invalid="ignore"):                                     # (an infinite start: inf - inf is the reference's NaN)
+        xe = np.where(zero, x - DX, xs).astype(f32); ye = np.where(zero, y - DY, ys).astype(f32)
+        ddx = (xs - xe).astype(f32); ddy = (ys - ye).astype(f32)
+        length = (ddx * ddx + ddy * ddy).astype(f32)
     return xe, ye, length
 
 
@@ -65,7 +66,7 @@ def find_longest_line(img, px, py, max_gap):
     bx, by, ex, ey = f32(0), f32(0), f32(0), f32(0)
     m = length.max()
     if not (f32(0) > m):                                                    # `a_length > b_length` else b: the LAST maximum wins
-        best = int(np.nonzero(length == m)[0][-1]) if m >= 0 else 0
+        best = int(np.nonzero(length == m)[0][-1]) if m >= 0 else len(length) - 1    # (NaN lengths: b wins every comparison, the last ray stays)
         bx, by, ex, ey, best_len = xs, ys, xe[best], ye[best], length[best]
     return np.array([bx, by, ex, ey], f32), f32(best_len)
 
