@@ -1327,6 +1327,112 @@ SMHV_API int smhv_batch_clearance_map_ptr(smhv_batch *b, void **d_clearance_map)
 SMHV_API int smhv_clearance_map(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_clearance_options *opt,
                                 const uint32_t minimap[4], uint8_t *rgba_inout, uint8_t *bytes, smhv_clearance_map_result *result);
 
+/* ---- terrain relief: contour lines, hillshade and heights of every window pixel ------------------------------------------------
+ * The reach map says where a tube can reach and the clearance map where the arc is blocked; this pass shows why: the shape of the
+ * ground under a map view's window -- the terrain height of every pixel, a hillshade value and whether a contour line or an index
+ * contour passes there.  The reference draws no such picture; the coordinates are "firing solutions"' alone.  Every operation is one
+ * IEEE f64 operation, left to right, unfused (a product is rounded before it is added; (double) of an integer or an f32 is exact),
+ * but for the rectangle, which stays f32 as the firing solutions have it.  W x H = the heightmap, texel (i, j) = data[j * W + i].
+ * Pixel.  Frame f, window pixel (X, Y): cx = X + 0.5f, cy = Y + 0.5f in f32.  R = {l, t, r, b} = the heightmap's rectangle of "firing
+ *   solutions" in f32, from the frame's minimap rectangle through the render options' viewport (viewport_scale, 0 = 1;
+ *   viewport_top_left); SMHV_RENDER_BOUNDS_OFFSET acts as SMHV_FIRING_BOUNDS_OFFSET.  rw = (double)(r - l), rh = (double)(b - t), the
+ *   differences in f32.  px = (((double)cx - (double)l) / rw) * (double)W, py = (((double)cy - (double)t) / rh) * (double)H.  The
+ *   window position itself is the translated point: unlike the reach map there is no inverse_xy / translate_xy round trip.
+ * rnd(v) = Rust's `v.round() as i32`: half away from zero, saturating, NaN -> 0 (the firing solutions' rounding).
+ * A pixel HAS A HEIGHT iff the frame is open and has a minimap rectangle (the per-call path: a minimap was given), 0 <= rnd(px) < W
+ *   and 0 <= rnd(py) < H (the firing solutions' inside test), and the z below is finite.  Everything else is flag byte 0, shade 0,
+ *   height 0.0f and no paint.  (A px that is NaN rounds to 0 and is inside: NEAREST then reads texel column 0, while the bilinear
+ *   weights are NaN, z is not finite and the pixel has no height.)
+ * Height.  Default, bilinear: i = floor(px), fx = px - i, gx = 1.0 - fx, taps i and i + 1, each clamped into [0, W - 1]; j, fy, gy
+ *   likewise from py.  With v00 = texel (i, j), v10 = (i + 1, j), v01 = (i, j + 1), v11 = (i + 1, j + 1) as f64:
+ *   top = v00 * gx + v10 * fx, bot = v01 * gx + v11 * fx, v = top * gy + bot * fy.  SMHV_RELIEF_NEAREST: v = (double)texel (rnd(px),
+ *   rnd(py)).  z = (v / 65535.0) * zscale, zscale = (double)scale[2] / 0.1953125 -- a true division.  With NEAREST z is "firing
+ *   solutions"' height of the pixel, bit for bit, everywhere; without it wherever px and py are integers (fx = fy = 0: v = v00).
+ * Neighbours.  zr = the height of pixel (X + 1, Y), zd = that of (X, Y + 1), each by the same rule also where it lies outside the window.
+ * Contours (interval_m > 0; 0 = none).  L = floor((z - base_m) / interval_m).  A pair (pixel, neighbour) CROSSES iff both have a
+ *   height, both L are finite and they differ.  SMHV_RELIEF_CONTOUR is set iff the right or the down pair crosses.  SMHV_RELIEF_MAJOR
+ *   (major_every = M >= 1; 0 = none) is set iff for a crossing pair, lo = the lesser and hi = the greater of its two L,
+ *   floor(hi / (double)M) != floor(lo / (double)M): some level index in (lo, hi] is a multiple of M, also below base_m.
+ * Hillshade.  One heightmap texel is one metre on the ground, as the firing solutions' range has it.  mx = (double)W / rw,
+ *   my = (double)H / rh (texels per window pixel).  p = ((zr - z) * exaggeration) / mx when the right neighbour has a height, else 0.0;
+ *   q likewise from zd and my.  With light = {lx, ly, lz}, the caller's vector from the ground towards the light in heightmap axes (x
+ *   right, y down, z up; not normalised by the library, no trigonometry runs on the device): t = (lz - p * lx) - q * ly,
+ *   den = sqrt((1.0 + p * p) + q * q), s = t / den; !(s > 0.0) gives 0.0 and s > 1.0 gives 1.0; shade = (uint8_t)(s * 255.0 + 0.5).
+ * Paint (SMHV_RELIEF_PAINT), into the batch's render slab, over whatever is there, only on pixels with a height: first the reach map's
+ *   integer blend with the entry (shade, shade, shade, shade_weight), then on a CONTOUR pixel the same blend with major[4] when the
+ *   MAJOR bit is set, else with contour[4].  A weight of 0 leaves the pixel as it is; the image's alpha byte is untouched.  As for
+ *   the reach map the tint lies over everything already drawn; a caller draws the text passes afterwards.
+ * Planes, each out_w * out_h elements per frame, rows and frames tightly packed, the call's first frame first, into caller-provided
+ *   device memory (smhv_relief_planes): SMHV_RELIEF_BYTES u8 = SMHV_RELIEF_HAS_HEIGHT | _CONTOUR | _MAJOR; SMHV_RELIEF_SHADES u8;
+ *   SMHV_RELIEF_HEIGHTS f32 = (float)z.  A frame without relief (closed, or no minimap rectangle) gets zeroed planes and an untouched
+ *   slab.  The shade is computed when SHADES, or PAINT with shade_weight != 0, asks for it.
+ * Summary.  One smhv_relief_result per frame in the batch's relief slab (allocated by the first call), cleared on the stream ahead of
+ *   the kernel: valid = 1 iff the frame is open and has a minimap rectangle (else every field is 0); n_height, n_contour, n_major =
+ *   window pixels with that bit; z_min, z_max = the least and the greatest z over the window pixels with a height, both 0.0 when
+ *   n_height == 0. */
+#define SMHV_RELIEF_PAINT 1u           /* smhv_relief_options.flags: tint the render slab (per call: implied by rgba_inout) */
+#define SMHV_RELIEF_BYTES 2u           /*   ... write the flag bytes (per call: implied by bytes) */
+#define SMHV_RELIEF_SHADES 4u          /*   ... write the shade bytes (per call: implied by shades) */
+#define SMHV_RELIEF_HEIGHTS 8u         /*   ... write the f32 heights (per call: implied by heights) */
+#define SMHV_RELIEF_NEAREST 16u        /*   ... the height is the nearest texel's, not the bilinear one */
+#define SMHV_RELIEF_HAS_HEIGHT 1u      /* the flag byte */
+#define SMHV_RELIEF_CONTOUR 2u
+#define SMHV_RELIEF_MAJOR 4u
+typedef struct {
+	uint32_t size;                       /*  0: sizeof(smhv_relief_options) == 80 */
+	uint32_t flags;                      /*  4: SMHV_RELIEF_PAINT | _BYTES | _SHADES | _HEIGHTS | _NEAREST (no output flag: the summary alone) */
+	uint32_t major_every;                /*  8: M, every M-th level is an index contour; 0 = none */
+	uint32_t reserved0;                  /* 12 */
+	double interval_m;                   /* 16: metres between contour levels; 0 = none; finite, >= 0 */
+	double base_m;                       /* 24: the height of level 0; finite */
+	double exaggeration;                 /* 32: the slopes' factor in the hillshade; finite */
+	double light[3];                     /* 40: from the ground towards the light (x right, y down, z up); finite */
+	uint8_t contour[4];                  /* 64: R, G, B and the blend weight a of a contour pixel */
+	uint8_t major[4];                    /* 68: ... of an index contour's pixel */
+	uint32_t shade_weight;               /* 72: the blend weight of the hillshade, <= 255 */
+	uint32_t reserved;                   /* 76 */
+} smhv_relief_options;
+typedef struct {
+	uint32_t valid;                      /*  0 */
+	uint32_t n_height;                   /*  4 */
+	uint32_t n_contour;                  /*  8 */
+	uint32_t n_major;                    /* 12 */
+	double z_min;                        /* 16 */
+	double z_max;                        /* 24 */
+	uint32_t reserved[4];                /* 32 */
+} smhv_relief_result;                    /* 48 bytes */
+typedef struct {
+	void *bytes;                         /*  0: SMHV_RELIEF_BYTES: n * out_w * out_h u8, device memory */
+	void *shades;                        /*  8: SMHV_RELIEF_SHADES: n * out_w * out_h u8 */
+	void *heights;                       /* 16: SMHV_RELIEF_HEIGHTS: n * out_w * out_h f32 */
+} smhv_relief_planes;                    /* 24 bytes */
+/* Host only.  Fills *opt: size, flags = PAINT, interval_m = 10, base_m = 0, major_every = 5, exaggeration = 1, light from the
+ * north-west at 45 degrees {-0.5, -0.5, 0x1.6a09e667f3bcdp-1}, contour (60, 40, 20, 110), major (60, 40, 20, 200), shade_weight 96. */
+SMHV_API int smhv_relief_defaults(smhv_relief_options *opt);
+/* The terrain relief of frames [first, first + n), asynchronously on `stream`; the frames' results in the relief slab are cleared on
+ * the stream ahead of the kernel.  ropt supplies the window and the viewport (quad, background and the HEIGHTMAP / MARKERS flags are
+ * not used); hm is the terrain.  With PAINT the call runs behind whatever the batch's previous render enqueued and ropt->out_w /
+ * out_h must be the most recent render's (SMHV_E_STATE for another size or before the first render).  Without PAINT only the records
+ * are read: a plain batch after smhv_batch_run, or a pipeline slot's batch after smhv_pipeline_wait, for both searches (a batch that
+ * has not run has closed maps only).  planes (NULL: none) names the planes' device memory.  SMHV_E_INVALID: hm == NULL (relief
+ * without terrain is nothing), what smhv_batch_render rejects in ropt, a wrong size, unknown flags, a plane flag whose pointer (or
+ * `planes`) is NULL, an interval_m, base_m, exaggeration or light component that is not finite, interval_m < 0, shade_weight > 255,
+ * n == 0, a range beyond the batch's capacity, a heightmap on another device.  A failed call enqueues nothing.  The batch keeps a
+ * reference of hm as smhv_batch_render does. */
+SMHV_API int smhv_batch_relief(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_render_options *ropt,
+                               const smhv_relief_options *opt, const smhv_relief_planes *planes, void *stream);
+/* The batch's relief slab: read is a synchronising host copy, ptr the device address (SMHV_E_STATE before the first smhv_batch_relief) */
+SMHV_API int smhv_batch_read_relief(smhv_batch *b, uint32_t first, uint32_t n, smhv_relief_result *out);
+SMHV_API int smhv_batch_relief_ptr(smhv_batch *b, void **d_relief);
+/* The per-call path, stateless like smhv_reach_map: minimap = {left, right, top, bottom} (NULL: none -- nothing has a height).
+ * rgba_inout (host, out_w * out_h * 4 bytes, an image of any smhv_render_map* call or any other) is tinted in place; bytes, shades
+ * (host, out_w * out_h bytes each) and heights (host, out_w * out_h floats) receive the planes; result receives the summary.  Each
+ * of the five may be NULL, not all of them.  Of opt->flags NEAREST applies; the others are checked and otherwise not used.  Runs
+ * on the context's stream. */
+SMHV_API int smhv_relief_map(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_relief_options *opt,
+                             const uint32_t minimap[4], uint8_t *rgba_inout, uint8_t *bytes, uint8_t *shades, float *heights,
+                             smhv_relief_result *result);
+
 /* ---- scale labels: word boxes, the bar under each, glyph crops -----------------------------------------------------------------
  * The reference's scales branch (src/vision/mod.rs:128-193) pulls the whole ocr_preprocess plane to the host, runs a full-page OCR
  * over it (ocr::read, mod.rs:149) and filters the hits (mod.rs:161-186) into label anchors.  Reading digits stays on the host; all

@@ -144,6 +144,28 @@ class ReachResult(C.Structure):
                 ("reserved", C.c_uint32 * 2)]
 
 
+RELIEF_PAINT, RELIEF_BYTES, RELIEF_SHADES, RELIEF_HEIGHTS, RELIEF_NEAREST = 1, 2, 4, 8, 16   # smhv_relief_options.flags
+RELIEF_HAS_HEIGHT, RELIEF_CONTOUR, RELIEF_MAJOR = 1, 2, 4             # the flag byte
+
+
+class ReliefOptionsStruct(C.Structure):
+    """smhv_relief_options: contour spacing, the hillshade's light and the paint of a terrain relief (80 bytes)."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("major_every", C.c_uint32), ("reserved0", C.c_uint32), ("interval_m", C.c_double),
+                ("base_m", C.c_double), ("exaggeration", C.c_double), ("light", C.c_double * 3), ("contour", C.c_uint8 * 4), ("major", C.c_uint8 * 4),
+                ("shade_weight", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ReliefResult(C.Structure):
+    """smhv_relief_result: a frame's summary of its terrain relief (48 bytes)."""
+    _fields_ = [("valid", C.c_uint32), ("n_height", C.c_uint32), ("n_contour", C.c_uint32), ("n_major", C.c_uint32), ("z_min", C.c_double),
+                ("z_max", C.c_double), ("reserved", C.c_uint32 * 4)]
+
+
+class ReliefPlanes(C.Structure):
+    """smhv_relief_planes: the device memory of the planes a batch call writes (24 bytes)."""
+    _fields_ = [("bytes", C.c_void_p), ("shades", C.c_void_p), ("heights", C.c_void_p)]
+
+
 CLEAR_MAX_SAMPLES = 256
 CLEAR_PROFILE = CLEAR_MAX_SAMPLES + 1                                  # floats of a line's profile row
 CLEAR_PAINT, CLEAR_BYTES = 1, 2                                        # smhv_clearance_options.flags
@@ -440,6 +462,13 @@ SIGNATURES = {
     "smhv_batch_clearance_map_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "smhv_clearance_map": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(ClearanceOptionsStruct), C.POINTER(C.c_uint32), C.c_void_p,
                                      C.c_void_p, C.POINTER(ClearanceMapResult)]),
+    "smhv_relief_defaults": (C.c_int, [C.POINTER(ReliefOptionsStruct)]),
+    "smhv_batch_relief": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(ReliefOptionsStruct),
+                                    C.POINTER(ReliefPlanes), C.c_void_p]),
+    "smhv_batch_read_relief": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ReliefResult)]),
+    "smhv_batch_relief_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smhv_relief_map": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(ReliefOptionsStruct), C.POINTER(C.c_uint32), C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ReliefResult)]),
     "smhv_batch_scale_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "smhv_batch_read_scale_labels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ScaleLabelFrame), C.c_void_p]),
     "smhv_batch_scale_labels_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

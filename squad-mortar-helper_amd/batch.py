@@ -317,6 +317,43 @@ class FrameBatch:
         L.check(self._lib.smhv_batch_reach_ptr(self._b, C.byref(d)))
         return d.value or 0
 
+    def relief(self, options, relief, first=0, n=None, heightmap=None, bytes_ptr=None, shades_ptr=None, heights_ptr=None, stream=None):
+        """The terrain relief of frames [first, first + n) on `stream` (smhv_batch_relief): options = a RenderOptions (the window and
+        the viewport; with paint the most recent render's), relief = a ReliefOptions, heightmap = the terrain.  A plane that relief
+        asks for and that has no pointer (device memory, n * out_h * out_w elements) is allocated as a torch tensor [n, out_h,
+        out_w] (uint8, uint8, float32), and the call then returns after the device has finished; with every plane's pointer given,
+        or no plane, it is asynchronous.  -> dict(bytes=, shades=, heights=) of the tensors allocated here."""
+        n = self.max_frames - first if n is None else n
+        ro = relief.struct()
+        out = {}
+        ptrs = dict(bytes=bytes_ptr, shades=shades_ptr, heights=heights_ptr)
+        for name in ("bytes", "shades", "heights"):
+            if getattr(relief, name) and ptrs[name] is None:
+                import torch
+                out[name] = torch.zeros((n, int(options.out_h), int(options.out_w)), dtype=torch.float32 if name == "heights" else torch.uint8, device="cuda")
+                ptrs[name] = out[name].data_ptr()
+        if out:
+            torch.cuda.synchronize()
+        planes = L.ReliefPlanes(*[int(ptrs[k]) if ptrs[k] else None for k in ("bytes", "shades", "heights")])
+        L.check(self._lib.smhv_batch_relief(self._b, first, n, heightmap._hm if heightmap is not None else None, C.byref(options), C.byref(ro),
+                                            C.byref(planes), C.c_void_p(int(stream)) if stream else None))
+        if out:
+            torch.cuda.synchronize()
+        return out
+
+    def read_relief(self, first=0, n=None):
+        """Synchronising host copy of the relief slab -> a ctypes array of n ReliefResult."""
+        n = self.max_frames - first if n is None else n
+        out = (L.ReliefResult * n)()
+        L.check(self._lib.smhv_batch_read_relief(self._b, first, n, out))
+        return out
+
+    def relief_ptr(self):
+        """Device address of the relief slab (one smhv_relief_result per frame)."""
+        d = C.c_void_p()
+        L.check(self._lib.smhv_batch_relief_ptr(self._b, C.byref(d)))
+        return d.value or 0
+
     def clearance(self, clearance, first=0, n=None, heightmap=None, fit_to_minimap=True, viewport=None, profiles_ptr=None, profiles=False, stream=None):
         """The terrain clearance of the detected lines of frames [first, first + n) on `stream` (smhv_batch_clearance): clearance = a
         ClearanceOptions (samples, margin_m); heightmap, fit_to_minimap, viewport as the firing solutions take them.  With

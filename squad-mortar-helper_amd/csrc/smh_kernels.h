@@ -297,6 +297,27 @@ struct ClearMapRun {
 	uint32_t per_call, has_mm;           // 1: mm / has_mm are the call's and aux, res are not read
 	uint32_t pal[4];                     // out_of_range, clear, blocked, los: R, G, B, a as a little-endian word
 };
+// smhv_batch_relief / smhv_relief_map (k_relief, k_relief_finish: smh_relief.hip): the terrain relief of n frames, in k_reach's tiles.
+struct ReliefRun {
+	FiringRun fr;                        // the heightmap and the viewport, as the firing solutions take them (`out` is not used)
+	const FrameAux *aux;                 // batch, per frame: open
+	const smhv_frame_result *res;        // batch, per frame: the minimap rectangle
+	smhv_relief_result *out;             // the relief slab, at the first frame of the call; cleared ahead of the launch
+	uint8_t *img;                        // PAINT: the render slab, at the first frame of the call
+	uint8_t *bytes, *shades;             // the planes (null: not asked for): out_w * out_h elements per frame
+	float *heights;
+	uint64_t img_stride, plane_stride;   // out_w * out_h * 4 bytes, out_w * out_h elements
+	double interval_m, base_m, exaggeration;
+	double light[3];
+	uint32_t mm[4];                      // per call: the minimap rectangle (valid iff has_mm)
+	uint32_t out_w, out_h;
+	uint32_t nearest;                    // SMHV_RELIEF_NEAREST
+	uint32_t major_every;                // M
+	uint32_t per_call, has_mm;           // 1: mm / has_mm are the call's and aux, res are not read
+	uint32_t shade_weight;
+	uint32_t pal[2];                     // contour, major: R, G, B, a as a little-endian word
+	uint32_t pad;
+};
 // smhv_batch_scale_labels / smhv_scale_labels (k_scale_labels: smh_scalelabels.hip): the scale labels of n frames, one workgroup
 // each.  Launch arguments, taken by value at the launch.
 #define SMH_SL_MAX_DIM 2048u             // the quadrant's padded row and its height, at most: a row is two 16-byte loads per lane of a wave
@@ -603,6 +624,9 @@ hipError_t launch_heightmap_lut16(const uint32_t *lut, uint16_t *lut16, uint32_t
 hipError_t launch_labels(const LabelRun &r, uint32_t n, hipStream_t s);
 // the reach map (smh_reach.hip): k_reach<paint, classes> over n frames (at most 65,535: the grid's third dimension)
 hipError_t launch_reach(const ReachRun &r, uint32_t n, bool paint, bool classes, hipStream_t s);
+// the terrain relief (smh_relief.hip): k_relief<paint, planes> over n frames (at most 65,535), then k_relief_finish over their
+// summaries; the planes asked for are the non-null pointers of r
+hipError_t launch_relief(const ReliefRun &r, uint32_t n, bool paint, hipStream_t s);
 // terrain clearance (smh_clear.hip): k_clear_lines over n frames x SMHV_MAX_LINES lines (per call: n = 1, r.n_lines lines), and
 // k_clear_map<paint, bytes> over n frames (at most 65,535 each: a grid dimension)
 hipError_t launch_clear_lines(const ClearLinesRun &r, uint32_t n, hipStream_t s);

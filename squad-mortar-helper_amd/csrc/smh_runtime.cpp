@@ -278,6 +278,9 @@ struct smhv_batch {
 	smhv_clearance_result *d_clear = nullptr;
 	smhv_clearance_map_result *d_clear_map = nullptr;
 	smhv_heightmap *clear_hm = nullptr, *clear_map_hm = nullptr;
+	// smhv_batch_relief: the relief slab (allocated by the first call) and the heightmap the last call read
+	smhv_relief_result *d_relief = nullptr;
+	smhv_heightmap *relief_hm = nullptr;
 	// smhv_batch_scale_labels: the label slab, the crop slab and the family's own find_scales_preprocess plane with start row 0
 	// (allocated by the first call); what the batch's most recent run covered (its stages and frame count)
 	smhv_scale_label_frame *d_sl = nullptr;
@@ -677,7 +680,7 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	(void)hipDeviceSynchronize();
 	void *ptrs[] = {b->d_ui, b->d_ui_luma, b->d_ui_form, b->d_mask, b->d_bits, b->d_tiled, b->d_occ, b->d_ocr, b->d_scales, b->d_aux, b->d_results, b->d_anchors, b->d_bars, b->d_farm,
 	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run, b->d_overlay, b->d_render, b->d_prims, b->d_labels,
-	                b->d_label_cull, b->d_label_extra, b->d_probes, b->d_dbg_items, b->d_dbg_pool, b->d_dbg_stage, b->d_reach, b->d_clear, b->d_clear_map,
+	                b->d_label_cull, b->d_label_extra, b->d_probes, b->d_dbg_items, b->d_dbg_pool, b->d_dbg_stage, b->d_reach, b->d_clear, b->d_clear_map, b->d_relief,
 	                b->d_sl, b->d_sl_crops, b->d_sl_s0, b->d_lt, b->d_lt_anchors};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
@@ -703,6 +706,7 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	hm_release(b->reach_hm);
 	hm_release(b->clear_hm);
 	hm_release(b->clear_map_hm);
+	hm_release(b->relief_hm);
 	if (b->ev_render) (void)hipEventDestroy(b->ev_render);
 	if (b->ev) {
 		for (int r = 0; r < smhv_batch::TIMING_RING; ++r)
@@ -3349,5 +3353,6 @@ extern "C" SMHV_API int smhv_heightmap_overlay(smhv_ctx *c, const smhv_heightmap
 #include "smh_debugtext.inc"
 #include "smh_reach.inc"
 #include "smh_clear.inc"
+#include "smh_relief.inc"
 #include "smh_scalelabels.inc"
 #include "smh_labeltext.inc"

@@ -2,6 +2,7 @@
 render call.  MapViewport is the app's own (src/ui/map.rs:14-126): calc letter-boxes the map into the window, zooms and pans;
 the same object feeds the firing solutions (firing_viewport), so the numbers and the picture use one viewport."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -265,6 +266,50 @@ class ClearanceOptions:
             for k in range(4):
                 for name in ("out_of_range", "clear", "blocked", "los"):
                     getattr(o, name)[k] = int(self.palette[name][k])
+        return o
+
+
+# ---- terrain relief (smhv_batch_relief / smhv_relief_map): contour lines, hillshade and heights of every window pixel ---------------
+def relief_light(azimuth_deg=315.0, altitude_deg=45.0):
+    """The unit vector from the ground towards a light at compass azimuth (0 = north = up on the map, 90 = east) and altitude above
+    the horizon, in heightmap axes (x right, y down, z up) -> (lx, ly, lz).  A host convenience: the library takes the vector."""
+    az, alt = math.radians(float(azimuth_deg)), math.radians(float(altitude_deg))
+    return (math.sin(az) * math.cos(alt), -math.cos(az) * math.cos(alt), math.sin(alt))
+
+
+class ReliefOptions:
+    """What a relief call computes: interval_m = metres between contour levels (0: none), base_m = the height of level 0, major_every
+    = every M-th level is an index contour (0: none); exaggeration, light = the hillshade's slope factor and its vector towards the
+    light (relief_light()); nearest = the nearest texel's height, not the bilinear one; paint / bytes / shades / heights = tint the
+    render slab / write that plane; contour, major = rgba with a = the blend weight, shade_weight = the hillshade's (None: the
+    library's, smhv_relief_defaults)."""
+
+    def __init__(self, interval_m=None, base_m=None, major_every=None, exaggeration=None, light=None, nearest=False, paint=True, bytes=False,
+                 shades=False, heights=False, contour=None, major=None, shade_weight=None):
+        self.interval_m, self.base_m, self.major_every, self.exaggeration, self.light = interval_m, base_m, major_every, exaggeration, light
+        self.nearest, self.paint, self.bytes, self.shades, self.heights = bool(nearest), bool(paint), bool(bytes), bool(shades), bool(heights)
+        self.contour, self.major, self.shade_weight = contour, major, shade_weight
+
+    def struct(self):
+        """-> smhv_relief_options."""
+        o = L.ReliefOptionsStruct()
+        L.check(L.load().smhv_relief_defaults(C.byref(o)))
+        o.flags = ((L.RELIEF_PAINT if self.paint else 0) | (L.RELIEF_BYTES if self.bytes else 0) | (L.RELIEF_SHADES if self.shades else 0) |
+                   (L.RELIEF_HEIGHTS if self.heights else 0) | (L.RELIEF_NEAREST if self.nearest else 0))
+        for name in ("interval_m", "base_m", "exaggeration"):
+            if getattr(self, name) is not None:
+                setattr(o, name, float(getattr(self, name)))
+        if self.major_every is not None:
+            o.major_every = int(self.major_every)
+        if self.shade_weight is not None:
+            o.shade_weight = int(self.shade_weight)
+        if self.light is not None:
+            for k in range(3):
+                o.light[k] = float(self.light[k])
+        for name in ("contour", "major"):
+            if getattr(self, name) is not None:
+                for k in range(4):
+                    getattr(o, name)[k] = int(getattr(self, name)[k])
         return o
 
 

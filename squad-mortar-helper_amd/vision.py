@@ -351,6 +351,26 @@ class HipVision:
                                              image.ctypes.data if image is not None else None, out.ctypes.data if out is not None else None, C.byref(res)))
         return out, res
 
+    def relief_map(self, options, relief, minimap=None, heightmap=None, image=None, bytes=True, shades=True, heights=True):
+        """The terrain relief of one window (smhv_relief_map; stateless like reach_map): options = a RenderOptions (the window and the
+        viewport), relief = a ReliefOptions; minimap = (left, right, top, bottom) or None, heightmap: the terrain.  image: uint8
+        [out_h, out_w, 4], tinted in place; bytes / shades / heights: return that plane.
+        -> (uint8 [out_h, out_w] or None, uint8 [out_h, out_w] or None, float32 [out_h, out_w] or None, ReliefResult)."""
+        ro = relief.struct()
+        h, w = int(options.out_h), int(options.out_w)
+        if image is not None and (image.dtype != np.uint8 or image.shape != (h, w, 4) or not image.flags["C_CONTIGUOUS"]):
+            raise L.VisionError(L.E_INVALID, "relief_map: image must be a contiguous uint8 [%d, %d, 4]" % (h, w))
+        shape = (max(h, 1), max(w, 1))
+        fb = np.empty(shape, np.uint8) if bytes else None
+        sh = np.empty(shape, np.uint8) if shades else None
+        hs = np.empty(shape, np.float32) if heights else None
+        res = L.ReliefResult()
+        mm = (C.c_uint32 * 4)(*[int(v) for v in minimap]) if minimap is not None else None
+        L.check(self._lib.smhv_relief_map(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(options), C.byref(ro), mm,
+                                          image.ctypes.data if image is not None else None, fb.ctypes.data if fb is not None else None,
+                                          sh.ctypes.data if sh is not None else None, hs.ctypes.data if hs is not None else None, C.byref(res)))
+        return fb, sh, hs, res
+
     def probe(self, viewport, points, out_w=1, out_h=1):
         """The vision debugger's numbers of the current frame at `points` = [(mx, my)] window positions through `viewport` (a
         MapViewport) -> a ctypes array of MAX_PROBES Probe.  The per-call path has no probe-only entry point: this is
