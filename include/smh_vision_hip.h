@@ -238,7 +238,13 @@ SMHV_API int smhv_batch_layout_get(smhv_batch *b, smhv_batch_layout *out);
  * packed, so with a width that is no multiple of 4 every row, and every frame after the first, starts 4, 8 or 12 bytes off a
  * 16-byte boundary anyway; the kernels' 16-byte loads take any 4-byte aligned address and a base pointer at such an offset gives
  * the same outputs, bit for bit (16-byte alignment and frame_w % 4 == 0 are merely the fastest case).  A pointer that is not
- * 4-byte aligned is refused with SMHV_E_INVALID before anything is enqueued. */
+ * 4-byte aligned is refused with SMHV_E_INVALID before anything is enqueued.
+ * Indices >= n (here and in smhv_pipeline_submit, for the slot's batch): a run over n < max_frames frames touches nothing of the
+ * frames from n on -- every kernel of the run is launched over n frames.  Their records, images, bit rows and tile-major masks stay,
+ * byte for byte, what the newest earlier run of this batch that covered the index left (zeroes where none did), and the slabs the
+ * library makes on demand (d_mask, d_ui) are brought up to date for every frame any run since the last read covered, not only for
+ * this run's n.  Within 0 .. n - 1 a frame the run finds closed gets its record and keeps its older images and bit rows; its
+ * tile-major mask then reads as not written (smhv_batch_read_tile_mask). */
 SMHV_API int smhv_batch_run(smhv_batch *b, const void *d_frames, uint32_t n, uint32_t stages, int grayscale, uint32_t max_gap,
                             const smhv_anchors *anchors, void *stream);
 /* device pointers of the batch outputs (valid for the life of the batch); any of them may be NULL.
@@ -375,6 +381,8 @@ typedef struct {
 SMHV_API int smhv_pipeline_create_ex(smhv_ctx *ctx, uint32_t frame_w, uint32_t frame_h, uint32_t max_frames, uint32_t depth,
                                      const smhv_pipeline_options *options, smhv_pipeline **out);
 SMHV_API void smhv_pipeline_destroy(smhv_pipeline *p);
+/* n may differ from submission to submission (1 .. max_frames): what the slot holds at indices >= n is what its earlier submissions
+ * left there -- the rule at smhv_batch_run. */
 SMHV_API int smhv_pipeline_submit(smhv_pipeline *p, const void *d_frames, uint32_t n, uint32_t stages, int grayscale, uint32_t max_gap,
                                   const smhv_anchors *anchors, void *after_stream, uint32_t *slot);
 SMHV_API int smhv_pipeline_wait(smhv_pipeline *p, uint32_t slot);

@@ -841,6 +841,9 @@ def test_ingest_roi_upload_hashes_on_the_host_and_uploads_only_what_is_read(visi
             assert r.map_open == ref["map_open"] == 1 and np.array_equal(lines, ref["lines"])
         # the slab frames hold the two rectangles and zeros elsewhere
         import ctypes as C
+        from collections import namedtuple
+        from ingest_cases import expected_slab_frame
+        Size = namedtuple("Size", "W H")
         nb = W * H * 4
         x, y, rw, rh = o.map_bounds(W, H)
         hip = C.CDLL("libamdhip64.so")
@@ -850,6 +853,7 @@ def test_ingest_roi_upload_hashes_on_the_host_and_uploads_only_what_is_read(visi
             assert hip.hipMemcpy(fr_dev.ctypes.data, ptr + i * nb, nb, 2) == 0            # hipMemcpyDeviceToHost
             assert np.array_equal(fr_dev[y:y + rh, x:x + rw], f[y:y + rh, x:x + rw])
             assert not fr_dev[:min(y, 8), :8].any() and fr_dev.sum() < f.sum()
+            assert np.array_equal(fr_dev, expected_slab_frame(f, Size(W, H), "bgra")), (W, H, i)     # ... over the whole frame, exactly
         # a slab frame also feeds the per-call path
         vision.load_frame_device(ptr + 2 * nb, W, H)
         ui, roi = vision.crop_to_map(True)
