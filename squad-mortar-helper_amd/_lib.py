@@ -563,6 +563,11 @@ def load():
     return _lib
 
 
+def _hm(heightmap):
+    """The library's handle of a Heightmap, or None for none."""
+    return heightmap._hm if heightmap is not None else None
+
+
 def check(rc):
     if rc != 0:
         raise VisionError(rc, load().smhv_last_error().decode("utf-8", "replace"))

@@ -44,6 +44,10 @@ def results_to_dicts(recs):
 _PTR_KEYS = ("results", "ui", "mask", "ocr", "scales", "bits")
 
 
+def _ptr(address):
+    return C.c_void_p(int(address)) if address else None
+
+
 class _DevicePtrs(Mapping):
     """FrameBatch.device_ptrs(): read-only; the "mask" and "ui" entries ask the library for d_mask / d_ui the first time they are read."""
 
@@ -179,6 +183,39 @@ class FrameBatch:
         L.check(self._lib.smhv_batch_read_tile_mask(self._b, frame, tiled.ctypes.data, occ.ctypes.data, bits.ctypes.data, C.byref(written)))
         return (tiled if written.value else None), (occ if written.value else None), bits, xoff
 
+    def _read_slab(self, fn, ctype, first, n, per_frame=1):
+        """Synchronising host copy of rows [first, first + n) of a result slab (a smhv_batch_read_*) -> a ctypes array of n * per_frame ctype."""
+        n = self.max_frames - first if n is None else n
+        out = (ctype * (n * per_frame))()
+        L.check(fn(self._b, first, n, out))
+        return out
+
+    def _slab_ptr(self, fn, k=1):
+        """The device address(es) a smhv_batch_*_ptr hands out: one int, or a tuple of k."""
+        d = [C.c_void_p() for _ in range(k)]
+        L.check(fn(self._b, *[C.byref(x) for x in d]))
+        return d[0].value or 0 if k == 1 else tuple(x.value or 0 for x in d)
+
+    @staticmethod
+    def _plane(made, name, ptr, asked, shape, dtype="uint8"):
+        """The device address of an output plane: `ptr`, or, when the plane is asked for and ptr is None, that of a zeroed torch tensor of
+        `shape` allocated here and kept in made[name]."""
+        if asked and ptr is None:
+            import torch
+            made[name] = torch.zeros(shape, dtype=getattr(torch, dtype), device="cuda")
+            ptr = made[name].data_ptr()
+        return ptr
+
+    @staticmethod
+    def _call(made, fn, *args):
+        """fn(*args), checked; when planes were allocated here (`made`), after their zeros are in place, and the device has finished on return."""
+        if made:
+            import torch
+            torch.cuda.synchronize()
+        L.check(fn(*args))
+        if made:
+            torch.cuda.synchronize()
+
     def read_results(self, first=0, n=None, check=True):
         """Synchronising host copy of the records.  A frame the library gave up (status != 0 in its record) makes the call
         raise VisionError(E_STATE) -- the reference drops a frame on any Err (src/vision/mod.rs:272-276); check=False returns
@@ -200,22 +237,18 @@ class FrameBatch:
         """Bind a Heightmap (None = none) and the options for STAGE_FIRING runs of this batch (smhv_batch_set_firing; the
         library keeps its own reference of the heightmap).  Without a call the runs use no heightmap and the default options."""
         opt = L.firing_options(fit_to_minimap, viewport)
-        L.check(self._lib.smhv_batch_set_firing(self._b, heightmap._hm if heightmap is not None else None, C.byref(opt)))
+        L.check(self._lib.smhv_batch_set_firing(self._b, L._hm(heightmap), C.byref(opt)))
 
     def read_firing(self, first=0, n=None):
         """Synchronising host copy of the firing slab -> (n_lines uint32 [n], numpy structured array [n, MAX_LINES] of smhv_firing)."""
-        n = self.max_frames - first if n is None else n
-        out = (L.FiringResult * n)()
-        L.check(self._lib.smhv_batch_read_firing(self._b, first, n, out))
-        raw = np.frombuffer(out, np.uint8).reshape(n, C.sizeof(L.FiringResult))
-        n_lines = raw[:, :4].copy().view(np.uint32).reshape(n)
-        lines = raw[:, 8:].copy().view(L.firing_dtype()).reshape(n, L.MAX_LINES)
+        out = self._read_slab(self._lib.smhv_batch_read_firing, L.FiringResult, first, n)
+        raw = np.frombuffer(out, np.uint8).reshape(len(out), C.sizeof(L.FiringResult))
+        n_lines = raw[:, :4].copy().view(np.uint32).reshape(len(out))
+        lines = raw[:, 8:].copy().view(L.firing_dtype()).reshape(len(out), L.MAX_LINES)
         return n_lines, lines
 
     def firing_ptr(self):
-        d = C.c_void_p()
-        L.check(self._lib.smhv_batch_firing_ptr(self._b, C.byref(d)))
-        return d.value or 0
+        return self._slab_ptr(self._lib.smhv_batch_firing_ptr)
 
     def read_overlay(self, frame):
         """Synchronising host copy of a frame's heightmap overlay (STAGE_HEIGHTMAP_OVERLAY) -> uint8 [h, w, 4] RGBA."""
@@ -223,9 +256,7 @@ class FrameBatch:
 
     def overlay_ptr(self):
         """Device address of the overlay slab (the ui slab's layout: layout.ui_pitch / ui_stride / ui_offset)."""
-        d = C.c_void_p()
-        L.check(self._lib.smhv_batch_overlay_ptr(self._b, C.byref(d)))
-        return d.value or 0
+        return self._slab_ptr(self._lib.smhv_batch_overlay_ptr)
 
     def render(self, viewport, out_w, out_h, first=0, n=None, heightmap=None, markers=False, fit_to_minimap=True, background=(0, 0, 0, 255),
                stream=None, options=None, layers=None):
@@ -238,10 +269,10 @@ class FrameBatch:
         opt = options if options is not None else render_options(viewport, out_w, out_h, heightmap is not None, markers, fit_to_minimap, background)
         if layers is not None:
             ly, keep = layers.struct()
-            L.check(self._lib.smhv_batch_render_layers(self._b, first, n, heightmap._hm if heightmap is not None else None, C.byref(opt), C.byref(ly), stream))
+            L.check(self._lib.smhv_batch_render_layers(self._b, first, n, L._hm(heightmap), C.byref(opt), C.byref(ly), stream))
             del keep
             return
-        L.check(self._lib.smhv_batch_render(self._b, first, n, heightmap._hm if heightmap is not None else None, C.byref(opt), stream))
+        L.check(self._lib.smhv_batch_render(self._b, first, n, L._hm(heightmap), C.byref(opt), stream))
 
     def render_size(self):
         """(out_w, out_h) of the most recent render, from the library."""
@@ -268,21 +299,16 @@ class FrameBatch:
         viewport); labels: a LabelOptions; heightmap: what the numbers take their range and altitude from.  Asynchronous."""
         n = self.max_frames - first if n is None else n
         lo, keep = labels.struct()
-        L.check(self._lib.smhv_batch_render_labels(self._b, first, n, heightmap._hm if heightmap is not None else None, C.byref(options), C.byref(lo), stream))
+        L.check(self._lib.smhv_batch_render_labels(self._b, first, n, L._hm(heightmap), C.byref(options), C.byref(lo), stream))
         del keep
 
     def read_labels(self, first=0, n=None):
         """Synchronising host copy of the label slab -> a ctypes array of n LabelResult."""
-        n = self.max_frames - first if n is None else n
-        out = (L.LabelResult * n)()
-        L.check(self._lib.smhv_batch_read_labels(self._b, first, n, out))
-        return out
+        return self._read_slab(self._lib.smhv_batch_read_labels, L.LabelResult, first, n)
 
     def labels_ptr(self):
         """Device address of the label slab (one smhv_label_result per frame)."""
-        d = C.c_void_p()
-        L.check(self._lib.smhv_batch_labels_ptr(self._b, C.byref(d)))
-        return d.value or 0
+        return self._slab_ptr(self._lib.smhv_batch_labels_ptr)
 
     def reach(self, options, reach, first=0, n=None, heightmap=None, classes_ptr=None, stream=None):
         """The reach map of frames [first, first + n) on `stream` (smhv_batch_reach): options = a RenderOptions (the window and the
@@ -292,30 +318,18 @@ class FrameBatch:
         asynchronous and returns None, as it does without classes."""
         n = self.max_frames - first if n is None else n
         ro = reach.struct()
-        out = None
-        if reach.classes and classes_ptr is None:
-            import torch
-            out = torch.zeros((n, int(options.out_h), int(options.out_w)), dtype=torch.uint8, device="cuda")
-            torch.cuda.synchronize()
-            classes_ptr = out.data_ptr()
-        L.check(self._lib.smhv_batch_reach(self._b, first, n, heightmap._hm if heightmap is not None else None, C.byref(options), C.byref(ro),
-                                           C.c_void_p(int(classes_ptr)) if classes_ptr else None, C.c_void_p(int(stream)) if stream else None))
-        if out is not None:
-            torch.cuda.synchronize()
-        return out
+        made = {}
+        classes_ptr = self._plane(made, "classes", classes_ptr, reach.classes, (n, int(options.out_h), int(options.out_w)))
+        self._call(made, self._lib.smhv_batch_reach, self._b, first, n, L._hm(heightmap), C.byref(options), C.byref(ro), _ptr(classes_ptr), _ptr(stream))
+        return made.get("classes")
 
     def read_reach(self, first=0, n=None):
         """Synchronising host copy of the reach slab -> a ctypes array of n ReachResult."""
-        n = self.max_frames - first if n is None else n
-        out = (L.ReachResult * n)()
-        L.check(self._lib.smhv_batch_read_reach(self._b, first, n, out))
-        return out
+        return self._read_slab(self._lib.smhv_batch_read_reach, L.ReachResult, first, n)
 
     def reach_ptr(self):
         """Device address of the reach slab (one smhv_reach_result per frame)."""
-        d = C.c_void_p()
-        L.check(self._lib.smhv_batch_reach_ptr(self._b, C.byref(d)))
-        return d.value or 0
+        return self._slab_ptr(self._lib.smhv_batch_reach_ptr)
 
     def relief(self, options, relief, first=0, n=None, heightmap=None, bytes_ptr=None, shades_ptr=None, heights_ptr=None, stream=None):
         """The terrain relief of frames [first, first + n) on `stream` (smhv_batch_relief): options = a RenderOptions (the window and
@@ -326,33 +340,20 @@ class FrameBatch:
         n = self.max_frames - first if n is None else n
         ro = relief.struct()
         out = {}
-        ptrs = dict(bytes=bytes_ptr, shades=shades_ptr, heights=heights_ptr)
-        for name in ("bytes", "shades", "heights"):
-            if getattr(relief, name) and ptrs[name] is None:
-                import torch
-                out[name] = torch.zeros((n, int(options.out_h), int(options.out_w)), dtype=torch.float32 if name == "heights" else torch.uint8, device="cuda")
-                ptrs[name] = out[name].data_ptr()
-        if out:
-            torch.cuda.synchronize()
-        planes = L.ReliefPlanes(*[int(ptrs[k]) if ptrs[k] else None for k in ("bytes", "shades", "heights")])
-        L.check(self._lib.smhv_batch_relief(self._b, first, n, heightmap._hm if heightmap is not None else None, C.byref(options), C.byref(ro),
-                                            C.byref(planes), C.c_void_p(int(stream)) if stream else None))
-        if out:
-            torch.cuda.synchronize()
+        shape = (n, int(options.out_h), int(options.out_w))
+        ptrs = [self._plane(out, name, ptr, getattr(relief, name), shape, "float32" if name == "heights" else "uint8")
+                for name, ptr in (("bytes", bytes_ptr), ("shades", shades_ptr), ("heights", heights_ptr))]
+        planes = L.ReliefPlanes(*[int(p) if p else None for p in ptrs])
+        self._call(out, self._lib.smhv_batch_relief, self._b, first, n, L._hm(heightmap), C.byref(options), C.byref(ro), C.byref(planes), _ptr(stream))
         return out
 
     def read_relief(self, first=0, n=None):
         """Synchronising host copy of the relief slab -> a ctypes array of n ReliefResult."""
-        n = self.max_frames - first if n is None else n
-        out = (L.ReliefResult * n)()
-        L.check(self._lib.smhv_batch_read_relief(self._b, first, n, out))
-        return out
+        return self._read_slab(self._lib.smhv_batch_read_relief, L.ReliefResult, first, n)
 
     def relief_ptr(self):
         """Device address of the relief slab (one smhv_relief_result per frame)."""
-        d = C.c_void_p()
-        L.check(self._lib.smhv_batch_relief_ptr(self._b, C.byref(d)))
-        return d.value or 0
+        return self._slab_ptr(self._lib.smhv_batch_relief_ptr)
 
     def clearance(self, clearance, first=0, n=None, heightmap=None, fit_to_minimap=True, viewport=None, profiles_ptr=None, profiles=False, stream=None):
         """The terrain clearance of the detected lines of frames [first, first + n) on `stream` (smhv_batch_clearance): clearance = a
@@ -363,30 +364,18 @@ class FrameBatch:
         n = self.max_frames - first if n is None else n
         co = clearance.struct()
         fo = L.firing_options(fit_to_minimap, viewport)
-        out = None
-        if profiles and profiles_ptr is None:
-            import torch
-            out = torch.zeros((n, L.MAX_LINES, L.CLEAR_PROFILE), dtype=torch.float32, device="cuda")
-            torch.cuda.synchronize()
-            profiles_ptr = out.data_ptr()
-        L.check(self._lib.smhv_batch_clearance(self._b, first, n, heightmap._hm if heightmap is not None else None, C.byref(fo), C.byref(co),
-                                               C.c_void_p(int(profiles_ptr)) if profiles_ptr else None, C.c_void_p(int(stream)) if stream else None))
-        if out is not None:
-            torch.cuda.synchronize()
-        return out
+        made = {}
+        profiles_ptr = self._plane(made, "profiles", profiles_ptr, profiles, (n, L.MAX_LINES, L.CLEAR_PROFILE), "float32")
+        self._call(made, self._lib.smhv_batch_clearance, self._b, first, n, L._hm(heightmap), C.byref(fo), C.byref(co), _ptr(profiles_ptr), _ptr(stream))
+        return made.get("profiles")
 
     def read_clearance(self, first=0, n=None):
         """Synchronising host copy of the clearance slab -> a ctypes array of n ClearanceResult."""
-        n = self.max_frames - first if n is None else n
-        out = (L.ClearanceResult * n)()
-        L.check(self._lib.smhv_batch_read_clearance(self._b, first, n, out))
-        return out
+        return self._read_slab(self._lib.smhv_batch_read_clearance, L.ClearanceResult, first, n)
 
     def clearance_ptr(self):
         """Device address of the clearance slab (one smhv_clearance_result per frame)."""
-        d = C.c_void_p()
-        L.check(self._lib.smhv_batch_clearance_ptr(self._b, C.byref(d)))
-        return d.value or 0
+        return self._slab_ptr(self._lib.smhv_batch_clearance_ptr)
 
     def clearance_map(self, options, clearance, first=0, n=None, heightmap=None, bytes_ptr=None, stream=None):
         """The clearance map of frames [first, first + n) on `stream` (smhv_batch_clearance_map): options = a RenderOptions (the
@@ -396,30 +385,18 @@ class FrameBatch:
         as it does without bytes."""
         n = self.max_frames - first if n is None else n
         co = clearance.struct()
-        out = None
-        if clearance.bytes and bytes_ptr is None:
-            import torch
-            out = torch.zeros((n, int(options.out_h), int(options.out_w)), dtype=torch.uint8, device="cuda")
-            torch.cuda.synchronize()
-            bytes_ptr = out.data_ptr()
-        L.check(self._lib.smhv_batch_clearance_map(self._b, first, n, heightmap._hm if heightmap is not None else None, C.byref(options), C.byref(co),
-                                                   C.c_void_p(int(bytes_ptr)) if bytes_ptr else None, C.c_void_p(int(stream)) if stream else None))
-        if out is not None:
-            torch.cuda.synchronize()
-        return out
+        made = {}
+        bytes_ptr = self._plane(made, "bytes", bytes_ptr, clearance.bytes, (n, int(options.out_h), int(options.out_w)))
+        self._call(made, self._lib.smhv_batch_clearance_map, self._b, first, n, L._hm(heightmap), C.byref(options), C.byref(co), _ptr(bytes_ptr), _ptr(stream))
+        return made.get("bytes")
 
     def read_clearance_map(self, first=0, n=None):
         """Synchronising host copy of the clearance-map slab -> a ctypes array of n ClearanceMapResult."""
-        n = self.max_frames - first if n is None else n
-        out = (L.ClearanceMapResult * n)()
-        L.check(self._lib.smhv_batch_read_clearance_map(self._b, first, n, out))
-        return out
+        return self._read_slab(self._lib.smhv_batch_read_clearance_map, L.ClearanceMapResult, first, n)
 
     def clearance_map_ptr(self):
         """Device address of the clearance-map slab (one smhv_clearance_map_result per frame)."""
-        d = C.c_void_p()
-        L.check(self._lib.smhv_batch_clearance_map_ptr(self._b, C.byref(d)))
-        return d.value or 0
+        return self._slab_ptr(self._lib.smhv_batch_clearance_map_ptr)
 
     def scale_labels(self, frames_ptr, n, stream=0):
         """The scale labels of frames [0, n) (smhv_batch_scale_labels), on `stream` behind this batch's run over the same frames
@@ -437,9 +414,7 @@ class FrameBatch:
 
     def scale_labels_ptr(self):
         """Device addresses of the label slab (one smhv_scale_label_frame per frame) and the crop slab."""
-        d, c = C.c_void_p(), C.c_void_p()
-        L.check(self._lib.smhv_batch_scale_labels_ptr(self._b, C.byref(d), C.byref(c)))
-        return d.value or 0, c.value or 0
+        return self._slab_ptr(self._lib.smhv_batch_scale_labels_ptr, 2)
 
     def label_text(self, atlas, n, stream=0):
         """The texts of the scale labels of frames [0, n) read against `atlas` (a GlyphAtlas; smhv_batch_label_text), on `stream`
@@ -448,16 +423,11 @@ class FrameBatch:
 
     def read_label_text(self, first=0, n=None):
         """Synchronising host copy of the text slab -> a ctypes array of n LabelTextFrame."""
-        n = self.max_frames - first if n is None else n
-        out = (L.LabelTextFrame * n)()
-        L.check(self._lib.smhv_batch_read_label_text(self._b, first, n, out))
-        return out
+        return self._read_slab(self._lib.smhv_batch_read_label_text, L.LabelTextFrame, first, n)
 
     def label_text_ptr(self):
         """Device addresses of the text slab (one smhv_label_text_frame per frame) and of the frames' smhv_anchors, tightly packed."""
-        d, a = C.c_void_p(), C.c_void_p()
-        L.check(self._lib.smhv_batch_label_text_ptr(self._b, C.byref(d), C.byref(a)))
-        return d.value or 0, a.value or 0
+        return self._slab_ptr(self._lib.smhv_batch_label_text_ptr, 2)
 
     def run_label_anchors(self, frames_ptr, n, stages=L.STAGE_ALL, grayscale=True, max_gap=15, stream=0):
         """run() with the anchors the last label_text() left on the device (smhv_batch_run_label_anchors): the meters never visit the host."""
@@ -474,16 +444,11 @@ class FrameBatch:
 
     def read_probes(self, first=0, n=None):
         """Synchronising host copy of the probe slab -> a ctypes array of n * MAX_PROBES Probe (frame f's at [f * MAX_PROBES])."""
-        n = self.max_frames - first if n is None else n
-        out = (L.Probe * (n * L.MAX_PROBES))()
-        L.check(self._lib.smhv_batch_read_probes(self._b, first, n, out))
-        return out
+        return self._read_slab(self._lib.smhv_batch_read_probes, L.Probe, first, n, L.MAX_PROBES)
 
     def probes_ptr(self):
         """Device address of the probe slab (MAX_PROBES smhv_probe per frame)."""
-        d = C.c_void_p()
-        L.check(self._lib.smhv_batch_probes_ptr(self._b, C.byref(d)))
-        return d.value or 0
+        return self._slab_ptr(self._lib.smhv_batch_probes_ptr)
 
     def render_debug(self, options, debug, first=0, n=None, stream=None):
         """Draw the debug text and the vision debugger onto the images of the most recent render over frames [first, first + n) on
@@ -592,7 +557,7 @@ class Pipeline:
         """Bind a Heightmap (None = none) and the options for STAGE_FIRING submissions made after this call
         (smhv_pipeline_set_firing); submissions in flight keep what they were submitted with."""
         opt = L.firing_options(fit_to_minimap, viewport)
-        L.check(self._lib.smhv_pipeline_set_firing(self._p, heightmap._hm if heightmap is not None else None, C.byref(opt)))
+        L.check(self._lib.smhv_pipeline_set_firing(self._p, L._hm(heightmap), C.byref(opt)))
 
     def search_stats(self):
         """Diagnostic (synchronises): the frame-granular line search of a pipeline of depth >= 3 -> dict, or None."""

@@ -31,19 +31,6 @@ static int check_clearance_options(const smhv_clearance_options *o, bool map, co
 	return SMHV_OK;
 }
 
-// a batch's result slab of `row` bytes per frame, allocated and zeroed by the first call that needs it
-static int clear_slab(smhv_batch *b, void **slab, size_t row, const char *what) {
-	if (*slab) return SMHV_OK;
-	hipError_t e = hipMalloc(slab, row * (size_t)b->max_frames);
-	if (e == hipSuccess) e = hipMemset(*slab, 0, row * (size_t)b->max_frames);
-	if (e != hipSuccess) {
-		if (*slab) (void)hipFree(*slab);
-		*slab = nullptr;
-		return fail(SMHV_E_HIP, "%s slab (%u frames): %s", what, b->max_frames, hipGetErrorString(e));
-	}
-	return SMHV_OK;
-}
-
 // ---- the lines
 extern "C" SMHV_API int smhv_batch_clearance(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_firing_options *fopt,
                                              const smhv_clearance_options *opt, void *d_profiles, void *stream) {
@@ -58,7 +45,7 @@ extern "C" SMHV_API int smhv_batch_clearance(smhv_batch *b, uint32_t first, uint
 	rc = check_hm_device(hm, b->ctx->device, "batch_clearance", "batch");
 	if (rc) return rc;
 	HIPCHK(hipSetDevice(b->ctx->device));
-	rc = clear_slab(b, (void **)&b->d_clear, sizeof(smhv_clearance_result), "clearance");
+	rc = first_use_slabs(b, "clearance slab (%u frames)", {{(void **)&b->d_clear, sizeof(smhv_clearance_result) * (size_t)b->max_frames, 0}});
 	if (rc) return rc;
 	hipStream_t s = (hipStream_t)stream;
 	hm_rebind(&b->clear_hm, hm);                                   // the batch's reference of the heightmap its enqueued call reads
@@ -68,29 +55,22 @@ extern "C" SMHV_API int smhv_batch_clearance(smhv_batch *b, uint32_t first, uint
 	firing_run_params(hm, &fo, &r.fr);
 	r.margin_m = opt->margin_m;
 	r.samples = opt->samples;
-	for (uint32_t done = 0; done < n;) {                           // at most 65,535 frames per launch (the grid's second dimension)
-		const uint32_t k = std::min(n - done, 65535u);
+	return for_each_launch(n, [&](uint32_t done, uint32_t k) -> int {
 		ClearLinesRun part = r;
 		part.res = b->d_results + first + done;
 		part.out = b->d_clear + first + done;
 		part.profiles = d_profiles ? (float *)d_profiles + (size_t)done * SMHV_MAX_LINES * SMH_CLEAR_PROFILE : nullptr;
 		HIPCHK(launch_clear_lines(part, k, s));
-		done += k;
-	}
-	return SMHV_OK;
+		return SMHV_OK;
+	});
 }
 
 extern "C" SMHV_API int smhv_batch_read_clearance(smhv_batch *b, uint32_t first, uint32_t n, smhv_clearance_result *out) {
-	if (!b || !out || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_read_clearance: bad arguments");
-	if (!b->d_clear) return fail(SMHV_E_STATE, "batch_read_clearance: this batch has computed no clearance");
-	return batch_read_rows(b, b->d_clear, sizeof(smhv_clearance_result), first, n, out);
+	return batch_read_slab(b, b ? b->d_clear : nullptr, sizeof(smhv_clearance_result), first, n, out, "batch_read_clearance", "this batch has computed no clearance");
 }
 
 extern "C" SMHV_API int smhv_batch_clearance_ptr(smhv_batch *b, void **d_clearance) {
-	if (!b || !d_clearance) return fail(SMHV_E_INVALID, "batch_clearance_ptr: null argument");
-	if (!b->d_clear) return fail(SMHV_E_STATE, "batch_clearance_ptr: this batch has computed no clearance");
-	*d_clearance = b->d_clear;
-	return SMHV_OK;
+	return batch_slab_ptr(b, b ? b->d_clear : nullptr, d_clearance, "batch_clearance_ptr", "this batch has computed no clearance");
 }
 
 // The per-call path: the lines up, the kernel, the records and the profiles down, through the context's pinned block.
@@ -116,21 +96,23 @@ extern "C" SMHV_API int smhv_clearance_lines(smhv_ctx *c, const smhv_line *lines
 	r.has_mm = minimap ? 1u : 0u;
 	if (minimap) memcpy(r.mm, minimap, sizeof r.mm);
 	// [the lines][the records][the profiles], each part on a 256-byte boundary
-	const size_t in_bytes = sizeof(smhv_line) * (size_t)n, rec_off = (in_bytes + 255u) & ~(size_t)255u, rec_bytes = sizeof(smhv_clearance) * (size_t)n;
-	const size_t prof_off = rec_off + ((rec_bytes + 255u) & ~(size_t)255u), prof_bytes = profiles ? sizeof(float) * SMH_CLEAR_PROFILE * (size_t)n : 0u;
+	StageLayout lay;
+	const size_t in_bytes = sizeof(smhv_line) * (size_t)n;
+	lay.take(in_bytes);
+	const StagePart rec = lay.part(out, sizeof(smhv_clearance) * (size_t)n), prof = lay.part(profiles, sizeof(float) * SMH_CLEAR_PROFILE * (size_t)n);
 	std::lock_guard<std::mutex> lk(c->fire_mu);
-	rc = ctx_stage_reserve(c, prof_off + prof_bytes);
+	rc = ctx_stage_reserve(c, lay.total());
 	if (rc) return rc;
 	r.lines = (const smhv_line *)c->d_fire;
-	r.out_lines = (smhv_clearance *)(c->d_fire + rec_off);
-	r.profiles = profiles ? (float *)(c->d_fire + prof_off) : nullptr;
+	r.out_lines = (smhv_clearance *)(c->d_fire + rec.off);
+	r.profiles = profiles ? (float *)(c->d_fire + prof.off) : nullptr;
 	memcpy(c->h_fire, lines, in_bytes);
 	HIPCHK(hipMemcpyAsync(c->d_fire, c->h_fire, in_bytes, hipMemcpyHostToDevice, c->s_main));
 	HIPCHK(launch_clear_lines(r, 1, c->s_main));
-	HIPCHK(hipMemcpyAsync(c->h_fire + rec_off, c->d_fire + rec_off, prof_off + prof_bytes - rec_off, hipMemcpyDeviceToHost, c->s_main));
+	HIPCHK(hipMemcpyAsync(c->h_fire + rec.off, c->d_fire + rec.off, lay.total() - rec.off, hipMemcpyDeviceToHost, c->s_main));   // the records and the profiles: not the lines
 	HIPCHK(wait_stream(c->s_main));
-	memcpy(out, c->h_fire + rec_off, rec_bytes);
-	if (profiles) memcpy(profiles, c->h_fire + prof_off, prof_bytes);
+	memcpy(out, c->h_fire + rec.off, rec.len);
+	if (profiles) memcpy(profiles, c->h_fire + prof.off, prof.len);
 	return SMHV_OK;
 }
 
@@ -167,49 +149,27 @@ extern "C" SMHV_API int smhv_batch_clearance_map(smhv_batch *b, uint32_t first, 
 	if (rc) return rc;
 	const bool paint = (opt->flags & SMHV_CLEAR_PAINT) != 0u, bytes = (opt->flags & SMHV_CLEAR_BYTES) != 0u;
 	if (bytes && !d_bytes) return fail(SMHV_E_INVALID, "batch_clearance_map: SMHV_CLEAR_BYTES and a null d_bytes");
-	if (paint) {
-		if (!b->d_render) return fail(SMHV_E_STATE, "batch_clearance_map: SMHV_CLEAR_PAINT and this batch has not rendered");
-		rc = check_window_is_last_render(b, ropt, "batch_clearance_map");
-		if (rc) return rc;
-	}
-	HIPCHK(hipSetDevice(b->ctx->device));
-	rc = clear_slab(b, (void **)&b->d_clear_map, sizeof(smhv_clearance_map_result), "clearance-map");
-	if (rc) return rc;
-	hipStream_t s = (hipStream_t)stream;
-	if (paint) HIPCHK(hipStreamWaitEvent(s, b->ev_render, 0));     // behind the render (and the text passes) that drew the images
-	hm_rebind(&b->clear_map_hm, hm);
 	ClearMapRun r;
 	clear_map_params(hm, ropt, opt, &r);
-	HIPCHK(hipMemsetAsync(b->d_clear_map + first, 0, sizeof(smhv_clearance_map_result) * (size_t)n, s));
-	for (uint32_t done = 0; done < n;) {                           // at most 65,535 frames per launch (the grid's third dimension)
-		const uint32_t k = std::min(n - done, 65535u);
-		ClearMapRun part = r;
-		part.aux = b->d_aux + first + done;
-		part.res = b->d_results + first + done;
-		part.out = b->d_clear_map + first + done;
-		part.img = paint ? b->d_render + (size_t)(first + done) * r.img_stride : nullptr;
+	hipStream_t s = (hipStream_t)stream;
+	return window_pass_batch(b, first, n, hm, ropt, r, paint, "SMHV_CLEAR_PAINT", &b->d_clear_map, "clearance-map slab (%u frames)", &b->clear_map_hm, s,
+	                         "batch_clearance_map", [&](ClearMapRun &part, uint32_t done, uint32_t k) -> int {
 		part.bytes = bytes ? (uint8_t *)d_bytes + (size_t)done * r.bytes_stride : nullptr;
 		HIPCHK(launch_clear_map(part, k, paint, bytes, s));
-		done += k;
-	}
-	if (paint) HIPCHK(hipEventRecord(b->ev_render, s));            // (the slab's next owner waits for the tint too)
-	return SMHV_OK;
+		return SMHV_OK;
+	});
 }
 
 extern "C" SMHV_API int smhv_batch_read_clearance_map(smhv_batch *b, uint32_t first, uint32_t n, smhv_clearance_map_result *out) {
-	if (!b || !out || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_read_clearance_map: bad arguments");
-	if (!b->d_clear_map) return fail(SMHV_E_STATE, "batch_read_clearance_map: this batch has computed no clearance map");
-	return batch_read_rows(b, b->d_clear_map, sizeof(smhv_clearance_map_result), first, n, out);
+	return batch_read_slab(b, b ? b->d_clear_map : nullptr, sizeof(smhv_clearance_map_result), first, n, out, "batch_read_clearance_map",
+	                       "this batch has computed no clearance map");
 }
 
 extern "C" SMHV_API int smhv_batch_clearance_map_ptr(smhv_batch *b, void **d_clearance_map) {
-	if (!b || !d_clearance_map) return fail(SMHV_E_INVALID, "batch_clearance_map_ptr: null argument");
-	if (!b->d_clear_map) return fail(SMHV_E_STATE, "batch_clearance_map_ptr: this batch has computed no clearance map");
-	*d_clearance_map = b->d_clear_map;
-	return SMHV_OK;
+	return batch_slab_ptr(b, b ? b->d_clear_map : nullptr, d_clearance_map, "batch_clearance_map_ptr", "this batch has computed no clearance map");
 }
 
-// The per-call path: the caller's image up, the kernel, the image, the bytes and the summary down (smhv_reach_map's block layout).
+// The per-call path (window_pass_per_call): the caller's image up, the kernel, the image, the bytes and the summary down.
 extern "C" SMHV_API int smhv_clearance_map(smhv_ctx *c, const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_clearance_options *opt,
                                            const uint32_t minimap[4], uint8_t *rgba_inout, uint8_t *bytes, smhv_clearance_map_result *result) {
 	if (!c) return fail(SMHV_E_INVALID, "clearance_map: null context");
@@ -226,28 +186,13 @@ extern "C" SMHV_API int smhv_clearance_map(smhv_ctx *c, const smhv_heightmap *hm
 	HIPCHK(hipSetDevice(c->device));
 	ClearMapRun r;
 	clear_map_params(hm, ropt, opt, &r);
-	r.per_call = 1u;
-	r.has_mm = minimap ? 1u : 0u;
-	if (minimap) memcpy(r.mm, minimap, sizeof r.mm);
 	// [the summary, 256 bytes][the bytes][the image], each part on a 256-byte boundary
-	const size_t b_off = 256u, b_bytes = bytes ? (size_t)r.bytes_stride : 0u, img_off = b_off + ((b_bytes + 255u) & ~(size_t)255u);
-	const size_t img_bytes = rgba_inout ? (size_t)r.img_stride : 0u, total = img_off + img_bytes;
-	std::lock_guard<std::mutex> lk(c->fire_mu);
-	rc = ctx_stage_reserve(c, total);
-	if (rc) return rc;
-	r.out = (smhv_clearance_map_result *)c->d_fire;
-	r.bytes = bytes ? c->d_fire + b_off : nullptr;
-	r.img = rgba_inout ? c->d_fire + img_off : nullptr;
-	HIPCHK(hipMemsetAsync(c->d_fire, 0, sizeof(smhv_clearance_map_result), c->s_main));
-	if (rgba_inout) {
-		memcpy(c->h_fire + img_off, rgba_inout, img_bytes);
-		HIPCHK(hipMemcpyAsync(c->d_fire + img_off, c->h_fire + img_off, img_bytes, hipMemcpyHostToDevice, c->s_main));
-	}
-	HIPCHK(launch_clear_map(r, 1, rgba_inout != nullptr, bytes != nullptr, c->s_main));
-	HIPCHK(hipMemcpyAsync(c->h_fire, c->d_fire, total, hipMemcpyDeviceToHost, c->s_main));
-	HIPCHK(wait_stream(c->s_main));
-	if (rgba_inout) memcpy(rgba_inout, c->h_fire + img_off, img_bytes);
-	if (bytes) memcpy(bytes, c->h_fire + b_off, b_bytes);
-	if (result) memcpy(result, c->h_fire, sizeof *result);
-	return SMHV_OK;
+	StageLayout lay;
+	lay.take(256u);
+	const StagePart plane = lay.part(bytes, (size_t)r.bytes_stride), img = lay.part(rgba_inout, (size_t)r.img_stride);
+	return window_pass_per_call(c, r, minimap, lay.total(), img, {plane, {result, 0, sizeof *result}}, [&](ClearMapRun &run, uint8_t *block, hipStream_t s) -> int {
+		run.bytes = bytes ? block + plane.off : nullptr;
+		HIPCHK(launch_clear_map(run, 1, rgba_inout != nullptr, bytes != nullptr, s));
+		return SMHV_OK;
+	});
 }

@@ -66,32 +66,19 @@ static const smhv_debug_options *probe_options(smhv_debug_options *d, const smhv
 // waits for the previous call's kernels, which read the device copy), and the launch arguments but for the frames' own pointers.
 static int debug_prepare(smhv_batch *b, const smhv_render_options *ropt, const smhv_debug_options *d, bool draw, hipStream_t s, DebugRun *r) {
 	const size_t frames = (size_t)b->max_frames;
-	if (!b->d_probes) {
-		hipError_t e = hipMalloc((void **)&b->d_probes, sizeof(smhv_probe) * SMHV_MAX_PROBES * frames);
-		if (e == hipSuccess) e = hipMalloc((void **)&b->d_dbg_stage, SMH_DBG_STAGE_BYTES);
-		if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_dbg_stage, SMH_DBG_STAGE_BYTES, hipHostMallocDefault);
-		if (e == hipSuccess) e = hipMemset(b->d_probes, 0, sizeof(smhv_probe) * SMHV_MAX_PROBES * frames);
-		if (e == hipSuccess) e = hipEventCreateWithFlags(&b->ev_dbg, hipEventDisableTiming);
-		if (e != hipSuccess) {
-			if (b->d_probes) (void)hipFree(b->d_probes);
-			if (b->d_dbg_stage) (void)hipFree(b->d_dbg_stage);
-			if (b->h_dbg_stage) (void)hipHostFree(b->h_dbg_stage);
-			if (b->ev_dbg) (void)hipEventDestroy(b->ev_dbg);
-			b->d_probes = nullptr; b->d_dbg_stage = nullptr; b->h_dbg_stage = nullptr; b->ev_dbg = nullptr;
-			return fail(SMHV_E_HIP, "probe slab (%u frames): %s", b->max_frames, hipGetErrorString(e));
-		}
+	if (!b->d_probes) {                                            // the event first: a failure of the slabs takes it back with them
+		hipError_t e = hipEventCreateWithFlags(&b->ev_dbg, hipEventDisableTiming);
+		if (e != hipSuccess) { b->ev_dbg = nullptr; return fail(SMHV_E_HIP, "probe slab (%u frames): %s", b->max_frames, hipGetErrorString(e)); }
+		int rc = first_use_slabs(b, "probe slab (%u frames)", {{(void **)&b->d_probes, sizeof(smhv_probe) * SMHV_MAX_PROBES * frames, 0},
+		                                                       {(void **)&b->d_dbg_stage, SMH_DBG_STAGE_BYTES, SLAB_NO_FILL},
+		                                                       {(void **)&b->h_dbg_stage, SMH_DBG_STAGE_BYTES, SLAB_PINNED_HOST}});
+		if (rc) { (void)hipEventDestroy(b->ev_dbg); b->ev_dbg = nullptr; return rc; }
 	} else
 		HIPCHK(hipStreamWaitEvent(s, b->ev_dbg, 0));
-	if (draw && !b->d_dbg_items) {
-		hipError_t e = hipMalloc((void **)&b->d_dbg_items, sizeof(DebugItem) * SMH_DBG_ITEMS * frames);
-		if (e == hipSuccess) e = hipMalloc((void **)&b->d_dbg_pool, (size_t)SMHV_MAX_PROBES * SMH_DBG_TEXT * frames);
-		if (e == hipSuccess) e = hipMemset(b->d_dbg_items, 0, sizeof(DebugItem) * SMH_DBG_ITEMS * frames);
-		if (e != hipSuccess) {
-			if (b->d_dbg_items) (void)hipFree(b->d_dbg_items);
-			if (b->d_dbg_pool) (void)hipFree(b->d_dbg_pool);
-			b->d_dbg_items = nullptr; b->d_dbg_pool = nullptr;
-			return fail(SMHV_E_HIP, "debug item lists (%u frames): %s", b->max_frames, hipGetErrorString(e));
-		}
+	if (draw) {
+		int rc = first_use_slabs(b, "debug item lists (%u frames)", {{(void **)&b->d_dbg_items, sizeof(DebugItem) * SMH_DBG_ITEMS * frames, 0},
+		                                                             {(void **)&b->d_dbg_pool, (size_t)SMHV_MAX_PROBES * SMH_DBG_TEXT * frames, SLAB_NO_FILL}});
+		if (rc) return rc;
 	}
 	const size_t run_bytes = sizeof(smhv_text_run) * (size_t)d->n_runs, point_bytes = sizeof(smhv_probe_point) * (size_t)d->n_probes;
 	const size_t point_off = sizeof(smhv_text_run) * SMHV_TEXT_MAX_RUNS;
@@ -152,16 +139,11 @@ extern "C" SMHV_API int smhv_batch_probe(smhv_batch *b, uint32_t first, uint32_t
 }
 
 extern "C" SMHV_API int smhv_batch_read_probes(smhv_batch *b, uint32_t first, uint32_t n, smhv_probe *out) {
-	if (!b || !out || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_read_probes: bad arguments");
-	if (!b->probed) return fail(SMHV_E_STATE, "batch_read_probes: this batch has not probed");
-	return batch_read_rows(b, b->d_probes, sizeof(smhv_probe) * SMHV_MAX_PROBES, first, n, out);
+	return batch_read_slab(b, b && b->probed ? b->d_probes : nullptr, sizeof(smhv_probe) * SMHV_MAX_PROBES, first, n, out, "batch_read_probes", "this batch has not probed");
 }
 
 extern "C" SMHV_API int smhv_batch_probes_ptr(smhv_batch *b, void **d_probes) {
-	if (!b || !d_probes) return fail(SMHV_E_INVALID, "batch_probes_ptr: null argument");
-	if (!b->probed) return fail(SMHV_E_STATE, "batch_probes_ptr: this batch has not probed");
-	*d_probes = b->d_probes;
-	return SMHV_OK;
+	return batch_slab_ptr(b, b && b->probed ? b->d_probes : nullptr, d_probes, "batch_probes_ptr", "this batch has not probed");
 }
 
 extern "C" SMHV_API int smhv_batch_render_debug(smhv_batch *b, uint32_t first, uint32_t n, const smhv_render_options *ropt, const smhv_debug_options *dopt,

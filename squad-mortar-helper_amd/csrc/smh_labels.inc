@@ -27,23 +27,12 @@ static int check_label_options(const smhv_label_options *lo, const char *what) {
 // The batch's label buffers (first call), the extras through pinned staging onto `s` (waits, host, for the previous call's copy to
 // have read the staging), and the launch arguments but for the frames' own pointers.
 static int labels_prepare(smhv_batch *b, const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_label_options *lo, hipStream_t s, LabelRun *r) {
-	if (!b->d_labels) {
-		const size_t frames = (size_t)b->max_frames;
-		hipError_t e = hipMalloc((void **)&b->d_labels, sizeof(smhv_label_result) * frames);
-		if (e == hipSuccess) e = hipMalloc((void **)&b->d_label_cull, sizeof(LabelCull) * SMH_LBL_SLOTS * frames);
-		if (e == hipSuccess) e = hipMalloc((void **)&b->d_label_extra, sizeof(smhv_label_line) * SMHV_LABEL_MAX_EXTRA);
-		if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_label_extra, sizeof(smhv_label_line) * SMHV_LABEL_MAX_EXTRA, hipHostMallocDefault);
-		if (e == hipSuccess) e = hipMemset(b->d_labels, 0, sizeof(smhv_label_result) * frames);
-		if (e == hipSuccess) e = hipMemset(b->d_label_cull, 0, sizeof(LabelCull) * SMH_LBL_SLOTS * frames);
-		if (e != hipSuccess) {
-			if (b->d_labels) (void)hipFree(b->d_labels);
-			if (b->d_label_cull) (void)hipFree(b->d_label_cull);
-			if (b->d_label_extra) (void)hipFree(b->d_label_extra);
-			if (b->h_label_extra) (void)hipHostFree(b->h_label_extra);
-			b->d_labels = nullptr; b->d_label_cull = nullptr; b->d_label_extra = nullptr; b->h_label_extra = nullptr;
-			return fail(SMHV_E_HIP, "label slab (%u frames): %s", b->max_frames, hipGetErrorString(e));
-		}
-	}
+	const size_t frames = (size_t)b->max_frames, extra_bytes = sizeof(smhv_label_line) * SMHV_LABEL_MAX_EXTRA;
+	int rc = first_use_slabs(b, "label slab (%u frames)", {{(void **)&b->d_labels, sizeof(smhv_label_result) * frames, 0},
+	                                                       {(void **)&b->d_label_cull, sizeof(LabelCull) * SMH_LBL_SLOTS * frames, 0},
+	                                                       {(void **)&b->d_label_extra, extra_bytes, SLAB_NO_FILL},
+	                                                       {(void **)&b->h_label_extra, extra_bytes, SLAB_PINNED_HOST}});
+	if (rc) return rc;
 	if (lo->n_extra) {
 		if (!b->ev_label_extra) HIPCHK(hipEventCreateWithFlags(&b->ev_label_extra, hipEventDisableTiming));
 		else HIPCHK(wait_event(b->ev_label_extra));
@@ -98,16 +87,11 @@ extern "C" SMHV_API int smhv_batch_render_labels(smhv_batch *b, uint32_t first, 
 }
 
 extern "C" SMHV_API int smhv_batch_read_labels(smhv_batch *b, uint32_t first, uint32_t n, smhv_label_result *out) {
-	if (!b || !out || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_read_labels: bad arguments");
-	if (!b->d_labels) return fail(SMHV_E_STATE, "batch_read_labels: this batch has drawn no labels");
-	return batch_read_rows(b, b->d_labels, sizeof(smhv_label_result), first, n, out);
+	return batch_read_slab(b, b ? b->d_labels : nullptr, sizeof(smhv_label_result), first, n, out, "batch_read_labels", "this batch has drawn no labels");
 }
 
 extern "C" SMHV_API int smhv_batch_labels_ptr(smhv_batch *b, void **d_labels) {
-	if (!b || !d_labels) return fail(SMHV_E_INVALID, "batch_labels_ptr: null argument");
-	if (!b->d_labels) return fail(SMHV_E_STATE, "batch_labels_ptr: this batch has drawn no labels");
-	*d_labels = b->d_labels;
-	return SMHV_OK;
+	return batch_slab_ptr(b, b ? b->d_labels : nullptr, d_labels, "batch_labels_ptr", "this batch has drawn no labels");
 }
 
 // the per-call path: render_map_per_call (smh_render.inc) with the labels over the image

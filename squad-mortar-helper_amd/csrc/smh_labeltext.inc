@@ -84,19 +84,9 @@ extern "C" SMHV_API void smhv_glyph_atlas_destroy(smhv_glyph_atlas *a) {
 
 // the family's slabs, by the first call
 static int label_text_slabs(smhv_batch *b) {
-	if (b->d_lt) return SMHV_OK;
 	const size_t frames = b->max_frames;
-	hipError_t e = hipMalloc((void **)&b->d_lt, sizeof(smhv_label_text_frame) * frames);
-	if (e == hipSuccess) e = hipMalloc((void **)&b->d_lt_anchors, sizeof(smhv_anchors) * frames);
-	if (e == hipSuccess) e = hipMemset(b->d_lt, 0, sizeof(smhv_label_text_frame) * frames);
-	if (e == hipSuccess) e = hipMemset(b->d_lt_anchors, 0, sizeof(smhv_anchors) * frames);
-	if (e != hipSuccess) {
-		if (b->d_lt) (void)hipFree(b->d_lt);
-		if (b->d_lt_anchors) (void)hipFree(b->d_lt_anchors);
-		b->d_lt = nullptr; b->d_lt_anchors = nullptr;
-		return fail(SMHV_E_HIP, "label text slabs (%u frames): %s", b->max_frames, hipGetErrorString(e));
-	}
-	return SMHV_OK;
+	return first_use_slabs(b, "label text slabs (%u frames)", {{(void **)&b->d_lt, sizeof(smhv_label_text_frame) * frames, 0},
+	                                                           {(void **)&b->d_lt_anchors, sizeof(smhv_anchors) * frames, 0}});
 }
 
 static int label_text_enqueue(smhv_batch *b, const smhv_glyph_atlas *a, uint32_t n, hipStream_t s) {
@@ -125,9 +115,7 @@ extern "C" SMHV_API int smhv_batch_label_text(smhv_batch *b, const smhv_glyph_at
 }
 
 extern "C" SMHV_API int smhv_batch_read_label_text(smhv_batch *b, uint32_t first, uint32_t n, smhv_label_text_frame *out) {
-	if (!b || !out || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_read_label_text: bad arguments");
-	if (!b->d_lt) return fail(SMHV_E_STATE, "batch_read_label_text: this batch has read no label text");
-	return batch_read_rows(b, b->d_lt, sizeof(smhv_label_text_frame), first, n, out);
+	return batch_read_slab(b, b ? b->d_lt : nullptr, sizeof(smhv_label_text_frame), first, n, out, "batch_read_label_text", "this batch has read no label text");
 }
 
 extern "C" SMHV_API int smhv_batch_label_text_ptr(smhv_batch *b, void **d_text, void **d_anchors) {

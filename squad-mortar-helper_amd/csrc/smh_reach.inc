@@ -65,57 +65,26 @@ extern "C" SMHV_API int smhv_batch_reach(smhv_batch *b, uint32_t first, uint32_t
 	if (rc) return rc;
 	const bool paint = (opt->flags & SMHV_REACH_PAINT) != 0u, classes = (opt->flags & SMHV_REACH_CLASSES) != 0u;
 	if (classes && !d_classes) return fail(SMHV_E_INVALID, "batch_reach: SMHV_REACH_CLASSES and a null d_classes");
-	if (paint) {
-		if (!b->d_render) return fail(SMHV_E_STATE, "batch_reach: SMHV_REACH_PAINT and this batch has not rendered");
-		rc = check_window_is_last_render(b, ropt, "batch_reach");
-		if (rc) return rc;
-	}
-	HIPCHK(hipSetDevice(b->ctx->device));
-	if (!b->d_reach) {
-		hipError_t e = hipMalloc((void **)&b->d_reach, sizeof(smhv_reach_result) * (size_t)b->max_frames);
-		if (e == hipSuccess) e = hipMemset(b->d_reach, 0, sizeof(smhv_reach_result) * (size_t)b->max_frames);
-		if (e != hipSuccess) {
-			if (b->d_reach) (void)hipFree(b->d_reach);
-			b->d_reach = nullptr;
-			return fail(SMHV_E_HIP, "reach slab (%u frames): %s", b->max_frames, hipGetErrorString(e));
-		}
-	}
-	hipStream_t s = (hipStream_t)stream;
-	if (paint) HIPCHK(hipStreamWaitEvent(s, b->ev_render, 0));     // behind the render (and the text passes) that drew the images
-	hm_rebind(&b->reach_hm, hm);                                   // the batch's reference of the heightmap its enqueued call reads
 	ReachRun r;
 	reach_run_params(hm, ropt, opt, &r);
-	HIPCHK(hipMemsetAsync(b->d_reach + first, 0, sizeof(smhv_reach_result) * (size_t)n, s));
-	for (uint32_t done = 0; done < n;) {                           // at most 65,535 frames per launch (the grid's third dimension)
-		const uint32_t k = std::min(n - done, 65535u);
-		ReachRun part = r;
-		part.aux = b->d_aux + first + done;
-		part.res = b->d_results + first + done;
-		part.out = b->d_reach + first + done;
-		part.img = paint ? b->d_render + (size_t)(first + done) * r.img_stride : nullptr;
+	hipStream_t s = (hipStream_t)stream;
+	return window_pass_batch(b, first, n, hm, ropt, r, paint, "SMHV_REACH_PAINT", &b->d_reach, "reach slab (%u frames)", &b->reach_hm, s, "batch_reach",
+	                         [&](ReachRun &part, uint32_t done, uint32_t k) -> int {
 		part.cls = classes ? (uint8_t *)d_classes + (size_t)done * r.cls_stride : nullptr;
 		HIPCHK(launch_reach(part, k, paint, classes, s));
-		done += k;
-	}
-	if (paint) HIPCHK(hipEventRecord(b->ev_render, s));            // (the slab's next owner waits for the tint too)
-	return SMHV_OK;
+		return SMHV_OK;
+	});
 }
 
 extern "C" SMHV_API int smhv_batch_read_reach(smhv_batch *b, uint32_t first, uint32_t n, smhv_reach_result *out) {
-	if (!b || !out || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_read_reach: bad arguments");
-	if (!b->d_reach) return fail(SMHV_E_STATE, "batch_read_reach: this batch has computed no reach map");
-	return batch_read_rows(b, b->d_reach, sizeof(smhv_reach_result), first, n, out);
+	return batch_read_slab(b, b ? b->d_reach : nullptr, sizeof(smhv_reach_result), first, n, out, "batch_read_reach", "this batch has computed no reach map");
 }
 
 extern "C" SMHV_API int smhv_batch_reach_ptr(smhv_batch *b, void **d_reach) {
-	if (!b || !d_reach) return fail(SMHV_E_INVALID, "batch_reach_ptr: null argument");
-	if (!b->d_reach) return fail(SMHV_E_STATE, "batch_reach_ptr: this batch has computed no reach map");
-	*d_reach = b->d_reach;
-	return SMHV_OK;
+	return batch_slab_ptr(b, b ? b->d_reach : nullptr, d_reach, "batch_reach_ptr", "this batch has computed no reach map");
 }
 
-// The per-call path: the caller's image up, the kernel, the image, the classes and the summary down, through the context's pinned
-// block (smhv_firing_solutions' buffers, grown on demand; fire_mu from sizing them to the last copy).
+// The per-call path (window_pass_per_call): the caller's image up, the kernel, the image, the classes and the summary down.
 extern "C" SMHV_API int smhv_reach_map(smhv_ctx *c, const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_reach_options *opt, const double *mpx,
                                        const uint32_t minimap[4], uint8_t *rgba_inout, uint8_t *classes, smhv_reach_result *result) {
 	if (!c) return fail(SMHV_E_INVALID, "reach_map: null context");
@@ -131,29 +100,14 @@ extern "C" SMHV_API int smhv_reach_map(smhv_ctx *c, const smhv_heightmap *hm, co
 	HIPCHK(hipSetDevice(c->device));
 	ReachRun r;
 	reach_run_params(hm, ropt, opt, &r);
-	r.per_call = 1u;
 	r.has_mpx = mpx ? 1u : 0u; r.mpx = mpx ? *mpx : 0.0;
-	r.has_mm = minimap ? 1u : 0u;
-	if (minimap) memcpy(r.mm, minimap, sizeof r.mm);
 	// [the summary, 256 bytes][the classes][the image], each part on a 256-byte boundary
-	const size_t cls_off = 256u, cls_bytes = classes ? (size_t)r.cls_stride : 0u, img_off = cls_off + ((cls_bytes + 255u) & ~(size_t)255u);
-	const size_t img_bytes = rgba_inout ? (size_t)r.img_stride : 0u, bytes = img_off + img_bytes;
-	std::lock_guard<std::mutex> lk(c->fire_mu);
-	rc = ctx_stage_reserve(c, bytes);
-	if (rc) return rc;
-	r.out = (smhv_reach_result *)c->d_fire;
-	r.cls = classes ? c->d_fire + cls_off : nullptr;
-	r.img = rgba_inout ? c->d_fire + img_off : nullptr;
-	HIPCHK(hipMemsetAsync(c->d_fire, 0, sizeof(smhv_reach_result), c->s_main));
-	if (rgba_inout) {
-		memcpy(c->h_fire + img_off, rgba_inout, img_bytes);
-		HIPCHK(hipMemcpyAsync(c->d_fire + img_off, c->h_fire + img_off, img_bytes, hipMemcpyHostToDevice, c->s_main));
-	}
-	HIPCHK(launch_reach(r, 1, rgba_inout != nullptr, classes != nullptr, c->s_main));
-	HIPCHK(hipMemcpyAsync(c->h_fire, c->d_fire, bytes, hipMemcpyDeviceToHost, c->s_main));
-	HIPCHK(wait_stream(c->s_main));
-	if (rgba_inout) memcpy(rgba_inout, c->h_fire + img_off, img_bytes);
-	if (classes) memcpy(classes, c->h_fire + cls_off, cls_bytes);
-	if (result) memcpy(result, c->h_fire, sizeof *result);
-	return SMHV_OK;
+	StageLayout lay;
+	lay.take(256u);
+	const StagePart cls = lay.part(classes, (size_t)r.cls_stride), img = lay.part(rgba_inout, (size_t)r.img_stride);
+	return window_pass_per_call(c, r, minimap, lay.total(), img, {cls, {result, 0, sizeof *result}}, [&](ReachRun &run, uint8_t *block, hipStream_t s) -> int {
+		run.cls = classes ? block + cls.off : nullptr;
+		HIPCHK(launch_reach(run, 1, rgba_inout != nullptr, classes != nullptr, s));
+		return SMHV_OK;
+	});
 }

@@ -77,59 +77,28 @@ extern "C" SMHV_API int smhv_batch_relief(smhv_batch *b, uint32_t first, uint32_
 		if (!planes || !planes->heights) return fail(SMHV_E_INVALID, "batch_relief: SMHV_RELIEF_HEIGHTS and a null heights plane");
 		d_heights = (float *)planes->heights;
 	}
-	if (paint) {
-		if (!b->d_render) return fail(SMHV_E_STATE, "batch_relief: SMHV_RELIEF_PAINT and this batch has not rendered");
-		rc = check_window_is_last_render(b, ropt, "batch_relief");
-		if (rc) return rc;
-	}
-	HIPCHK(hipSetDevice(b->ctx->device));
-	if (!b->d_relief) {
-		hipError_t e = hipMalloc((void **)&b->d_relief, sizeof(smhv_relief_result) * (size_t)b->max_frames);
-		if (e == hipSuccess) e = hipMemset(b->d_relief, 0, sizeof(smhv_relief_result) * (size_t)b->max_frames);
-		if (e != hipSuccess) {
-			if (b->d_relief) (void)hipFree(b->d_relief);
-			b->d_relief = nullptr;
-			return fail(SMHV_E_HIP, "relief slab (%u frames): %s", b->max_frames, hipGetErrorString(e));
-		}
-	}
-	hipStream_t s = (hipStream_t)stream;
-	if (paint) HIPCHK(hipStreamWaitEvent(s, b->ev_render, 0));     // behind the render (and the text passes) that drew the images
-	hm_rebind(&b->relief_hm, hm);                                  // the batch's reference of the heightmap its enqueued call reads
 	ReliefRun r;
 	relief_run_params(hm, ropt, opt, &r);
-	HIPCHK(hipMemsetAsync(b->d_relief + first, 0, sizeof(smhv_relief_result) * (size_t)n, s));
-	for (uint32_t done = 0; done < n;) {                           // at most 65,535 frames per launch (the grid's third dimension)
-		const uint32_t k = std::min(n - done, 65535u);
-		ReliefRun part = r;
-		part.aux = b->d_aux + first + done;
-		part.res = b->d_results + first + done;
-		part.out = b->d_relief + first + done;
-		part.img = paint ? b->d_render + (size_t)(first + done) * r.img_stride : nullptr;
+	hipStream_t s = (hipStream_t)stream;
+	return window_pass_batch(b, first, n, hm, ropt, r, paint, "SMHV_RELIEF_PAINT", &b->d_relief, "relief slab (%u frames)", &b->relief_hm, s, "batch_relief",
+	                         [&](ReliefRun &part, uint32_t done, uint32_t k) -> int {
 		part.bytes = d_bytes ? d_bytes + (size_t)done * r.plane_stride : nullptr;
 		part.shades = d_shades ? d_shades + (size_t)done * r.plane_stride : nullptr;
 		part.heights = d_heights ? d_heights + (size_t)done * r.plane_stride : nullptr;
 		HIPCHK(launch_relief(part, k, paint, s));
-		done += k;
-	}
-	if (paint) HIPCHK(hipEventRecord(b->ev_render, s));            // (the slab's next owner waits for the tint too)
-	return SMHV_OK;
+		return SMHV_OK;
+	});
 }
 
 extern "C" SMHV_API int smhv_batch_read_relief(smhv_batch *b, uint32_t first, uint32_t n, smhv_relief_result *out) {
-	if (!b || !out || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_read_relief: bad arguments");
-	if (!b->d_relief) return fail(SMHV_E_STATE, "batch_read_relief: this batch has computed no relief");
-	return batch_read_rows(b, b->d_relief, sizeof(smhv_relief_result), first, n, out);
+	return batch_read_slab(b, b ? b->d_relief : nullptr, sizeof(smhv_relief_result), first, n, out, "batch_read_relief", "this batch has computed no relief");
 }
 
 extern "C" SMHV_API int smhv_batch_relief_ptr(smhv_batch *b, void **d_relief) {
-	if (!b || !d_relief) return fail(SMHV_E_INVALID, "batch_relief_ptr: null argument");
-	if (!b->d_relief) return fail(SMHV_E_STATE, "batch_relief_ptr: this batch has computed no relief");
-	*d_relief = b->d_relief;
-	return SMHV_OK;
+	return batch_slab_ptr(b, b ? b->d_relief : nullptr, d_relief, "batch_relief_ptr", "this batch has computed no relief");
 }
 
-// The per-call path: the caller's image up, the kernels, the image, the planes and the summary down, through the context's pinned
-// block (smhv_firing_solutions' buffers, grown on demand; fire_mu from sizing them to the last copy).
+// The per-call path (window_pass_per_call): the caller's image up, the kernels, the image, the planes and the summary down.
 extern "C" SMHV_API int smhv_relief_map(smhv_ctx *c, const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_relief_options *opt,
                                         const uint32_t minimap[4], uint8_t *rgba_inout, uint8_t *bytes, uint8_t *shades, float *heights,
                                         smhv_relief_result *result) {
@@ -146,35 +115,16 @@ extern "C" SMHV_API int smhv_relief_map(smhv_ctx *c, const smhv_heightmap *hm, c
 	HIPCHK(hipSetDevice(c->device));
 	ReliefRun r;
 	relief_run_params(hm, ropt, opt, &r);
-	r.per_call = 1u;
-	r.has_mm = minimap ? 1u : 0u;
-	if (minimap) memcpy(r.mm, minimap, sizeof r.mm);
 	// [the summary, 256 bytes][the flag bytes][the shades][the heights][the image], each part on a 256-byte boundary
-	const auto pad = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
+	StageLayout lay;
+	lay.take(256u);
 	const size_t px = (size_t)r.plane_stride;
-	const size_t bytes_off = 256u, bytes_len = bytes ? px : 0u, shades_off = bytes_off + pad(bytes_len), shades_len = shades ? px : 0u;
-	const size_t heights_off = shades_off + pad(shades_len), heights_len = heights ? px * sizeof(float) : 0u;
-	const size_t img_off = heights_off + pad(heights_len), img_len = rgba_inout ? (size_t)r.img_stride : 0u, total = img_off + img_len;
-	std::lock_guard<std::mutex> lk(c->fire_mu);
-	rc = ctx_stage_reserve(c, total);
-	if (rc) return rc;
-	r.out = (smhv_relief_result *)c->d_fire;
-	r.bytes = bytes ? c->d_fire + bytes_off : nullptr;
-	r.shades = shades ? c->d_fire + shades_off : nullptr;
-	r.heights = heights ? (float *)(c->d_fire + heights_off) : nullptr;
-	r.img = rgba_inout ? c->d_fire + img_off : nullptr;
-	HIPCHK(hipMemsetAsync(c->d_fire, 0, sizeof(smhv_relief_result), c->s_main));
-	if (rgba_inout) {
-		memcpy(c->h_fire + img_off, rgba_inout, img_len);
-		HIPCHK(hipMemcpyAsync(c->d_fire + img_off, c->h_fire + img_off, img_len, hipMemcpyHostToDevice, c->s_main));
-	}
-	HIPCHK(launch_relief(r, 1, rgba_inout != nullptr, c->s_main));
-	HIPCHK(hipMemcpyAsync(c->h_fire, c->d_fire, total, hipMemcpyDeviceToHost, c->s_main));
-	HIPCHK(wait_stream(c->s_main));
-	if (rgba_inout) memcpy(rgba_inout, c->h_fire + img_off, img_len);
-	if (bytes) memcpy(bytes, c->h_fire + bytes_off, bytes_len);
-	if (shades) memcpy(shades, c->h_fire + shades_off, shades_len);
-	if (heights) memcpy(heights, c->h_fire + heights_off, heights_len);
-	if (result) memcpy(result, c->h_fire, sizeof *result);
-	return SMHV_OK;
+	const StagePart pb = lay.part(bytes, px), ps = lay.part(shades, px), ph = lay.part(heights, px * sizeof(float)), img = lay.part(rgba_inout, (size_t)r.img_stride);
+	return window_pass_per_call(c, r, minimap, lay.total(), img, {pb, ps, ph, {result, 0, sizeof *result}}, [&](ReliefRun &run, uint8_t *block, hipStream_t s) -> int {
+		run.bytes = bytes ? block + pb.off : nullptr;
+		run.shades = shades ? block + ps.off : nullptr;
+		run.heights = heights ? (float *)(block + ph.off) : nullptr;
+		HIPCHK(launch_relief(run, 1, rgba_inout != nullptr, s));
+		return SMHV_OK;
+	});
 }

@@ -55,13 +55,13 @@ static int render_prepare(smhv_batch *b, uint32_t first, uint32_t n, const smhv_
 	const bool use_hm = (opt->flags & SMHV_RENDER_HEIGHTMAP) != 0u;
 	const uint32_t *lut = nullptr;
 	if (use_hm) {
-		if (hm->ctx->device != b->ctx->device) return fail(SMHV_E_INVALID, "render: the heightmap lives on device %d, the batch on %d", hm->ctx->device, b->ctx->device);
-		int rc = hm_lut(hm, &lut);
+		int rc = check_hm_device(hm, b->ctx->device, "render", "batch");
+		if (rc) return rc;
+		rc = hm_lut(hm, &lut);
 		if (rc) return rc;
 	}
 	const uint64_t stride = (uint64_t)opt->out_w * opt->out_h * 4u;
 	const uint64_t need = stride * (uint64_t)b->max_frames;       // the whole batch: rendering it in parts keeps the earlier parts
-	(void)first; (void)n;
 	if (!b->ev_render) HIPCHK(hipEventCreateWithFlags(&b->ev_render, hipEventDisableTiming));
 	if (b->render_cap < need) {
 		if (b->d_render) {
@@ -230,15 +230,15 @@ static int batch_render(smhv_batch *b, uint32_t first, uint32_t n, const smhv_he
 		if (rc) return rc;
 	}
 	hm_rebind(&b->render_hm, use_hm ? hm : nullptr);           // the batch's reference of the heightmap its enqueued render reads
-	for (uint32_t done = 0; done < n;) {                       // at most 65,535 frames per launch (the grid's third dimension)
-		const uint32_t k = std::min(n - done, 65535u);
+	rc = for_each_launch(n, [&](uint32_t done, uint32_t k) -> int {
 		RenderRun part = r;
 		part.ui += (size_t)done * g.ui_stride; part.out += (size_t)done * r.out_stride; part.aux += done; part.res += done;
 		RenderLayersRun yp = y;
 		if (yp.src) yp.src += (size_t)done * y.src_stride;
 		HIPCHK(with_layers ? launch_render_map_layers(g, part, yp, k, s) : launch_render_map(g, part, k, s));
-		done += k;
-	}
+		return SMHV_OK;
+	});
+	if (rc) return rc;
 	HIPCHK(hipEventRecord(b->ev_render, s));
 	return SMHV_OK;
 }

@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <initializer_list>
 #include <sched.h>
 #include <pthread.h>
 #include <cctype>
@@ -891,6 +892,25 @@ static int ctx_stage_reserve(smhv_ctx *c, size_t bytes) {
 	return SMHV_OK;
 }
 
+// The parts of the staging block of one per-call entry point, each on a 256-byte boundary, in the order they are taken.
+struct StagePart {
+	void *host;                                                // the caller's buffer the part comes from or goes to (null: not asked for)
+	size_t off, len;
+};
+struct StageLayout {
+	size_t end = 0;
+	size_t take(size_t bytes) {
+		const size_t off = (end + 255u) & ~(size_t)255u;
+		end = off + bytes;
+		return off;
+	}
+	StagePart part(void *host, size_t bytes) {                 // a part that is there when the caller asked for it
+		const size_t len = host ? bytes : 0u;
+		return {host, take(len), len};
+	}
+	size_t total() const { return end; }
+};
+
 // rows [first, first + n) of a batch's result slab to the host, after everything enqueued on the device has finished
 static int batch_read_rows(smhv_batch *b, const void *src, size_t row_bytes, uint32_t first, uint32_t n, void *out) {
 	HIPCHK(hipSetDevice(b->ctx->device));
@@ -899,20 +919,136 @@ static int batch_read_rows(smhv_batch *b, const void *src, size_t row_bytes, uin
 	return SMHV_OK;
 }
 
+// smhv_batch_read_X and smhv_batch_X_ptr of a family with one slab: `slab` is null while the batch (or `b` itself) has none, `what`
+// the entry point's name, `none_msg` its sentence for "no call has filled this slab yet"
+static int batch_read_slab(smhv_batch *b, const void *slab, size_t row_bytes, uint32_t first, uint32_t n, void *out, const char *what, const char *none_msg) {
+	if (!b || !out || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "%s: bad arguments", what);
+	if (!slab) return fail(SMHV_E_STATE, "%s: %s", what, none_msg);
+	return batch_read_rows(b, slab, row_bytes, first, n, out);
+}
+static int batch_slab_ptr(smhv_batch *b, void *slab, void **out, const char *what, const char *none_msg) {
+	if (!b || !out) return fail(SMHV_E_INVALID, "%s: null argument", what);
+	if (!slab) return fail(SMHV_E_STATE, "%s: %s", what, none_msg);
+	*out = slab;
+	return SMHV_OK;
+}
+
+// A family's device buffers, made by its first call, all or nothing: every part is allocated and, unless its fill is SLAB_NO_FILL,
+// set to that byte; on a failure every slot of the list is freed and null again.  A part whose first slot is set already means the
+// family has them.  `what`: the message's noun with one %u for the batch's frames ("reach slab (%u frames)").
+enum : int { SLAB_NO_FILL = -1, SLAB_PINNED_HOST = -2 };          // (pinned host memory is not filled either)
+struct SlabPart {
+	void **slot;
+	size_t bytes;
+	int fill;
+};
+static int first_use_slabs(const smhv_batch *b, const char *what, std::initializer_list<SlabPart> parts) {
+	if (*parts.begin()->slot) return SMHV_OK;
+	hipError_t e = hipSuccess;
+	for (const SlabPart &p : parts) {
+		if (e == hipSuccess) e = p.fill == SLAB_PINNED_HOST ? hipHostMalloc(p.slot, p.bytes, hipHostMallocDefault) : hipMalloc(p.slot, p.bytes);
+		if (e == hipSuccess && p.fill >= 0) e = hipMemset(*p.slot, p.fill, p.bytes);
+	}
+	if (e == hipSuccess) return SMHV_OK;
+	for (const SlabPart &p : parts) {
+		if (*p.slot) (void)(p.fill == SLAB_PINNED_HOST ? hipHostFree(*p.slot) : hipFree(*p.slot));
+		*p.slot = nullptr;
+	}
+	char noun[96];
+	snprintf(noun, sizeof noun, what, b->max_frames);
+	return fail(SMHV_E_HIP, "%s: %s", noun, hipGetErrorString(e));
+}
+
+// fn(done, k) for the frames of a call in launches of at most 65,535 (a grid's second and third dimension hold no more)
+template <class F> static int for_each_launch(uint32_t n, F &&fn) {
+	for (uint32_t done = 0; done < n;) {
+		const uint32_t k = std::min(n - done, 65535u);
+		const int rc = fn(done, k);
+		if (rc) return rc;
+		done += k;
+	}
+	return SMHV_OK;
+}
+
+// ---- the window passes (the reach map, the clearance map, the relief): one batch path and one per-call path.  Their Run structs
+// agree on fr, out_w, out_h, img_stride, aux, res, out, img, per_call, has_mm, mm; the planes are the family's own, set by its
+// `launch`.  A new window pass is its options' defaults and check, its run params, and two entry points that call these.
+//
+// What holds for every one of them:
+//  - nothing is enqueued and no state of the batch changes (its heightmap reference, its slabs, ev_render) before every check of
+//    the arguments and of the batch's state has passed;
+//  - hipSetDevice comes before the first allocation;
+//  - with `paint` the call's stream waits for ev_render before the result rows are cleared and the kernel launched, and ev_render is
+//    recorded on that stream after the last launch; without it neither happens;
+//  - hm_rebind takes the batch's reference of the heightmap before the first launch;
+//  - the result rows [first, first + n) are cleared with hipMemsetAsync on the call's stream; the caller's planes are offset by
+//    `done` (they start at the call's first frame), the batch's slabs by first + done;
+//  - per call, fire_mu is held from sizing the block to the last host copy, and the work runs on c->s_main;
+//  - launch_relief enqueues k_relief_finish itself: nothing here adds a second one.
+//
+// The batch path, from "PAINT needs the most recent render" to the record of ev_render.  `r`: the family's run params; `slab`: the
+// batch's result slab, `slab_what` its noun for first_use_slabs; launch(part, done, k) -> int sets the family's planes and launches.
+template <class Run, class Result, class Launch>
+static int window_pass_batch(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_render_options *ropt, const Run &r, bool paint,
+                             const char *paint_flag, Result **slab, const char *slab_what, smhv_heightmap **hm_slot, hipStream_t s, const char *what, Launch launch) {
+	if (paint) {
+		if (!b->d_render) return fail(SMHV_E_STATE, "%s: %s and this batch has not rendered", what, paint_flag);
+		const int rc = check_window_is_last_render(b, ropt, what);
+		if (rc) return rc;
+	}
+	HIPCHK(hipSetDevice(b->ctx->device));
+	int rc = first_use_slabs(b, slab_what, {{(void **)slab, sizeof(Result) * (size_t)b->max_frames, 0}});
+	if (rc) return rc;
+	if (paint) HIPCHK(hipStreamWaitEvent(s, b->ev_render, 0));     // behind the render (and the text passes) that drew the images
+	hm_rebind(hm_slot, hm);                                        // the batch's reference of the heightmap its enqueued call reads
+	HIPCHK(hipMemsetAsync(*slab + first, 0, sizeof(Result) * (size_t)n, s));
+	rc = for_each_launch(n, [&](uint32_t done, uint32_t k) -> int {
+		Run part = r;
+		part.aux = b->d_aux + first + done;
+		part.res = b->d_results + first + done;
+		part.out = *slab + first + done;
+		part.img = paint ? b->d_render + (size_t)(first + done) * r.img_stride : nullptr;
+		return launch(part, done, k);
+	});
+	if (rc) return rc;
+	if (paint) HIPCHK(hipEventRecord(b->ev_render, s));            // (the slab's next owner waits for the tint too)
+	return SMHV_OK;
+}
+
+// The per-call path through the context's pinned block (smhv_firing_solutions' buffers, grown on demand): the summary at offset 0,
+// the caller's image (`img`) up, the kernel, the whole block (`total` bytes) down in one copy, then every part of `outs` and the
+// image to the caller.  launch(run, block, stream) -> int sets the family's planes inside `block` and launches over one frame.
+template <class Run, class Launch>
+static int window_pass_per_call(smhv_ctx *c, Run r, const uint32_t minimap[4], size_t total, const StagePart &img, std::initializer_list<StagePart> outs, Launch launch) {
+	r.per_call = 1u;
+	r.has_mm = minimap ? 1u : 0u;
+	if (minimap) memcpy(r.mm, minimap, sizeof r.mm);
+	std::lock_guard<std::mutex> lk(c->fire_mu);
+	int rc = ctx_stage_reserve(c, total);
+	if (rc) return rc;
+	r.out = (decltype(r.out))c->d_fire;
+	r.img = img.host ? c->d_fire + img.off : nullptr;
+	HIPCHK(hipMemsetAsync(c->d_fire, 0, sizeof *r.out, c->s_main));
+	if (img.host) {
+		memcpy(c->h_fire + img.off, img.host, img.len);
+		HIPCHK(hipMemcpyAsync(c->d_fire + img.off, c->h_fire + img.off, img.len, hipMemcpyHostToDevice, c->s_main));
+	}
+	rc = launch(r, c->d_fire, c->s_main);
+	if (rc) return rc;
+	HIPCHK(hipMemcpyAsync(c->h_fire, c->d_fire, total, hipMemcpyDeviceToHost, c->s_main));
+	HIPCHK(wait_stream(c->s_main));
+	if (img.host) memcpy(img.host, c->h_fire + img.off, img.len);
+	for (const StagePart &p : outs)
+		if (p.host) memcpy(p.host, c->h_fire + p.off, p.len);
+	return SMHV_OK;
+}
+
 // SMHV_STAGE_FIRING: the run's parameter block (the batch's binding as it stands now) from pinned staging into the batch's device block,
 // on the stream of the run's first kernel (sb); the slab is allocated by the first run that asks for it
 static int firing_upload(smhv_batch *b, hipStream_t sb) {
-	if (!b->d_firing) {
-		hipError_t e = hipMalloc((void **)&b->d_firing, sizeof(smhv_firing_result) * (size_t)b->max_frames);
-		if (e == hipSuccess) e = hipMalloc((void **)&b->d_fire_run, sizeof(FiringRun));
-		if (e == hipSuccess) e = hipMemset(b->d_firing, 0, sizeof(smhv_firing_result) * (size_t)b->max_frames);
-		if (e != hipSuccess) {
-			if (b->d_firing) (void)hipFree(b->d_firing);
-			if (b->d_fire_run) (void)hipFree(b->d_fire_run);
-			b->d_firing = nullptr; b->d_fire_run = nullptr;
-			return fail(SMHV_E_HIP, "firing slab: %s", hipGetErrorString(e));
-		}
-	}
+	int rc = first_use_slabs(b, "firing slab", {{(void **)&b->d_firing, sizeof(smhv_firing_result) * (size_t)b->max_frames, 0},
+	                                            {(void **)&b->d_fire_run, sizeof(FiringRun), SLAB_NO_FILL}});
+	if (rc) return rc;
 	smhv_batch::FireStage *st = nullptr;
 	for (auto &a : b->fire_stage)
 		if (hipEventQuery(a.done) == hipSuccess) { st = &a; break; }
@@ -3273,16 +3409,11 @@ extern "C" SMHV_API int smhv_pipeline_set_firing(smhv_pipeline *p, smhv_heightma
 }
 
 extern "C" SMHV_API int smhv_batch_read_firing(smhv_batch *b, uint32_t first, uint32_t n, smhv_firing_result *out) {
-	if (!b || !out || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_read_firing: bad arguments");
-	if (!b->d_firing) return fail(SMHV_E_STATE, "batch_read_firing: no run of this batch had SMHV_STAGE_FIRING");
-	return batch_read_rows(b, b->d_firing, sizeof(smhv_firing_result), first, n, out);
+	return batch_read_slab(b, b ? b->d_firing : nullptr, sizeof(smhv_firing_result), first, n, out, "batch_read_firing", "no run of this batch had SMHV_STAGE_FIRING");
 }
 
 extern "C" SMHV_API int smhv_batch_firing_ptr(smhv_batch *b, void **d_firing) {
-	if (!b || !d_firing) return fail(SMHV_E_INVALID, "batch_firing_ptr: null argument");
-	if (!b->d_firing) return fail(SMHV_E_STATE, "batch_firing_ptr: no run of this batch had SMHV_STAGE_FIRING");
-	*d_firing = b->d_firing;
-	return SMHV_OK;
+	return batch_slab_ptr(b, b ? b->d_firing : nullptr, d_firing, "batch_firing_ptr", "no run of this batch had SMHV_STAGE_FIRING");
 }
 
 extern "C" SMHV_API int smhv_firing_solutions(smhv_ctx *c, const smhv_line *lines, uint32_t n, const double *mpx, const uint32_t minimap[4],
@@ -3299,17 +3430,21 @@ extern "C" SMHV_API int smhv_firing_solutions(smhv_ctx *c, const smhv_line *line
 	FiringRun r;
 	firing_run_params(hm, &o, &r);
 	const uint32_t mm0[4] = {0, 0, 0, 0};
-	const size_t in_bytes = ((sizeof(smhv_line) * (size_t)n + 255u) & ~(size_t)255u), bytes = in_bytes + sizeof(smhv_firing) * (size_t)n;
+	// [the lines][the solutions], each part on a 256-byte boundary
+	StageLayout lay;
+	const size_t in_bytes = sizeof(smhv_line) * (size_t)n, out_bytes = sizeof(smhv_firing) * (size_t)n;
+	lay.take(in_bytes);
+	const size_t out_off = lay.take(out_bytes);
 	std::lock_guard<std::mutex> lk(c->fire_mu);
-	rc = ctx_stage_reserve(c, bytes);
+	rc = ctx_stage_reserve(c, lay.total());
 	if (rc) return rc;
-	memcpy(c->h_fire, lines, sizeof(smhv_line) * (size_t)n);
-	HIPCHK(hipMemcpyAsync(c->d_fire, c->h_fire, sizeof(smhv_line) * (size_t)n, hipMemcpyHostToDevice, c->s_main));
+	memcpy(c->h_fire, lines, in_bytes);
+	HIPCHK(hipMemcpyAsync(c->d_fire, c->h_fire, in_bytes, hipMemcpyHostToDevice, c->s_main));
 	HIPCHK(launch_firing_lines(r, (const smhv_line *)c->d_fire, n, mpx ? 1u : 0u, mpx ? *mpx : 0.0, minimap ? 1u : 0u, minimap ? minimap : mm0,
-	                           (smhv_firing *)(c->d_fire + in_bytes), c->s_main));
-	HIPCHK(hipMemcpyAsync(c->h_fire + in_bytes, c->d_fire + in_bytes, sizeof(smhv_firing) * (size_t)n, hipMemcpyDeviceToHost, c->s_main));
+	                           (smhv_firing *)(c->d_fire + out_off), c->s_main));
+	HIPCHK(hipMemcpyAsync(c->h_fire + out_off, c->d_fire + out_off, out_bytes, hipMemcpyDeviceToHost, c->s_main));
 	HIPCHK(wait_stream(c->s_main));
-	memcpy(out, c->h_fire + in_bytes, sizeof(smhv_firing) * (size_t)n);
+	memcpy(out, c->h_fire + out_off, out_bytes);
 	return SMHV_OK;
 }
 
@@ -3317,10 +3452,7 @@ extern "C" SMHV_API int smhv_firing_solutions(smhv_ctx *c, const smhv_line *line
 // heightmap overlay: public entry points (smh_vision_hip.h; device code in smh_misc.hip, k_hm_overlay)
 // ------------------------------------------------------------------------------------------------
 extern "C" SMHV_API int smhv_batch_overlay_ptr(smhv_batch *b, void **d_overlay) {
-	if (!b || !d_overlay) return fail(SMHV_E_INVALID, "batch_overlay_ptr: null argument");
-	if (!b->d_overlay) return fail(SMHV_E_STATE, "batch_overlay_ptr: no run of this batch had SMHV_STAGE_HEIGHTMAP_OVERLAY");
-	*d_overlay = b->d_overlay;
-	return SMHV_OK;
+	return batch_slab_ptr(b, b ? b->d_overlay : nullptr, d_overlay, "batch_overlay_ptr", "no run of this batch had SMHV_STAGE_HEIGHTMAP_OVERLAY");
 }
 
 // The current frame's ui_map (frame 0 of the single-frame batch's ui slab, written by crop_to_map's pass) and the minimap

@@ -5,21 +5,10 @@
 // with start row 0 from the frames' pixels (the batch's scales plane keeps the rows of its own run's start row, and its readers
 // their image).
 static int scale_labels_slabs(smhv_batch *b) {
-	if (b->d_sl) return SMHV_OK;
 	const size_t frames = b->max_frames;
-	hipError_t e = hipMalloc((void **)&b->d_sl, sizeof(smhv_scale_label_frame) * frames);
-	if (e == hipSuccess) e = hipMalloc((void **)&b->d_sl_crops, (size_t)SMHV_LABEL_FRAME_CROP_BYTES * frames);
-	if (e == hipSuccess) e = hipMalloc((void **)&b->d_sl_s0, (size_t)b->g.ocr_stride * frames);
-	if (e == hipSuccess) e = hipMemset(b->d_sl, 0, sizeof(smhv_scale_label_frame) * frames);
-	if (e == hipSuccess) e = hipMemset(b->d_sl_crops, 255, (size_t)SMHV_LABEL_FRAME_CROP_BYTES * frames);
-	if (e != hipSuccess) {
-		if (b->d_sl) (void)hipFree(b->d_sl);
-		if (b->d_sl_crops) (void)hipFree(b->d_sl_crops);
-		if (b->d_sl_s0) (void)hipFree(b->d_sl_s0);
-		b->d_sl = nullptr; b->d_sl_crops = nullptr; b->d_sl_s0 = nullptr;
-		return fail(SMHV_E_HIP, "scale label slabs (%u frames): %s", b->max_frames, hipGetErrorString(e));
-	}
-	return SMHV_OK;
+	return first_use_slabs(b, "scale label slabs (%u frames)", {{(void **)&b->d_sl, sizeof(smhv_scale_label_frame) * frames, 0},
+	                                                            {(void **)&b->d_sl_crops, (size_t)SMHV_LABEL_FRAME_CROP_BYTES * frames, 255},
+	                                                            {(void **)&b->d_sl_s0, (size_t)b->g.ocr_stride * frames, SLAB_NO_FILL}});
 }
 
 static int check_scale_labels_geom(const Geom &g, const char *what) {
@@ -64,9 +53,7 @@ extern "C" SMHV_API int smhv_batch_scale_labels(smhv_batch *b, const void *d_fra
 }
 
 extern "C" SMHV_API int smhv_batch_read_scale_labels(smhv_batch *b, uint32_t first, uint32_t n, smhv_scale_label_frame *out, uint8_t *crops) {
-	if (!b || !out || (uint64_t)first + n > b->max_frames) return fail(SMHV_E_INVALID, "batch_read_scale_labels: bad arguments");
-	if (!b->d_sl) return fail(SMHV_E_STATE, "batch_read_scale_labels: this batch has computed no scale labels");
-	int rc = batch_read_rows(b, b->d_sl, sizeof(smhv_scale_label_frame), first, n, out);
+	const int rc = batch_read_slab(b, b ? b->d_sl : nullptr, sizeof(smhv_scale_label_frame), first, n, out, "batch_read_scale_labels", "this batch has computed no scale labels");
 	if (rc || !crops) return rc;
 	return batch_read_rows(b, b->d_sl_crops, SMHV_LABEL_FRAME_CROP_BYTES, first, n, crops);
 }
@@ -94,18 +81,21 @@ extern "C" SMHV_API int smhv_scale_labels(smhv_ctx *c, smhv_scale_label_frame *o
 	rc = scale_labels_slabs(b);
 	if (rc) return rc;
 	hipStream_t s = c->s_scales;
-	const size_t rec = (sizeof(smhv_scale_label_frame) + 255u) & ~(size_t)255u, bytes = rec + (crops ? (size_t)SMHV_LABEL_FRAME_CROP_BYTES : 0u);
+	// [the record][the cells], each part on a 256-byte boundary
+	StageLayout lay;
+	lay.take(sizeof(smhv_scale_label_frame));
+	const StagePart cells = lay.part(crops, (size_t)SMHV_LABEL_FRAME_CROP_BYTES);
 	std::lock_guard<std::mutex> lk(c->fire_mu);
-	rc = ctx_stage_reserve(c, bytes);
+	rc = ctx_stage_reserve(c, lay.total());
 	if (rc) return rc;
 	rc = scale_labels_enqueue(b, c->frame_ptr, 1, s);
 	if (rc) return rc;
 	HIPCHK(hipMemcpyAsync(c->h_fire, b->d_sl, sizeof(smhv_scale_label_frame), hipMemcpyDeviceToHost, s));
-	if (crops) HIPCHK(hipMemcpyAsync(c->h_fire + rec, b->d_sl_crops, SMHV_LABEL_FRAME_CROP_BYTES, hipMemcpyDeviceToHost, s));
+	if (crops) HIPCHK(hipMemcpyAsync(c->h_fire + cells.off, b->d_sl_crops, cells.len, hipMemcpyDeviceToHost, s));
 	HIPCHK(wait_stream(s));
 	b->sl_n = 1; c->labels_valid = true;                       // (smhv_label_text)
 	memcpy(out, c->h_fire, sizeof *out);
-	if (crops) memcpy(crops, c->h_fire + rec, (size_t)std::min(out->n, (uint32_t)SMHV_MAX_SCALE_LABELS) * SMHV_LABEL_CROP_BYTES);
+	if (crops) memcpy(crops, c->h_fire + cells.off, (size_t)std::min(out->n, (uint32_t)SMHV_MAX_SCALE_LABELS) * SMHV_LABEL_CROP_BYTES);
 	return SMHV_OK;
 }
 

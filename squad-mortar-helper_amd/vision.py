@@ -25,6 +25,19 @@ def map_bounds(w, h):
     return tuple(out)
 
 
+def _minimap_arg(minimap):
+    """(left, right, top, bottom) or None -> the uint32[4] a per-call entry point takes, or NULL."""
+    return (C.c_uint32 * 4)(*[int(v) for v in minimap]) if minimap is not None else None
+
+
+def _window_image_check(name, image, options):
+    """(out_h, out_w) of `options`; an image to tint in place must be a contiguous uint8 [out_h, out_w, 4]."""
+    h, w = int(options.out_h), int(options.out_w)
+    if image is not None and (image.dtype != np.uint8 or image.shape != (h, w, 4) or not image.flags["C_CONTIGUOUS"]):
+        raise L.VisionError(L.E_INVALID, "%s: image must be a contiguous uint8 [%d, %d, 4]" % (name, h, w))
+    return h, w
+
+
 def button_bounds(w, h):
     out = (C.c_uint32 * 4)()
     L.check(L.load().smhv_button_bounds(w, h, out))
@@ -245,8 +258,7 @@ class HipVision:
         out = (L.Firing * max(n, 1))()
         opt = L.firing_options(fit_to_minimap, viewport)
         m = C.byref(C.c_double(float(mpx))) if mpx is not None else None
-        mm = (C.c_uint32 * 4)(*[int(v) for v in minimap]) if minimap is not None else None
-        L.check(self._lib.smhv_firing_solutions(self._ctx, ln.ctypes.data, n, m, mm, heightmap._hm if heightmap is not None else None, C.byref(opt), out))
+        L.check(self._lib.smhv_firing_solutions(self._ctx, ln.ctypes.data, n, m, _minimap_arg(minimap), L._hm(heightmap), C.byref(opt), out))
         return np.frombuffer(out, L.firing_dtype(), count=n).copy()
 
     def heightmap_overlay(self, heightmap, fit_to_minimap=True):
@@ -257,7 +269,7 @@ class HipVision:
         _, _, rw, rh = map_bounds(*self._size)
         out = np.empty((rh, rw, 4), np.uint8)
         opt = L.firing_options(fit_to_minimap)
-        L.check(self._lib.smhv_heightmap_overlay(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(opt), out.ctypes.data))
+        L.check(self._lib.smhv_heightmap_overlay(self._ctx, L._hm(heightmap), C.byref(opt), out.ctypes.data))
         return out
 
     def render_map(self, viewport, out_w, out_h, lines=None, heightmap=None, fit_to_minimap=True, background=(0, 0, 0, 255), options=None, layers=None,
@@ -278,7 +290,7 @@ class HipVision:
             ly, keep = layers.struct() if layers is not None else (None, None)
             res = L.LabelResult() if lo is not None else None
             probes = (L.Probe * L.MAX_PROBES)()
-            L.check(self._lib.smhv_render_map_debug(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(opt),
+            L.check(self._lib.smhv_render_map_debug(self._ctx, L._hm(heightmap), C.byref(opt),
                                                     C.byref(ly) if ly is not None else None, ln.ctypes.data if len(ln) else None, len(ln),
                                                     C.byref(lo) if lo is not None else None, C.byref(do), out.ctypes.data,
                                                     C.byref(res) if res is not None else None, probes))
@@ -288,18 +300,18 @@ class HipVision:
             lo, keep_labels = labels.struct()
             ly, keep = layers.struct() if layers is not None else (None, None)
             res = L.LabelResult()
-            L.check(self._lib.smhv_render_map_labeled(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(opt),
+            L.check(self._lib.smhv_render_map_labeled(self._ctx, L._hm(heightmap), C.byref(opt),
                                                       C.byref(ly) if ly is not None else None, ln.ctypes.data if len(ln) else None, len(ln), C.byref(lo),
                                                       out.ctypes.data, C.byref(res)))
             del keep, keep_labels
             return out, res
         if layers is not None:                                    # smhv_render_map_layers: prims, the minimap bounds, a debug view as the map
             ly, keep = layers.struct()
-            L.check(self._lib.smhv_render_map_layers(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(opt), C.byref(ly),
+            L.check(self._lib.smhv_render_map_layers(self._ctx, L._hm(heightmap), C.byref(opt), C.byref(ly),
                                                      ln.ctypes.data if len(ln) else None, len(ln), out.ctypes.data))
             del keep
             return out
-        L.check(self._lib.smhv_render_map(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(opt), ln.ctypes.data if len(ln) else None,
+        L.check(self._lib.smhv_render_map(self._ctx, L._hm(heightmap), C.byref(opt), ln.ctypes.data if len(ln) else None,
                                           len(ln), out.ctypes.data))
         return out
 
@@ -309,14 +321,11 @@ class HipVision:
         or None.  image: uint8 [out_h, out_w, 4] (any render_map image), tinted in place; classes: return the class bytes.
         -> (uint8 [out_h, out_w] or None, ReachResult)."""
         ro = reach.struct()
-        h, w = int(options.out_h), int(options.out_w)
-        if image is not None and (image.dtype != np.uint8 or image.shape != (h, w, 4) or not image.flags["C_CONTIGUOUS"]):
-            raise L.VisionError(L.E_INVALID, "reach_map: image must be a contiguous uint8 [%d, %d, 4]" % (h, w))
+        h, w = _window_image_check("reach_map", image, options)
         cls = np.empty((max(h, 1), max(w, 1)), np.uint8) if classes else None
         res = L.ReachResult()
         m = C.byref(C.c_double(float(mpx))) if mpx is not None else None
-        mm = (C.c_uint32 * 4)(*[int(v) for v in minimap]) if minimap is not None else None
-        L.check(self._lib.smhv_reach_map(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(options), C.byref(ro), m, mm,
+        L.check(self._lib.smhv_reach_map(self._ctx, L._hm(heightmap), C.byref(options), C.byref(ro), m, _minimap_arg(minimap),
                                          image.ctypes.data if image is not None else None, cls.ctypes.data if cls is not None else None, C.byref(res)))
         return cls, res
 
@@ -330,8 +339,7 @@ class HipVision:
         prof = np.zeros((n, L.CLEAR_PROFILE), np.float32) if profiles else None
         co = clearance.struct()
         opt = L.firing_options(fit_to_minimap, viewport)
-        mm = (C.c_uint32 * 4)(*[int(v) for v in minimap]) if minimap is not None else None
-        L.check(self._lib.smhv_clearance_lines(self._ctx, ln.ctypes.data if n else None, n, mm, heightmap._hm if heightmap is not None else None,
+        L.check(self._lib.smhv_clearance_lines(self._ctx, ln.ctypes.data if n else None, n, _minimap_arg(minimap), L._hm(heightmap),
                                                C.byref(opt), C.byref(co), out if n else None, prof.ctypes.data if prof is not None and n else None))
         return out, prof
 
@@ -341,13 +349,10 @@ class HipVision:
         frame's, or None.  image: uint8 [out_h, out_w, 4], tinted in place; bytes: return the status bytes.
         -> (uint8 [out_h, out_w] or None, ClearanceMapResult)."""
         co = clearance.struct()
-        h, w = int(options.out_h), int(options.out_w)
-        if image is not None and (image.dtype != np.uint8 or image.shape != (h, w, 4) or not image.flags["C_CONTIGUOUS"]):
-            raise L.VisionError(L.E_INVALID, "clearance_map: image must be a contiguous uint8 [%d, %d, 4]" % (h, w))
+        h, w = _window_image_check("clearance_map", image, options)
         out = np.empty((max(h, 1), max(w, 1)), np.uint8) if bytes else None
         res = L.ClearanceMapResult()
-        mm = (C.c_uint32 * 4)(*[int(v) for v in minimap]) if minimap is not None else None
-        L.check(self._lib.smhv_clearance_map(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(options), C.byref(co), mm,
+        L.check(self._lib.smhv_clearance_map(self._ctx, L._hm(heightmap), C.byref(options), C.byref(co), _minimap_arg(minimap),
                                              image.ctypes.data if image is not None else None, out.ctypes.data if out is not None else None, C.byref(res)))
         return out, res
 
@@ -357,16 +362,13 @@ class HipVision:
         [out_h, out_w, 4], tinted in place; bytes / shades / heights: return that plane.
         -> (uint8 [out_h, out_w] or None, uint8 [out_h, out_w] or None, float32 [out_h, out_w] or None, ReliefResult)."""
         ro = relief.struct()
-        h, w = int(options.out_h), int(options.out_w)
-        if image is not None and (image.dtype != np.uint8 or image.shape != (h, w, 4) or not image.flags["C_CONTIGUOUS"]):
-            raise L.VisionError(L.E_INVALID, "relief_map: image must be a contiguous uint8 [%d, %d, 4]" % (h, w))
+        h, w = _window_image_check("relief_map", image, options)
         shape = (max(h, 1), max(w, 1))
         fb = np.empty(shape, np.uint8) if bytes else None
         sh = np.empty(shape, np.uint8) if shades else None
         hs = np.empty(shape, np.float32) if heights else None
         res = L.ReliefResult()
-        mm = (C.c_uint32 * 4)(*[int(v) for v in minimap]) if minimap is not None else None
-        L.check(self._lib.smhv_relief_map(self._ctx, heightmap._hm if heightmap is not None else None, C.byref(options), C.byref(ro), mm,
+        L.check(self._lib.smhv_relief_map(self._ctx, L._hm(heightmap), C.byref(options), C.byref(ro), _minimap_arg(minimap),
                                           image.ctypes.data if image is not None else None, fb.ctypes.data if fb is not None else None,
                                           sh.ctypes.data if sh is not None else None, hs.ctypes.data if hs is not None else None, C.byref(res)))
         return fb, sh, hs, res
@@ -386,7 +388,7 @@ class HipVision:
         (smhv_feed_frame_view).  feed.read() hands the messages out."""
         ln = np.ascontiguousarray(lines if lines is not None else np.zeros((0, 4)), np.float32).reshape(-1, 4)
         m = C.byref(C.c_double(float(mpx))) if mpx is not None else None
-        mm = (C.c_uint32 * 4)(*[int(v) for v in minimap]) if minimap is not None else None
+        mm = _minimap_arg(minimap)
         flags = L.FEED_SNAPSHOT if snapshot else 0
         if map_source == L.VIEW_NONE:
             L.check(self._lib.smhv_feed_frame(self._ctx, feed._f, ln.ctypes.data if len(ln) else None, len(ln), m, mm, flags))
