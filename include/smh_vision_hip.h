@@ -1612,6 +1612,146 @@ SMHV_API int smhv_label_text(smhv_ctx *ctx, const smhv_glyph_atlas *atlas, smhv_
  * The frames' meters never visit the host.  (Pipelines take host anchors only.) */
 SMHV_API int smhv_batch_run_label_anchors(smhv_batch *b, const void *d_frames, uint32_t n, uint32_t stages, int grayscale, uint32_t max_gap, void *stream);
 
+/* ---- map grid: grid lines, cell labels and keypad references of every window pixel and of the line ends ----------------------------
+ * A mortar team talks in grid references: "B4, keypad 7, sub-keypad 3".  In Squad the minimap rectangle is the whole map and the
+ * grid's A1 sits at its top-left corner; with metres per pixel the cell of every window pixel and of every point follows.  The
+ * reference draws no grid; the rectangle and the translated points are "firing solutions"' alone.  Every operation is one IEEE f64
+ * operation, left to right, unfused, but for the rectangle, which stays f32 (csrc/smh_grid.h is the rule's one text, for the
+ * kernels, the host helper and a stand-alone check).
+ * Rectangle.  R = {l, t, r, b} = the heightmap's rectangle of "firing solutions" in f32, from the frame's minimap rectangle through the
+ *   render options' viewport (viewport_scale, 0 = 1; viewport_top_left).  An axis is (r0, r1) = (l, r) or (t, b), rlen = (double)(r1 - r0),
+ *   the difference in f32, s = the axis' viewport scale.
+ * Source.  SMHV_GRID_HEIGHTMAP: a heightmap is given and the frame is open and has a minimap rectangle (per call: a minimap was
+ *   given); SMHV_RENDER_BOUNDS_OFFSET acts on R as in the relief.  Metres of an f32 coordinate c on an axis of n texels:
+ *   m = (((double)c - (double)r0) / rlen) * (double)n -- one texel is one metre -- and pixels per metre ppm = rlen / (double)n.
+ *   SMHV_GRID_SCALES: no heightmap; the frame is open, has a minimap rectangle and metres per pixel (the record's has_mpx / mpx; per
+ *   call the mpx argument); no bounds offset applies.  m = (((double)c - (double)r0) / (double)s) * mpx, ppm = (double)s / mpx.
+ *   SMHV_GRID_NONE: anything else; nothing has a cell, the planes are zero and the summary is zero.
+ * Axis.  g = m - origin_m[axis].  The coordinate is IN iff r0 <= c && c < r1 in f32 and g is finite.  L = levels (0 .. 3),
+ *   P3 = {1, 3, 9, 27}, size_k = cell_m / (double)P3[k], a true division.  qf = floor(g / size_L), the one division of an axis
+ *   entry; the coordinate has no index when g is not finite or qf lies outside [-2^31, 2^31).  idx_L = (int64)qf, and every coarser
+ *   index comes by integer floor division, idx_(k-1) = floor_div(idx_k, 3) (towards minus infinity): a cell and its keypads agree by
+ *   construction, no second division exists that could disagree with the first at a boundary.
+ * Cell.  A pixel (c = X + 0.5f, Y + 0.5f in f32) or a point HAS A CELL iff both axes are IN and have an index, col = idx_0(x) lies
+ *   in [0, 702) and row1 = idx_0(y) + 1 in [1, 999].  Keypad digit of level k >= 1: cx = idx_k(x) mod 3, cy = idx_k(y) mod 3
+ *   (non-negative), digit = (2 - cy) * 3 + cx + 1: 7 8 9 on the top row as on the in-game map.
+ * Text.  The column in bijective base 26 (A .. Z, AA .. ZZ), the row in decimal, then "-<digit>" per level: "B4-7-3"; at most 11
+ *   characters, NUL-padded to 16.
+ * Drawn levels.  Ld = the greatest k <= L with size_k * ppm_x >= min_px and size_k * ppm_y >= min_px; -1 when no k does.
+ * Lines.  The pair (pixel, right neighbour), both with a cell, CROSSES at the least k <= Ld at which their idx_k(x) differ; the pair
+ *   (pixel, down neighbour) likewise with y.  A neighbour is evaluated by the same rule also where it lies outside the window.  The
+ *   pixel's line level is the lesser of its two pairs' levels, or none.
+ * Cell label.  "<letters><row>" inside every cell, in the 5 x 7 font of smhv_text_font, when Ld >= 0, label[3] != 0, rlen > 0 on both
+ *   axes and size_0 * ppm >= label_min_px on both.  Xfirst = the least integer column, inside the window or not, whose axis entry has
+ *   the pixel's own idx_0(x); Yfirst likewise.  ox = X - Xfirst - 3, oy = Y - Yfirst - 3; glyph gi = ox div 6, its column ox mod 6
+ *   (< 5), its row oy (0 .. 6), gi < the label's length; a pixel with a cell is LIT iff the font has that bit.  ox comes from the
+ *   pixel's own cell, so a label is clipped by its cell.  (A label is at most 5 glyphs: columns more than 32 to the left of X
+ *   decide nothing and are not looked at.)
+ * Paint (SMHV_GRID_PAINT), into the batch's render slab over whatever is there: the reach map's integer blend with line[k] on a pixel
+ *   of line level k (0 = major .. 3 = sub-sub-keypad), then with label on a LIT pixel.  A weight of 0 leaves the pixel as it is; the
+ *   alpha byte is untouched.
+ * Planes, out_w * out_h elements per frame, rows and frames tightly packed, the call's first frame first, into caller-provided device
+ *   memory (smhv_grid_planes): SMHV_GRID_BYTES u8 = SMHV_GRID_HAS_CELL | (level + 1) << 1 | SMHV_GRID_LABEL; SMHV_GRID_CELLS u32 =
+ *   col | row1 << 10 | digit_1 << 20 | digit_2 << 24 | digit_3 << 28, digits beyond `levels` 0, the whole word 0 without a cell.
+ * Summary.  One smhv_grid_result per frame in the batch's grid slab, cleared on the stream ahead of the kernel: valid = 1 iff source
+ *   != NONE (else every field is 0), source, drawn_levels = Ld + 1, n_cell, n_line[k], n_label = window pixels with a cell, of line
+ *   level k, LIT; col_first / col_last = the least and the greatest col, row_first / row_last the least and the greatest row1 over
+ *   the window pixels with a cell, all 0 when n_cell == 0.
+ * References (smhv_batch_grid_refs / smhv_grid_refs).  Each end of a line is the point P = (x * sw + tx, y * sh + ty) in f32, as the
+ *   firing solutions translate it, through the same axis rule: x_m, y_m = the g of both axes (0.0 where g is not finite), valid,
+ *   col, row1, digit[k - 1] and the text; a point without a cell has valid = 0 and zeros there.  With source NONE every field is 0. */
+#define SMHV_GRID_PAINT 1u             /* smhv_grid_options.flags: draw into the render slab (per call: implied by rgba_inout) */
+#define SMHV_GRID_BYTES 2u             /*   ... write the flag bytes (per call: implied by bytes) */
+#define SMHV_GRID_CELLS 4u             /*   ... write the cell words (per call: implied by cells) */
+#define SMHV_GRID_HAS_CELL 1u          /* the flag byte; bits 1 .. 3 = line level + 1 */
+#define SMHV_GRID_LABEL 0x10u
+#define SMHV_GRID_NONE 0u              /* smhv_grid_result.source */
+#define SMHV_GRID_SCALES 1u
+#define SMHV_GRID_HEIGHTMAP 2u
+#define SMHV_GRID_MAX_COLS 702u        /* A .. ZZ */
+#define SMHV_GRID_MAX_ROWS 999u
+typedef struct {
+	uint32_t size;                       /*  0: sizeof(smhv_grid_options) == 80 */
+	uint32_t flags;                      /*  4: SMHV_GRID_PAINT | _BYTES | _CELLS (no output flag: the summary alone) */
+	uint32_t levels;                     /*  8: L, keypad levels below the cell, 0 .. 3 */
+	uint32_t reserved0;                  /* 12 */
+	double cell_m;                       /* 16: the side of a cell in metres; finite, > 0 */
+	double origin_m[2];                  /* 24: metres from the rectangle's top-left corner to the corner of A1; finite */
+	double min_px;                       /* 40: a level is drawn when its cells are at least this many pixels wide and high; finite, >= 0 */
+	double label_min_px;                 /* 48: ... the labels when the cells are; finite */
+	uint8_t line[4][4];                  /* 56: R, G, B and the blend weight a of a line pixel of level 0 .. 3 */
+	uint8_t label[4];                    /* 72: ... of a LIT pixel; a == 0: no labels */
+	uint32_t reserved;                   /* 76 */
+} smhv_grid_options;
+typedef struct {
+	uint32_t valid;                      /*  0 */
+	uint32_t source;                     /*  4 */
+	uint32_t drawn_levels;               /*  8: Ld + 1 */
+	uint32_t n_cell;                     /* 12 */
+	uint32_t n_line[4];                  /* 16 */
+	uint32_t n_label;                    /* 32 */
+	uint32_t col_first, col_last;        /* 36 */
+	uint32_t row_first, row_last;        /* 44: as row1 */
+	uint32_t reserved[3];                /* 52 */
+} smhv_grid_result;                      /* 64 bytes */
+typedef struct {
+	void *bytes;                         /*  0: SMHV_GRID_BYTES: n * out_w * out_h u8, device memory */
+	void *cells;                         /*  8: SMHV_GRID_CELLS: n * out_w * out_h u32 */
+} smhv_grid_planes;                      /* 16 bytes */
+typedef struct {
+	double x_m, y_m;                     /*  0: g of both axes */
+	uint32_t col, row1;                  /* 16 */
+	uint8_t digit[3];                    /* 24: the keypad digits of levels 1 .. 3, 0 beyond `levels` */
+	uint8_t valid;                       /* 27: the point has a cell */
+	uint32_t reserved;                   /* 28 */
+	char text[16];                       /* 32 */
+} smhv_grid_ref;                         /* 48 bytes */
+typedef struct {
+	uint32_t n_lines;                    /*  0 */
+	uint32_t source;                     /*  4 */
+	uint32_t reserved[2];                /*  8 */
+	smhv_grid_ref ref[SMHV_MAX_LINES][2]; /* 16: the line's first and second end */
+} smhv_grid_refs_result;                 /* 3088 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(smhv_grid_options) == 80 && sizeof(smhv_grid_result) == 64 && sizeof(smhv_grid_planes) == 16, "map grid layout");
+static_assert(sizeof(smhv_grid_ref) == 48 && sizeof(smhv_grid_refs_result) == 3088, "map grid references layout");
+#endif
+/* Host only.  Fills *opt: size, flags = PAINT, cell_m = 300, levels = 2, origin_m = {0, 0}, min_px = 12, label_min_px = 48, line =
+ * (0, 0, 0, 170), (0, 0, 0, 110), (0, 0, 0, 70), (0, 0, 0, 45), label = (0, 0, 0, 200). */
+SMHV_API int smhv_grid_defaults(smhv_grid_options *opt);
+/* Host only: the text of a reference; digits[k - 1] = the digit of level k, levels of them are printed (digits may be NULL when
+ * levels == 0).  SMHV_E_INVALID: col >= 702, row1 outside 1 .. 999, levels > 3, a digit outside 1 .. 9, out == NULL. */
+SMHV_API int smhv_grid_ref_text(uint32_t col, uint32_t row1, const uint8_t *digits, uint32_t levels, char out[16]);
+/* The grid of frames [first, first + n), asynchronously on `stream`; the frames' results in the grid slab are cleared on the stream
+ * ahead of the kernel.  ropt supplies the window and the viewport; hm: the heightmap branch, NULL: the scales branch.  With PAINT
+ * the call runs behind whatever the batch's previous render enqueued and ropt->out_w / out_h must be the most recent render's
+ * (SMHV_E_STATE otherwise); without it only the records are read, as smhv_batch_relief reads them.  SMHV_E_INVALID: a wrong size,
+ * unknown flags, a plane flag whose pointer (or `planes`) is NULL, cell_m not finite or <= 0, levels > 3, origin_m, min_px or
+ * label_min_px not finite, min_px < 0, what smhv_batch_render rejects in ropt, n == 0, a range beyond the batch's capacity, a
+ * heightmap on another device.  A failed call enqueues nothing.  The batch keeps a reference of hm as smhv_batch_render does. */
+SMHV_API int smhv_batch_grid(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_render_options *ropt,
+                             const smhv_grid_options *opt, const smhv_grid_planes *planes, void *stream);
+/* The batch's grid slab: read is a synchronising host copy, ptr the device address (SMHV_E_STATE before the first smhv_batch_grid) */
+SMHV_API int smhv_batch_read_grid(smhv_batch *b, uint32_t first, uint32_t n, smhv_grid_result *out);
+SMHV_API int smhv_batch_grid_ptr(smhv_batch *b, void **d_grid);
+/* The per-call path, stateless like smhv_relief_map: mpx (NULL: none) and minimap = {left, right, top, bottom} (NULL: none) are the
+ * frame's.  rgba_inout (host, out_w * out_h * 4 bytes) is drawn into in place; bytes (host, out_w * out_h) and cells (host, out_w *
+ * out_h u32) receive the planes; result the summary.  Each of the four may be NULL, not all of them.  opt->flags is checked and
+ * otherwise not used.  Runs on the context's stream. */
+SMHV_API int smhv_grid_map(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_grid_options *opt, const double *mpx,
+                           const uint32_t minimap[4], uint8_t *rgba_inout, uint8_t *bytes, uint32_t *cells, smhv_grid_result *result);
+/* The references of the ends of the detected lines of frames [first, first + n), asynchronously on `stream`, into the batch's
+ * references slab (allocated by the first call): n_lines = the record's, ref[i] = line i's two ends, every entry past n_lines zero;
+ * a frame with source NONE is all zeros but n_lines.  The checks are smhv_batch_grid's (opt->flags is checked and not used). */
+SMHV_API int smhv_batch_grid_refs(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_render_options *ropt,
+                                  const smhv_grid_options *opt, void *stream);
+SMHV_API int smhv_batch_read_grid_refs(smhv_batch *b, uint32_t first, uint32_t n, smhv_grid_refs_result *out);
+SMHV_API int smhv_batch_grid_refs_ptr(smhv_batch *b, void **d_grid_refs);
+/* The per-call form, shaped like smhv_firing_solutions: lines in map-ROI coordinates, out receives 2 * n references (line i's ends at
+ * out[2 * i], out[2 * i + 1]); n == 0 does nothing. */
+SMHV_API int smhv_grid_refs(smhv_ctx *ctx, const smhv_line *lines, uint32_t n, const double *mpx, const uint32_t minimap[4], const smhv_heightmap *hm,
+                            const smhv_render_options *ropt, const smhv_grid_options *opt, smhv_grid_ref *out);
+
 #ifdef __cplusplus
 }
 #endif

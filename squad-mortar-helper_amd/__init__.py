@@ -17,6 +17,7 @@ from .render import LabelOptions, label_lines  # noqa: F401
 from .render import ReachOptions, reach_thresholds  # noqa: F401
 from .render import ClearanceOptions  # noqa: F401
 from .render import ReliefOptions, relief_light  # noqa: F401
+from .render import GridOptions, grid_ref_text  # noqa: F401
 from .render import scale_label_prims  # noqa: F401
 from .vision import scale_label_hits, scale_labels_anchors  # noqa: F401
 from ._lib import LABEL_CROP_H, LABEL_CROP_W, LABEL_MAX_RUNS, LABELS_RUNS_OVERFLOW, MAX_SCALE_LABELS, ScaleLabel, ScaleLabelFrame  # noqa: F401

@@ -166,6 +166,41 @@ class ReliefPlanes(C.Structure):
     _fields_ = [("bytes", C.c_void_p), ("shades", C.c_void_p), ("heights", C.c_void_p)]
 
 
+GRID_PAINT, GRID_BYTES, GRID_CELLS = 1, 2, 4                          # smhv_grid_options.flags
+GRID_HAS_CELL, GRID_LABEL = 1, 0x10                                   # the flag byte; bits 1 .. 3 = line level + 1
+GRID_NONE, GRID_SCALES, GRID_HEIGHTMAP = 0, 1, 2                      # smhv_grid_result.source
+
+
+class GridOptionsStruct(C.Structure):
+    """smhv_grid_options: the cells, their keypad levels and the paint of a map grid (80 bytes)."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("levels", C.c_uint32), ("reserved0", C.c_uint32), ("cell_m", C.c_double),
+                ("origin_m", C.c_double * 2), ("min_px", C.c_double), ("label_min_px", C.c_double), ("line", (C.c_uint8 * 4) * 4),
+                ("label", C.c_uint8 * 4), ("reserved", C.c_uint32)]
+
+
+class GridResult(C.Structure):
+    """smhv_grid_result: a frame's summary of its map grid (64 bytes)."""
+    _fields_ = [("valid", C.c_uint32), ("source", C.c_uint32), ("drawn_levels", C.c_uint32), ("n_cell", C.c_uint32), ("n_line", C.c_uint32 * 4),
+                ("n_label", C.c_uint32), ("col_first", C.c_uint32), ("col_last", C.c_uint32), ("row_first", C.c_uint32), ("row_last", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+class GridPlanes(C.Structure):
+    """smhv_grid_planes: the device memory of the planes a batch call writes (16 bytes)."""
+    _fields_ = [("bytes", C.c_void_p), ("cells", C.c_void_p)]
+
+
+class GridRef(C.Structure):
+    """smhv_grid_ref: the grid reference of a point (48 bytes)."""
+    _fields_ = [("x_m", C.c_double), ("y_m", C.c_double), ("col", C.c_uint32), ("row1", C.c_uint32), ("digit", C.c_uint8 * 3), ("valid", C.c_uint8),
+                ("reserved", C.c_uint32), ("text", C.c_char * 16)]
+
+
+class GridRefsResult(C.Structure):
+    """smhv_grid_refs_result: the references of the ends of a frame's lines (3088 bytes)."""
+    _fields_ = [("n_lines", C.c_uint32), ("source", C.c_uint32), ("reserved", C.c_uint32 * 2), ("ref", (GridRef * 2) * MAX_LINES)]
+
+
 CLEAR_MAX_SAMPLES = 256
 CLEAR_PROFILE = CLEAR_MAX_SAMPLES + 1                                  # floats of a line's profile row
 CLEAR_PAINT, CLEAR_BYTES = 1, 2                                        # smhv_clearance_options.flags
@@ -467,6 +502,19 @@ SIGNATURES = {
                                     C.POINTER(ReliefPlanes), C.c_void_p]),
     "smhv_batch_read_relief": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ReliefResult)]),
     "smhv_batch_relief_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smhv_grid_defaults": (C.c_int, [C.POINTER(GridOptionsStruct)]),
+    "smhv_grid_ref_text": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_uint32, C.c_char_p]),
+    "smhv_batch_grid": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(GridOptionsStruct),
+                                  C.POINTER(GridPlanes), C.c_void_p]),
+    "smhv_batch_read_grid": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(GridResult)]),
+    "smhv_batch_grid_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smhv_grid_map": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(GridOptionsStruct), C.POINTER(C.c_double),
+                                C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GridResult)]),
+    "smhv_batch_grid_refs": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(GridOptionsStruct), C.c_void_p]),
+    "smhv_batch_read_grid_refs": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(GridRefsResult)]),
+    "smhv_batch_grid_refs_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smhv_grid_refs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(RenderOptions),
+                                 C.POINTER(GridOptionsStruct), C.POINTER(GridRef)]),
     "smhv_relief_map": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(ReliefOptionsStruct), C.POINTER(C.c_uint32), C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ReliefResult)]),
     "smhv_batch_scale_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),

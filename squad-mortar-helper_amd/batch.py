@@ -355,6 +355,46 @@ class FrameBatch:
         """Device address of the relief slab (one smhv_relief_result per frame)."""
         return self._slab_ptr(self._lib.smhv_batch_relief_ptr)
 
+    def grid(self, options, grid, first=0, n=None, heightmap=None, bytes_ptr=None, cells_ptr=None, stream=None):
+        """The map grid of frames [first, first + n) on `stream` (smhv_batch_grid): options = a RenderOptions (the window and the
+        viewport; with paint the most recent render's), grid = a GridOptions, heightmap = the map's size in metres (None: the
+        records' metres per pixel).  A plane that grid asks for and that has no pointer (device memory, n * out_h * out_w elements)
+        is allocated as a torch tensor [n, out_h, out_w] (uint8; the cells int32, the u32 words' bits), and the call then returns
+        after the device has finished; with every plane's pointer given, or no plane, it is asynchronous.
+        -> dict(bytes=, cells=) of the tensors allocated here."""
+        n = self.max_frames - first if n is None else n
+        go = grid.struct()
+        out = {}
+        shape = (n, int(options.out_h), int(options.out_w))
+        ptrs = [self._plane(out, name, ptr, getattr(grid, name), shape, "int32" if name == "cells" else "uint8")
+                for name, ptr in (("bytes", bytes_ptr), ("cells", cells_ptr))]
+        planes = L.GridPlanes(*[int(p) if p else None for p in ptrs])
+        self._call(out, self._lib.smhv_batch_grid, self._b, first, n, L._hm(heightmap), C.byref(options), C.byref(go), C.byref(planes), _ptr(stream))
+        return out
+
+    def read_grid(self, first=0, n=None):
+        """Synchronising host copy of the grid slab -> a ctypes array of n GridResult."""
+        return self._read_slab(self._lib.smhv_batch_read_grid, L.GridResult, first, n)
+
+    def grid_ptr(self):
+        """Device address of the grid slab (one smhv_grid_result per frame)."""
+        return self._slab_ptr(self._lib.smhv_batch_grid_ptr)
+
+    def grid_refs(self, options, grid, first=0, n=None, heightmap=None, stream=None):
+        """The grid references of the ends of the detected lines of frames [first, first + n) on `stream` (smhv_batch_grid_refs);
+        options, grid, heightmap as grid() takes them.  Asynchronous; read_grid_refs() waits for the records."""
+        n = self.max_frames - first if n is None else n
+        go = grid.struct()
+        L.check(self._lib.smhv_batch_grid_refs(self._b, first, n, L._hm(heightmap), C.byref(options), C.byref(go), _ptr(stream)))
+
+    def read_grid_refs(self, first=0, n=None):
+        """Synchronising host copy of the references slab -> a ctypes array of n GridRefsResult."""
+        return self._read_slab(self._lib.smhv_batch_read_grid_refs, L.GridRefsResult, first, n)
+
+    def grid_refs_ptr(self):
+        """Device address of the references slab (one smhv_grid_refs_result per frame)."""
+        return self._slab_ptr(self._lib.smhv_batch_grid_refs_ptr)
+
     def clearance(self, clearance, first=0, n=None, heightmap=None, fit_to_minimap=True, viewport=None, profiles_ptr=None, profiles=False, stream=None):
         """The terrain clearance of the detected lines of frames [first, first + n) on `stream` (smhv_batch_clearance): clearance = a
         ClearanceOptions (samples, margin_m); heightmap, fit_to_minimap, viewport as the firing solutions take them.  With

@@ -32,6 +32,7 @@
 #include "smh_consts.h"
 #include "smh_kernels.h"
 #include "smh_glyph_rule.h"
+#include "smh_grid.h"
 
 using namespace smh;
 
@@ -282,6 +283,10 @@ struct smhv_batch {
 	// smhv_batch_relief: the relief slab (allocated by the first call) and the heightmap the last call read
 	smhv_relief_result *d_relief = nullptr;
 	smhv_heightmap *relief_hm = nullptr;
+	// smhv_batch_grid / smhv_batch_grid_refs: their slabs (allocated by the first call) and the heightmap the last smhv_batch_grid was given
+	smhv_grid_result *d_grid = nullptr;
+	smhv_grid_refs_result *d_grid_refs = nullptr;
+	smhv_heightmap *grid_hm = nullptr;
 	// smhv_batch_scale_labels: the label slab, the crop slab and the family's own find_scales_preprocess plane with start row 0
 	// (allocated by the first call); what the batch's most recent run covered (its stages and frame count)
 	smhv_scale_label_frame *d_sl = nullptr;
@@ -681,7 +686,7 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	(void)hipDeviceSynchronize();
 	void *ptrs[] = {b->d_ui, b->d_ui_luma, b->d_ui_form, b->d_mask, b->d_bits, b->d_tiled, b->d_occ, b->d_ocr, b->d_scales, b->d_aux, b->d_results, b->d_anchors, b->d_bars, b->d_farm,
 	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run, b->d_overlay, b->d_render, b->d_prims, b->d_labels,
-	                b->d_label_cull, b->d_label_extra, b->d_probes, b->d_dbg_items, b->d_dbg_pool, b->d_dbg_stage, b->d_reach, b->d_clear, b->d_clear_map, b->d_relief,
+	                b->d_label_cull, b->d_label_extra, b->d_probes, b->d_dbg_items, b->d_dbg_pool, b->d_dbg_stage, b->d_reach, b->d_clear, b->d_clear_map, b->d_relief, b->d_grid, b->d_grid_refs,
 	                b->d_sl, b->d_sl_crops, b->d_sl_s0, b->d_lt, b->d_lt_anchors};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
@@ -708,6 +713,7 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	hm_release(b->clear_hm);
 	hm_release(b->clear_map_hm);
 	hm_release(b->relief_hm);
+	hm_release(b->grid_hm);
 	if (b->ev_render) (void)hipEventDestroy(b->ev_render);
 	if (b->ev) {
 		for (int r = 0; r < smhv_batch::TIMING_RING; ++r)
@@ -970,7 +976,7 @@ template <class F> static int for_each_launch(uint32_t n, F &&fn) {
 	return SMHV_OK;
 }
 
-// ---- the window passes (the reach map, the clearance map, the relief): one batch path and one per-call path.  Their Run structs
+// ---- the window passes (the reach map, the clearance map, the relief, the map grid): one batch path and one per-call path.  Their Run structs
 // agree on fr, out_w, out_h, img_stride, aux, res, out, img, per_call, has_mm, mm; the planes are the family's own, set by its
 // `launch`.  A new window pass is its options' defaults and check, its run params, and two entry points that call these.
 //
@@ -3486,5 +3492,6 @@ extern "C" SMHV_API int smhv_heightmap_overlay(smhv_ctx *c, const smhv_heightmap
 #include "smh_reach.inc"
 #include "smh_clear.inc"
 #include "smh_relief.inc"
+#include "smh_grid.inc"
 #include "smh_scalelabels.inc"
 #include "smh_labeltext.inc"

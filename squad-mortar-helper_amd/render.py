@@ -313,6 +313,51 @@ class ReliefOptions:
         return o
 
 
+# ---- map grid (smhv_batch_grid / smhv_grid_map / smhv_batch_grid_refs / smhv_grid_refs): grid lines, cell labels, keypad references --------
+class GridOptions:
+    """What a grid call computes: cell_m = the side of a cell in metres, levels = keypad levels below the cell (0 .. 3), origin_m =
+    metres from the map's top-left corner to the corner of A1; min_px = a level is drawn when its cells are at least this many
+    pixels wide and high, label_min_px = the labels when the cells are; paint / bytes / cells = draw into the render slab / write that
+    plane; line = four rgba (major, keypad, sub-keypad, sub-sub-keypad) and label = one, a = the blend weight (None: the library's,
+    smhv_grid_defaults)."""
+
+    def __init__(self, cell_m=None, levels=None, origin_m=None, min_px=None, label_min_px=None, paint=True, bytes=False, cells=False, line=None,
+                 label=None):
+        self.cell_m, self.levels, self.origin_m, self.min_px, self.label_min_px = cell_m, levels, origin_m, min_px, label_min_px
+        self.paint, self.bytes, self.cells = bool(paint), bool(bytes), bool(cells)
+        self.line, self.label = line, label
+
+    def struct(self):
+        """-> smhv_grid_options."""
+        o = L.GridOptionsStruct()
+        L.check(L.load().smhv_grid_defaults(C.byref(o)))
+        o.flags = (L.GRID_PAINT if self.paint else 0) | (L.GRID_BYTES if self.bytes else 0) | (L.GRID_CELLS if self.cells else 0)
+        for name in ("cell_m", "min_px", "label_min_px"):
+            if getattr(self, name) is not None:
+                setattr(o, name, float(getattr(self, name)))
+        if self.levels is not None:
+            o.levels = int(self.levels)
+        if self.origin_m is not None:
+            o.origin_m[0], o.origin_m[1] = float(self.origin_m[0]), float(self.origin_m[1])
+        if self.line is not None:
+            for k in range(4):
+                for j in range(4):
+                    o.line[k][j] = int(self.line[k][j])
+        if self.label is not None:
+            for j in range(4):
+                o.label[j] = int(self.label[j])
+        return o
+
+
+def grid_ref_text(col, row1, digits=()):
+    """The text of a grid reference (smhv_grid_ref_text): column 0 = A, row1 from 1, digits = the keypad digits of levels 1 .. ->
+    "B4-7-3"."""
+    d = (C.c_uint8 * 3)(*[int(v) for v in digits])
+    out = C.create_string_buffer(16)
+    L.check(L.load().smhv_grid_ref_text(int(col), int(row1), d, len(digits), out))
+    return out.raw.rstrip(b"\0").decode("ascii")
+
+
 # ---- debug text and the vision debugger (smhv_batch_probe / smhv_batch_render_debug / smhv_render_map_debug) ------------------------
 def text_run(x, y, text, rgba=(255, 255, 255, 255), map_coords=False):
     """One smhv_text_run as a tuple (x, y, (r, g, b, a), flags, bytes): `text` a str (encoded as Latin-1) or bytes, '\\n' starts a

@@ -373,6 +373,36 @@ class HipVision:
                                           sh.ctypes.data if sh is not None else None, hs.ctypes.data if hs is not None else None, C.byref(res)))
         return fb, sh, hs, res
 
+    def grid_map(self, options, grid, mpx=None, minimap=None, heightmap=None, image=None, bytes=True, cells=True):
+        """The map grid of one window (smhv_grid_map; stateless like relief_map): options = a RenderOptions (the window and the
+        viewport), grid = a GridOptions; mpx, minimap = (left, right, top, bottom): the frame's, or None; heightmap: the map's size
+        in metres, None: the scales branch.  image: uint8 [out_h, out_w, 4], drawn into in place; bytes / cells: return that plane.
+        -> (uint8 [out_h, out_w] or None, uint32 [out_h, out_w] or None, GridResult)."""
+        go = grid.struct()
+        h, w = _window_image_check("grid_map", image, options)
+        shape = (max(h, 1), max(w, 1))
+        fb = np.empty(shape, np.uint8) if bytes else None
+        cw = np.empty(shape, np.uint32) if cells else None
+        res = L.GridResult()
+        m = C.byref(C.c_double(float(mpx))) if mpx is not None else None
+        L.check(self._lib.smhv_grid_map(self._ctx, L._hm(heightmap), C.byref(options), C.byref(go), m, _minimap_arg(minimap),
+                                        image.ctypes.data if image is not None else None, fb.ctypes.data if fb is not None else None,
+                                        cw.ctypes.data if cw is not None else None, C.byref(res)))
+        return fb, cw, res
+
+    def grid_refs(self, lines, options, grid, mpx=None, minimap=None, heightmap=None):
+        """The grid references of the ends of explicit lines in map-ROI coordinates (smhv_grid_refs; stateless like
+        firing_solutions): lines: float32 [n, 4]; options, grid, mpx, minimap, heightmap as grid_map takes them.
+        -> a ctypes array of 2 * n GridRef (line i's ends at 2 * i and 2 * i + 1)."""
+        ln = np.ascontiguousarray(np.asarray(lines, np.float32).reshape(-1, 4))
+        n = ln.shape[0]
+        out = (L.GridRef * (2 * n))()
+        go = grid.struct()
+        m = C.byref(C.c_double(float(mpx))) if mpx is not None else None
+        L.check(self._lib.smhv_grid_refs(self._ctx, ln.ctypes.data if n else None, n, m, _minimap_arg(minimap), L._hm(heightmap), C.byref(options),
+                                         C.byref(go), out if n else None))
+        return out
+
     def probe(self, viewport, points, out_w=1, out_h=1):
         """The vision debugger's numbers of the current frame at `points` = [(mx, my)] window positions through `viewport` (a
         MapViewport) -> a ctypes array of MAX_PROBES Probe.  The per-call path has no probe-only entry point: this is
