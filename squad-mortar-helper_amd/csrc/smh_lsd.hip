@@ -230,6 +230,42 @@ __device__ __forceinline__ uint32_t win2_raw(const Win &m, float x, float y) {
 	const uint32_t word = *(const LdsWord *)(m.w2 + __mul24(yi, (int)(4u * LSD_W2_PITCH)) + ((xi >> 3) & ~3));
 	return word >> ((uint32_t)xi & 31u);
 }
+// The search service's sampler of a ray's first batches (ray_batch<LSD_MODE_WIN2, G, true>; k_lsd_service only).  A wave of the
+// service is alone on its SIMD below the streaming waves' priority: nobody else fills its issue slots, every instruction it issues
+// is paid for, a satisfied s_waitcnt included -- so the sampler has an instruction budget (not the whole story: 5).
+//   Bit address.  A window row is LSD_W2_PITCH whole words = 192 bits and w2 is word-aligned, so with ba = yi * 192 + xi the
+//   word of pixel (xi, yi) is word (ba >> 5) from w2 and its bit is ba & 31:
+//       (ba >> 5) * 4 == yi * 24 + ((xi >> 3) & ~3)   and   ba & 31 == xi & 31      for EVERY int xi, yi, negative ones included
+//   (the window has columns left of and rows above the image), because 192 yi is a multiple of 32: it adds 6 yi to the
+//   arithmetic shift's floor and nothing to the low five bits.  One v_mad_i32_i24, one v_ashrrev, one v_lshl_add_u32 (the word
+//   index scaled in the address add) where win2_raw takes four; v_lshrrev uses the low five bits of ba as they are.
+//   win2_issue: the positions of N samples (the reference's additions in its order) and their N reads, nothing that waits.
+//   win2_bits: the whiteness bits of samples FROM .. TO - 1 shifted into Wm from the top -- behind ONE wait of the caller's for all
+//   of them: no wait that waits for nothing (the compiler's own come one per register, lgkmcnt(15) .. lgkmcnt(0)).
+static_assert((32u * LSD_W2_PITCH) % 32u == 0u && 32u * LSD_W2_PITCH == 192u, "the bit address yi * pitch + xi: a row is whole words (and the comments say 192)");
+static_assert(32u * LSD_W2_PITCH * 8192u < (1u << 23), "yi * 192 + xi stays a 24-bit product for every supported frame height");
+template <int N>
+__device__ __forceinline__ void win2_issue(const LdsWord *w2, float xs, float ys, float dx, float dy, float &xo, float &yo, float &x, float &y, uint32_t (&word)[N], uint32_t (&ba)[N]) {
+#pragma unroll
+	for (int j = 0; j < N; ++j) {
+		x = xo + xs; y = yo + ys;
+		const int b = __mul24((int)y, (int)(32u * LSD_W2_PITCH)) + (int)x;
+		ba[j] = (uint32_t)b;
+		word[j] = w2[b >> 5];
+		xo += dx; yo += dy;
+	}
+	// (the reads stay where the compiler puts them, all N behind all N addresses: issued one by one right behind their own addresses
+	// -- sched_group_barrier -- the same instructions ran SLOWER than ray_batch's generic loop)
+}
+template <int N, int FROM = 0, int TO = N>
+__device__ __forceinline__ void win2_bits(const uint32_t (&word)[N], const uint32_t (&ba)[N], uint32_t &Wm) {
+#pragma unroll
+	for (int j = FROM; j < TO; ++j) Wm = __builtin_amdgcn_alignbit(word[j] >> (ba[j] & 31u), Wm, 1);
+}
+// s_waitcnt lgkmcnt(n) alone (gfx9 encoding: vmcnt and expcnt at their maxima = not waited for), pinned where it stands.  LDS
+// reads return in order: lgkmcnt(n) after a group's reads and n younger ones retires the group.  The compiler keeps its own
+// count (a wait it still needs it adds itself); what this one buys is that its per-register waits behind it drop out.
+#define LSD_WAIT_LGKM(n) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0xC07F | ((n) << 8)); __builtin_amdgcn_sched_barrier(0); } while (0)
 __device__ __forceinline__ uint32_t win2_word(const Win &m, int wq, int yi) { return *(const LdsWord *)(m.w2 + __mul24(yi, (int)(4u * LSD_W2_PITCH)) + (wq << 2)); }
 __device__ __forceinline__ uint32_t win2_bit(const Win &m, int xi, int yi) { return (win2_word(m, xi >> 5, yi) >> ((uint32_t)xi & 31u)) & 1u; }
 
@@ -317,16 +353,33 @@ enum { RAY_CONTINUE = 0, RAY_ABORTED = 1, RAY_LEFT_IMAGE = 2 };
 //   RAY_ABORTED    : the run started at global step s.gk0 + s.gj; samples taken = *steps
 //   RAY_LEFT_IMAGE : the first out-of-image position is step s.k0 + s.nexit
 // G: samples whose LDS reads are in flight together (8, 16 or 32).
-template <int MODE, int G = 8>
+// LEAN (LSD_MODE_WIN2 only; the search service): the sampler above -- same samples, same additions, same results.
+template <int MODE, int G = 8, bool LEAN = false>
 __device__ __forceinline__ int ray_batch(const Win &m, float xs, float ys, float dx, float dy, uint32_t T, RayState &s, uint32_t &steps) {
-	static_assert((G == 8 || G == 16 || G == 32) && ((MODE != LSD_MODE_TILE && MODE != LSD_MODE_TILEC) || G == 8), "group size");
+	static_assert((G == 8 || G == 16 || G == 32) && ((MODE != LSD_MODE_TILE && MODE != LSD_MODE_TILEC) || G == 8) && (!LEAN || (MODE == LSD_MODE_WIN2 && G <= 16)), "group size (LEAN: the counted wait is G / 2 <= 15 reads)");
 	float xo = s.bxo, yo = s.byo, x = 0.0f, y = 0.0f;
-	uint32_t Wm = 0;
+	uint32_t Wm = 0, taken = 0;
+	if constexpr (LEAN) {
+		const LdsWord *w2 = (const LdsWord *)m.w2;
+		// G samples a round: one counted wait retires the first half, whose bits are assembled while the second half comes back
+#pragma unroll 1
+		for (int jj = 0; jj < 32 / G; ++jj) {
+			uint32_t wa[G], ba[G];
+			win2_issue(w2, xs, ys, dx, dy, xo, yo, x, y, wa, ba);
+			LSD_WAIT_LGKM(G / 2);
+			win2_bits<G, 0, G / 2>(wa, ba, Wm);
+			asm volatile("" : "+v"(Wm));                    // (no instruction: the first half's bits are assembled HERE, not sunk behind the second wait)
+			LSD_WAIT_LGKM(0);
+			win2_bits<G, G / 2, G>(wa, ba, Wm);
+			taken += (uint32_t)G;
+			if (taken > T && taken < 32u && __all((Wm >> (31u - T)) == 0u)) break;      // (as below)
+		}
+	}
 	// 4 x 8 samples: eight LDS reads in flight per wave keep the register footprint small enough for
 	// 16 waves per CU; the whiteness bits are shifted in from the top (sample j ends up in bit j).  (G = 16 / 32: the
 	// one-wave-per-frame scan of the search service, a single wave on its SIMD beside the streaming pass, where an LDS round
 	// trip takes several hundred cycles and there is nobody else to hide it behind.)
-	uint32_t taken = 0;
+	if constexpr (!LEAN)
 #pragma unroll 1
 	for (int jj = 0; jj < 32 / G; ++jj) {
 		if constexpr (MODE == LSD_MODE_TILE) tile_raw8(m, xs, ys, dx, dy, xo, yo, x, y, Wm);

@@ -289,13 +289,21 @@ __device__ __forceinline__ void tilec_win(Win &m, uint32_t rw, uint32_t rh, uint
 #endif
 #define SVC_WIN_ROWS(compact) (SVC_WIN_REUSE(compact) ? W_WIN_ROWS + SVC_WIN_EXTRA : W_WIN_ROWS)
 #define SVC_WIN_STRIDE(compact) (SVC_WIN_ROWS(compact) * LSD_W2_PITCH + 2u)   // words per service window block (as W_WIN_STRIDE)
+// The service's own sampler of a ray's first batches (ray_batch<.., LEAN>, smh_lsd.hip): k_lsd_service alone; k_lsd_service_c keeps
+// the 32-sample groups of ray_batch as they were.  -DSMH_NO_LEAN_SAMPLER: the sampler before it (the A/B switch).
+#ifdef SMH_NO_LEAN_SAMPLER
+#define SVC_LEAN_SAMPLER(compact) false
+#else
+#define SVC_LEAN_SAMPLER(compact) (!(compact))
+#endif
 
 // One candidate from its pixel to its longest ray, by one wave: window + get_centre + sector culling (cand_setup), then its
 // live 64-ray units one after the other (the next unit's directions fetched while this one is cast).
 // -> start point; wkey = len^2 bits << 32 | ray index of the longest exactly evaluated ray (0: none could make a line), its end
 // point; mask samples taken (sum over the wave)
 // REUSE: `wwin` holds the window `tag` places (W_WIN_ROWS + SVC_WIN_EXTRA rows) and is filled only when it does not serve; else: filled for this candidate
-template <int MODE, bool REUSE = false>
+// LEAN: the rays' first batches through the service's own sampler (ray_batch, smh_lsd.hip)
+template <int MODE, bool REUSE = false, bool LEAN = false>
 __device__ __forceinline__ void seq_cast_candidate(const Win &m, uint32_t *wwin, WinTag *tag, const uint32_t *cull_tab, uint32_t cull, const RayDir *dirs, const float *ray_off, float max_gap,
                                                    uint32_t px, uint32_t py, float &xs, float &ys, unsigned long long &wkey, float &ex0, float &ey0, uint32_t &steps_sum
 #ifdef SMH_LSD_WDEBUG
@@ -323,10 +331,10 @@ __device__ __forceinline__ void seq_cast_candidate(const Win &m, uint32_t *wwin,
 		unsigned long long key;
 		float xe, ye;
 #ifdef SMH_LSD_WDEBUG
-		unit_rays<MODE, (MODE == LSD_MODE_TILEC ? SEQ_RAY_GROUP_C : SEQ_RAY_GROUP), REUSE>(m, wwin, ray_off, px, py, xs, ys, u, d, max_gap, key, xe, ye, st, uprof, tag);
+		unit_rays<MODE, (MODE == LSD_MODE_TILEC ? SEQ_RAY_GROUP_C : SEQ_RAY_GROUP), REUSE, LEAN>(m, wwin, ray_off, px, py, xs, ys, u, d, max_gap, key, xe, ye, st, uprof, tag);
 		++n_units;
 #else
-		unit_rays<MODE, (MODE == LSD_MODE_TILEC ? SEQ_RAY_GROUP_C : SEQ_RAY_GROUP), REUSE>(m, wwin, ray_off, px, py, xs, ys, u, d, max_gap, key, xe, ye, st, tag);
+		unit_rays<MODE, (MODE == LSD_MODE_TILEC ? SEQ_RAY_GROUP_C : SEQ_RAY_GROUP), REUSE, LEAN>(m, wwin, ray_off, px, py, xs, ys, u, d, max_gap, key, xe, ye, st, tag);
 #endif
 		if (key > bkey) { bkey = key; bxe = xe; bye = ye; }
 	}
@@ -584,7 +592,8 @@ __device__ __forceinline__ void desk_post_more(WShared &ws, const uint32_t *list
 
 // dirs: the 3600 ray directions in LDS (a copy of g_ray_table).  TEAM: the frame may ask the other waves of its workgroup for
 // help (the search service; tile store only).  REUSE: the wave's window block keeps its window between candidates (seq_cast_candidate)
-template <int MODE, bool WAVE = false, bool TEAM = false, bool REUSE = false>
+// LEAN: seq_cast_candidate's
+template <int MODE, bool WAVE = false, bool TEAM = false, bool REUSE = false, bool LEAN = false>
 __device__ void lsd_frame_seq(const Geom &g, const Buffers &b, uint32_t f, float max_gap, const FrameAux &aux, uint32_t *smem, WShared &ws, const uint32_t *cull_tab, const RayDir *dirs,
                               uint32_t win_cap, uint32_t list_cap, const FrameView *tile_view = nullptr) {
 	static_assert(!TEAM || (WAVE && (MODE == LSD_MODE_TILE || MODE == LSD_MODE_TILEC)), "helpers read the owner's tile store in LDS");
@@ -654,9 +663,9 @@ __device__ void lsd_frame_seq(const Geom &g, const Buffers &b, uint32_t f, float
 #endif
 #ifdef SMH_LSD_WDEBUG
 			if (have) ++n_taken;
-			if (!have) seq_cast_candidate<MODE, REUSE>(m, wwin, &wtag, cull_tab, cull, dirs, b.ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum, sprof, slast, uprof, n_units);
+			if (!have) seq_cast_candidate<MODE, REUSE, LEAN>(m, wwin, &wtag, cull_tab, cull, dirs, b.ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum, sprof, slast, uprof, n_units);
 #else
-			if (!have) seq_cast_candidate<MODE, REUSE>(m, wwin, &wtag, cull_tab, cull, dirs, b.ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum);
+			if (!have) seq_cast_candidate<MODE, REUSE, LEAN>(m, wwin, &wtag, cull_tab, cull, dirs, b.ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum);
 #endif
 			if (lane == 0) ws.steps += st_sum;
 			if (wkey != 0ull && __uint_as_float((uint32_t)(wkey >> 32)) > SMH_LSD_ACCEPT_LEN_SQ) {   // lsd.rs:94

@@ -474,8 +474,9 @@ __device__ __forceinline__ void long_rays_round(const Win &m, const float *ray_o
 // The rays of unit u of the candidate whose pixel is (px, py) and start point (xs, ys): per lane the ray's key (len^2 bits << 32
 // | ray index; 0 = not evaluated exactly: it cannot matter), its end point and the mask samples it took (added to `steps`).
 __device__ __forceinline__ RayDir unit_dirs(uint32_t u) { return g_ray_table[min(u * 64u + (threadIdx.x & 63u), (uint32_t)SMH_LSD_RAYS - 1u)]; }
-// (d = unit_dirs(u): a global load the caller may issue early; tag: where the window lies when cand_setup was given one)
-template <int MODE, int G = 8, bool TAGGED = false>
+// (d = unit_dirs(u): a global load the caller may issue early; tag: where the window lies when cand_setup was given one; LEAN: the
+// first batches through the search service's sampler, ray_batch)
+template <int MODE, int G = 8, bool TAGGED = false, bool LEAN = false>
 __device__ __forceinline__ void unit_rays(const Win &m, const uint32_t *wwin, const float *ray_off, uint32_t px, uint32_t py, float xs, float ys, uint32_t u, const RayDir d, float max_gap,
                                           unsigned long long &key, float &xe, float &ye, uint32_t &steps UPROF_PARAM, const WinTag *tag = nullptr) {
 #ifdef SMH_LSD_WDEBUG
@@ -500,7 +501,7 @@ __device__ __forceinline__ void unit_rays(const Win &m, const uint32_t *wwin, co
 			mw.w2 = TAGGED ? window_base_at(wwin, tag->x0w, tag->y0) : window_base(wwin, px, py);
 			status = RAY_CONTINUE;
 #pragma unroll 1
-			for (uint32_t bi = 0; bi < W_A_BATCHES && status == RAY_CONTINUE; ++bi) status = ray_batch<LSD_MODE_WIN2, G>(mw, xs, ys, dx, dy, T, s, steps);
+			for (uint32_t bi = 0; bi < W_A_BATCHES && status == RAY_CONTINUE; ++bi) status = ray_batch<LSD_MODE_WIN2, G, LEAN>(mw, xs, ys, dx, dy, T, s, steps);
 			if (status == RAY_ABORTED) K = s.gk0 + s.gj;
 		} else {
 			cast_ray_literal(m, xs, ys, max_gap, dx, dy, xe, ye, steps);

@@ -53,7 +53,7 @@ __device__ __attribute__((noinline)) void svc_frame_global(const void *kargs, ui
 	const Geom g = ka->g;
 	const Buffers b = ((SvcSlotPtr)(ka->p.slots + slot))->b;
 	const FrameAux aux = b.aux[f];
-	lsd_frame_seq<LSD_MODE_GLOBAL, true, false, SVC_WIN_REUSE(COMPACT)>(g, b, f, ka->p.max_gap, aux, part + SVC_WS_WORDS, *(WShared *)part, lds_ptr(cull_off), (const RayDir *)lds_ptr(dirs_off), 0u, ka->p.list_cap);
+	lsd_frame_seq<LSD_MODE_GLOBAL, true, false, SVC_WIN_REUSE(COMPACT), SVC_LEAN_SAMPLER(COMPACT)>(g, b, f, ka->p.max_gap, aux, part + SVC_WS_WORDS, *(WShared *)part, lds_ptr(cull_off), (const RayDir *)lds_ptr(dirs_off), 0u, ka->p.list_cap);
 }
 
 // -> s_memtime at the end of the search proper (before the record)
@@ -92,7 +92,7 @@ __device__ __attribute__((noinline)) unsigned long long svc_frame(const void *ka
 		}
 		if (fits) {
 			if constexpr (COMPACT) lsd_frame_seq<LSD_MODE_TILEC, true, true, SVC_WIN_REUSE(true)>(g, b, f, ka->p.max_gap, aux, smem, ws, lds_ptr(cull_off), (const RayDir *)lds_ptr(dirs_off), tilec_mask_words(g.rw, g.rh, tile_cap), ka->p.list_cap, &v);
-			else lsd_frame_seq<LSD_MODE_TILE, true, true, SVC_WIN_REUSE(false)>(g, b, f, ka->p.max_gap, aux, smem, ws, lds_ptr(cull_off), (const RayDir *)lds_ptr(dirs_off), tile_mask_words(g.rw, g.rh, tile_cap), ka->p.list_cap, &v);
+			else lsd_frame_seq<LSD_MODE_TILE, true, true, SVC_WIN_REUSE(false), SVC_LEAN_SAMPLER(false)>(g, b, f, ka->p.max_gap, aux, smem, ws, lds_ptr(cull_off), (const RayDir *)lds_ptr(dirs_off), tile_mask_words(g.rw, g.rh, tile_cap), ka->p.list_cap, &v);
 		} else svc_frame_global<COMPACT>(kargs, slot, f, part_off, cull_off, dirs_off);
 	}
 	const unsigned long long t_search_end = __builtin_amdgcn_s_memtime();
@@ -163,9 +163,9 @@ __device__ __attribute__((noinline)) void svc_help(const void *kargs, uint32_t o
 #ifdef SMH_LSD_WDEBUG
 		unsigned long long sprof[8] = {0, 0, 0, 0, 0, 0, 0, 0}, slast = __builtin_amdgcn_s_memtime(), uprof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 		uint32_t n_units = 0;
-		seq_cast_candidate<COMPACT ? LSD_MODE_TILEC : LSD_MODE_TILE, SVC_WIN_REUSE(COMPACT)>(m, wwin, &wtag, cull_tab, cull, dirs, ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum, sprof, slast, uprof, n_units);
+		seq_cast_candidate<COMPACT ? LSD_MODE_TILEC : LSD_MODE_TILE, SVC_WIN_REUSE(COMPACT), SVC_LEAN_SAMPLER(COMPACT)>(m, wwin, &wtag, cull_tab, cull, dirs, ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum, sprof, slast, uprof, n_units);
 #else
-		seq_cast_candidate<COMPACT ? LSD_MODE_TILEC : LSD_MODE_TILE, SVC_WIN_REUSE(COMPACT)>(m, wwin, &wtag, cull_tab, cull, dirs, ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum);
+		seq_cast_candidate<COMPACT ? LSD_MODE_TILEC : LSD_MODE_TILE, SVC_WIN_REUSE(COMPACT), SVC_LEAN_SAMPLER(COMPACT)>(m, wwin, &wtag, cull_tab, cull, dirs, ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum);
 #endif
 		if (lane == 0) {
 			sl.ptx = xs; sl.pty = ys; sl.best = wkey; sl.ex = ex0; sl.ey = ey0; sl.steps = st_sum;
@@ -261,9 +261,9 @@ __device__ __attribute__((noinline)) void svc_help_remote(const void *kargs, uin
 #ifdef SMH_LSD_WDEBUG
 		unsigned long long sprof[8] = {0, 0, 0, 0, 0, 0, 0, 0}, slast = __builtin_amdgcn_s_memtime(), uprof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 		uint32_t n_units = 0;
-		seq_cast_candidate<COMPACT ? LSD_MODE_TILEC : LSD_MODE_TILE, SVC_WIN_REUSE(COMPACT)>(m, wwin, &wtag, cull_tab, cull, dirs, ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum, sprof, slast, uprof, n_units);
+		seq_cast_candidate<COMPACT ? LSD_MODE_TILEC : LSD_MODE_TILE, SVC_WIN_REUSE(COMPACT), SVC_LEAN_SAMPLER(COMPACT)>(m, wwin, &wtag, cull_tab, cull, dirs, ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum, sprof, slast, uprof, n_units);
 #else
-		seq_cast_candidate<COMPACT ? LSD_MODE_TILEC : LSD_MODE_TILE, SVC_WIN_REUSE(COMPACT)>(m, wwin, &wtag, cull_tab, cull, dirs, ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum);
+		seq_cast_candidate<COMPACT ? LSD_MODE_TILEC : LSD_MODE_TILE, SVC_WIN_REUSE(COMPACT), SVC_LEAN_SAMPLER(COMPACT)>(m, wwin, &wtag, cull_tab, cull, dirs, ray_off, max_gap, px, py, xs, ys, wkey, ex0, ey0, st_sum);
 #endif
 		++n_cast;
 		t_cast += __builtin_amdgcn_s_memtime() - t_c0;

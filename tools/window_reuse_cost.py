@@ -10,7 +10,8 @@ after it (so the rounds interleave), every figure a fresh child process under `t
 fails or runs out of time ends the job, nothing is started after it.
   (1) once, where --wprof names `make wprof` libraries: tools/svc_rate.py over 256 x 1080p at depth 12, as the pipeline runs it and
       with no help (RATE_FLAGS=9: the owner casts every candidate, which is what tools/window_reuse_count.py predicts fills for):
-      s_window_fill, setup, search and help cycles per frame, window fills per frame
+      s_window_fill, setup, search and help cycles per frame, window fills per frame, and the split inside the units (first batches,
+      long rays, end points)
   (2) the headline: `value` of the default bench.py run (config 2)
   (3) `bench.py --config 3`, the real-samples leg of a --full run; once: `bench.py --config 4` on one GPU
 The verdict: (2) every round of a build above every round of the parent; (3) a loss is every round below every round of the parent.
@@ -89,7 +90,8 @@ def main():
                       dict(SVC_RATE_WPROF="1", RATE_SEARCH="frame", RATE_FLAGS=flags))
             p, st = j["scan_profile_cycles_per_frame"], j["search_service"]
             rec[leg] = dict(s_window_fill=p["s_window_fill"], s_cull_scan=p["s_cull_scan"], setup=p["setup"], units=p["units"], verdict=p["verdict"], rounds=p["rounds"],
-                            window_fills=p.get("window_fills"), cast_by_owner=p.get("cast_by_owner"), n_units=p.get("n_units"), cycles_per_unit=p.get("cycles_per_unit"), search=st["cycles_per_frame_by_phase"]["search"],
+                            window_fills=p.get("window_fills"), cast_by_owner=p.get("cast_by_owner"), n_units=p.get("n_units"), cycles_per_unit=p.get("cycles_per_unit"),
+                            u_first_batches=p.get("u_first_batches"), u_long_rays=p.get("u_long_rays"), u_end_points=p.get("u_end_points"), search=st["cycles_per_frame_by_phase"]["search"],
                             help_cycles_per_frame=st["help_cycles_per_frame"], frames_per_s=j["frames_per_s"], equal=j["slots_equal_plain_run"])
             print("wprof %s %s: %s" % (n, leg, json.dumps(rec[leg])), flush=True)
         state["wprof"][n] = rec
