@@ -1107,6 +1107,44 @@ SMHV_API int smhv_feed_frame(smhv_ctx *ctx, smhv_feed *feed, const smhv_line *li
  * smhv_feed_frame, the capacity measured with the view's size; SMHV_E_INVALID for an unknown map_source. */
 SMHV_API int smhv_feed_frame_view(smhv_ctx *ctx, smhv_feed *feed, const smhv_line *lines, uint32_t n_lines, const double *mpx, const uint32_t minimap[4],
                                   uint32_t flags, uint32_t map_source);
+/* ---- remote-viewer feed: map tiles ------------------------------------------------------------------------------------------
+ * A Map is the whole picture and is sent whenever one pixel differs.  smhv_batch_feed_tiles / smhv_feed_frame_tiles are
+ * smhv_batch_feed / smhv_feed_frame with one more message, MapTiles, that carries only the tiles of the map that changed.  THE
+ * REFERENCE HAS NO SUCH MESSAGE (its web server sends Maps only): a client that turns tiles on must know id 6; the calls without
+ * tiles are unchanged and never send it.  The rule, for host and device, stands once in csrc/smh_maptiles.h.
+ * Tile grid: a map of w x h pixels is cut into tiles of 64 x 16 pixels counted from its pixel (0, 0): tiles_x = ceil(w / 64),
+ * tiles_y = ceil(h / 16), tile index t = ty * tiles_x + tx; tiles of the last column and row are clipped, cw = min(64, w - 64 tx),
+ * ch = min(16, h - 16 ty).  A tile's bytes are its ch rows of cw RGBA pixels, tightly packed, then zero bytes up to the next
+ * multiple of 16.
+ * MapTiles, all fields little endian:
+ *    0  u16  06 00                                  14  u32  n, the number of tiles
+ *    2  u32  w                                      18  u32  base_crc: the CRC-32 of the map these tiles are applied to
+ *    6  u32  h                                      22  u32  crc: the CRC-32 of the map after they are applied
+ *   10  u16  64                                     26  n x u32 tile indices, strictly ascending, then zero bytes up to a multiple of 16
+ *   12  u16  16                                     26 + pad16(4 n)  the n tiles in that order, each padded as above
+ * Messages start at offsets = 6 (mod 16) as before, so the index list and every tile start on a 16-byte boundary.  Length
+ * L = 26 + pad16(4 n) + the sum of pad16(4 cw ch) over the tiles.  A tile is in the list iff any of its bytes differs from the same
+ * bytes of the base map; alpha counts.
+ * What a frame sends: an open SMHV_FRAME_OK frame sends UpdateState and Markers exactly as before, and between them nothing when its
+ * CRC equals the texture's CRC as the frame finds it (the rule above, unchanged: equal CRCs count as equal maps), MapTiles against
+ * its base when it has a base and L < 10 + 4 w h, otherwise the Map, byte for byte the message above.  The base of a frame is the map
+ * of the nearest earlier open OK frame of the same call; the base of the first such frame of a call is the feed's KEPT MAP, usable
+ * iff the feed has a stored CRC, that CRC equals the kept map's CRC, and the kept map's w, h equal this call's.  After a call the kept
+ * map is the map of the last CONSUMED open OK frame (a call that consumed none leaves it unchanged); the stored CRC moves exactly as
+ * before.  Hence: smhv_feed_reset leads to a Map; a call without tiles that sent a Map makes the kept map stale, so the next tile
+ * call sends a Map, and one that sent none leaves it usable; a capacity cut keeps the map of the frame where the call stopped;
+ * another map size leads to a Map.  Every tile changed always gives L > 10 + 4 w h, so a wholly new picture goes out as a Map and
+ * one frame's worst case in the buffer is the one above.  Entries: kind = 6, length = L, crc = the frame's CRC.  The header is
+ * unchanged: n_maps counts Map messages only.
+ * flags must be 0: SMHV_FEED_SNAPSHOT is SMHV_E_INVALID (a snapshot has no base).  The source is the ui_map only; a debug view as the
+ * Map is out of scope here (no map_source).  Every other check, its order and its text are smhv_batch_feed's / smhv_feed_frame's; a
+ * failed call enqueues nothing, changes nothing and allocates nothing.  Tile calls and calls without tiles may alternate on one feed
+ * and chain as before.  The kept map and the per-frame tile bitmaps are device memory of the feed, made by the first tile call and
+ * freed by smhv_feed_destroy.  No host round trip inside a call. */
+#define SMHV_WEB_MAP_TILES 6u
+SMHV_API int smhv_batch_feed_tiles(smhv_batch *b, smhv_feed *feed, uint32_t first, uint32_t n, uint32_t flags, void *stream);
+SMHV_API int smhv_feed_frame_tiles(smhv_ctx *ctx, smhv_feed *feed, const smhv_line *lines, uint32_t n_lines, const double *mpx, const uint32_t minimap[4],
+                                   uint32_t flags);
 /* The rest of the protocol, host only (no device needed).  Encoders: *len <- the message's length; the message is written when
  * out != NULL and cap >= *len (out == NULL asks for the length), SMHV_E_INVALID when cap is too small.
  *   Markers (lib.rs:142-152): 02 00, custom as a byte, n as u32, n x 4 f32.

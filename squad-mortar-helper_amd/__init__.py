@@ -27,5 +27,5 @@ from .render import DebugOptions, ocr_text_runs, probe_points, probe_text, rust_
 from ._lib import DEBUG_DRAW_PROBES, DEBUG_MINIMAP_CAPTION, MAX_PROBES, TEXT_MAP_COORDS, TEXT_MAX_BYTES, TEXT_MAX_LINES, TEXT_MAX_RUNS  # noqa: F401
 from ._lib import LAYER_MINIMAP_BOUNDS, PRIM_FOREGROUND, PRIM_LINE, PRIM_RECT, PRIM_SHIFT1, RENDER_MAX_PRIMS  # noqa: F401
 from ._lib import RENDER_BOUNDS_OFFSET, RENDER_HEIGHTMAP, RENDER_MARKERS  # noqa: F401
-from .web import WebFeed, encode_fit, encode_heightmap, encode_markers, parse_interaction  # noqa: F401
-from ._lib import FEED_SNAPSHOT, WEB_FIT_TO_MINIMAP, WEB_HEIGHTMAP, WEB_MAP, WEB_MARKERS, WEB_UPDATE_STATE  # noqa: F401
+from .web import MapTexture, WebFeed, decode_map_tiles, encode_fit, encode_heightmap, encode_markers, parse_interaction  # noqa: F401
+from ._lib import FEED_SNAPSHOT, WEB_FIT_TO_MINIMAP, WEB_HEIGHTMAP, WEB_MAP, WEB_MAP_TILES, WEB_MARKERS, WEB_UPDATE_STATE  # noqa: F401

@@ -32,6 +32,7 @@ LAYER_MINIMAP_BOUNDS = 1                   # smhv_render_layers.flags
 RENDER_FORM_RULE, RENDER_FORM_GATHER, RENDER_FORM_STAGED, RENDER_FORM_TABLE = 0, 1, 2, 3   # smhv_debug_render_form
 
 WEB_MAP, WEB_MARKERS, WEB_UPDATE_STATE, WEB_HEIGHTMAP, WEB_FIT_TO_MINIMAP = 1, 2, 3, 4, 5   # the web server's event ids (SMHV_WEB_*)
+WEB_MAP_TILES = 6                          # the feed's own message (smhv_batch_feed_tiles / smhv_feed_frame_tiles): the reference has none
 FEED_SNAPSHOT = 1                          # smhv_batch_feed / smhv_feed_frame flags: what a client that has just connected gets
 
 E_INVALID, E_GEOMETRY, E_HIP, E_NO_DEVICE, E_STATE = -1, -2, -3, -4, -5
@@ -476,6 +477,8 @@ SIGNATURES = {
     "smhv_debug_feed_gray_form": (C.c_int, [C.c_uint32]),
     "smhv_batch_feed_view": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "smhv_feed_frame_view": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32]),
+    "smhv_batch_feed_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "smhv_feed_frame_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_uint32]),
     "smhv_reach_defaults": (C.c_int, [C.POINTER(ReachOptionsStruct)]),
     "smhv_reach_thresholds": (C.c_int, [C.POINTER(C.c_double)]),
     "smhv_batch_reach": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(ReachOptionsStruct), C.c_void_p,

@@ -511,6 +511,13 @@ class FrameBatch:
         else:
             L.check(self._lib.smhv_batch_feed_view(self._b, feed._f, first, n, flags, int(map_source), C.c_void_p(stream)))
 
+    def feed_tiles(self, feed, first=0, n=None, stream=0):
+        """feed() with map tiles (smhv_batch_feed_tiles): a frame whose ui_map differs from the map before it in a few 64 x 16
+        tiles sends a MapTiles message (web.decode_map_tiles, web.MapTexture) in the Map's place.  The ui_map only, no snapshot.
+        Asynchronous; feed.read() waits for it."""
+        n = self.max_frames - first if n is None else n
+        L.check(self._lib.smhv_batch_feed_tiles(self._b, feed._f, first, n, 0, C.c_void_p(stream)))
+
     def video(self, source, pixels, first=0, n=None, out_ptr=None, layout=None, stream=None):
         """Frames [first, first + n) of what the batch shows a viewer as NV12 / I420 video frames on `stream` (smhv_batch_video).
         source: "render" (the render slab at the most recent render's window size) or "ui_map" (the ui_map at the ROI's size; a grey

@@ -16,13 +16,20 @@ struct smhv_feed {
 	hipEvent_t ev_last = nullptr;                             // the feed's most recent call: the next one is ordered behind it
 	bool used = false;
 	smhv_frame_result *d_rec = nullptr, *h_rec = nullptr;     // smhv_feed_frame: the call's record (device, pinned staging)
+	// map tiles (smh_feedtiles.inc), made by the first tile call: the kept map (room for any map the feed accepts), its state,
+	// the plan's words for the copies, per frame the base, the sums and the MapTiles items; the tile bitmaps grow with the geometry
+	uint8_t *d_kept = nullptr;
+	uint32_t *d_kstate = nullptr, *d_tctl = nullptr, *d_tbase = nullptr, *d_tinfo = nullptr;
+	FeedTileItem *d_titems = nullptr;
+	uint2 *d_tbits = nullptr;
+	size_t tbits_words = 0;
 };
 
 extern "C" SMHV_API void smhv_feed_destroy(smhv_feed *f) {
 	if (!f) return;
 	if (f->ctx) (void)hipSetDevice(f->ctx->device);
 	(void)hipDeviceSynchronize();
-	void *ptrs[] = {f->d_bytes, f->d_header, f->d_entries, f->d_state, f->d_raw, f->d_tab, f->d_maps, f->d_rec, f->d_view};
+	void *ptrs[] = {f->d_bytes, f->d_header, f->d_entries, f->d_state, f->d_raw, f->d_tab, f->d_maps, f->d_rec, f->d_view, f->d_kept, f->d_kstate, f->d_tctl, f->d_tbase, f->d_tinfo, f->d_titems, f->d_tbits};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	if (f->h_rec) (void)hipHostFree(f->h_rec);
@@ -103,8 +110,9 @@ static FeedSrc feed_src_ui(const Geom &g, const uint8_t *ui) {
 	return v;
 }
 
-// The call's kernels on `s`, behind the feed's previous call (after feed_check).  v / res: the call's first frame.
-static int feed_enqueue(smhv_feed *f, const FeedSrc &v, const smhv_frame_result *res, uint32_t first, uint32_t n, uint32_t flags, hipStream_t s) {
+// `s` behind the feed's previous call, the CRC's tables for the call's source, and the call's FeedRun (after feed_check).
+// v / res: the call's first frame.
+static int feed_prepare(smhv_feed *f, const FeedSrc &v, const smhv_frame_result *res, uint32_t first, uint32_t n, uint32_t flags, hipStream_t s, FeedRun *out) {
 	if (f->used) HIPCHK(hipStreamWaitEvent(s, f->ev_last, 0));
 	const bool image = v.mode == SMH_RND_SRC_RGBA;
 	// the CRC's description of the message: an image is rows of SMH_FEED_IMAGE_ROW dwords, its lead-in of zeros included
@@ -126,12 +134,22 @@ static int feed_enqueue(smhv_feed *f, const FeedSrc &v, const smhv_frame_result 
 	r.capacity = f->capacity;
 	r.raw = f->d_raw; r.tab = f->d_tab; r.state = f->d_state;
 	r.header = f->d_header; r.entries = f->d_entries; r.bytes = f->d_bytes; r.maps = f->d_maps;
+	*out = r;
+	return SMHV_OK;
+}
+
+// The call's kernels on `s`, behind the feed's previous call (after feed_check).  v / res: the call's first frame.
+static int feed_enqueue(smhv_feed *f, const FeedSrc &v, const smhv_frame_result *res, uint32_t first, uint32_t n, uint32_t flags, hipStream_t s) {
+	FeedRun r;
+	const int rc = feed_prepare(f, v, res, first, n, flags, s, &r);
+	if (rc) return rc;
+	const bool image = v.mode == SMH_RND_SRC_RGBA;
 	if (v.mode == SMH_RND_SRC_UI) HIPCHK(launch_feed(r, s));
 	else if (!image) HIPCHK(launch_feed_view(r, v.mode, s));
 	else {
 		FeedRun c = r;                                        // k_map_crc's: the rows start `lead` dwords in front of the image
 		c.ui = v.base - 4ull * v.lead; c.ui_pitch = 4ull * SMH_FEED_IMAGE_ROW; c.ui_stride = 0;
-		c.w = cw; c.h = ch; c.xoff = 0u; c.quads = cquads;
+		c.w = SMH_FEED_IMAGE_ROW; c.h = (uint32_t)(((uint64_t)v.w * v.h + v.lead) / SMH_FEED_IMAGE_ROW); c.xoff = 0u; c.quads = SMH_FEED_IMAGE_ROW / 4u;
 		HIPCHK(launch_feed_image(c, r, s));
 	}
 	HIPCHK(hipEventRecord(f->ev_last, s));

@@ -755,4 +755,30 @@ hipError_t launch_feed_view(const FeedRun &r, uint32_t src_mode, hipStream_t s);
 hipError_t launch_feed_image(const FeedRun &crc, const FeedRun &r, hipStream_t s);
 void feed_set_gray_form(uint32_t form);   // diagnostic: 0 = the rule, 4 = a plane's CRC with four lookups per message dword always
 
+// ---- the feed's map tiles (smh_feedtiles.hip; smhv_batch_feed_tiles / smhv_feed_frame_tiles; the rule: smh_maptiles.h) --------------
+// k_map_crc (smh_feed.hip) runs as it is; behind it, on the same stream and with no host round trip:
+//   k_tiles_base   every frame's base: the nearest earlier open frame of the call, the feed's kept map, or none
+//   k_tiles_diff   one bit per tile of every open frame that differs from its base, read where both maps lie
+//   k_tiles_plan   k_feed_plan's scans, capacity cut and frames_done with a Map slot whose size and kind differ per frame
+//   k_tiles_copy   persistent workgroups over (MapTiles message, 32 tiles): the index list and the padded tiles
+//   k_feed_maps    (smh_feed.hip, as it is) the full Maps of the same call
+//   k_tiles_keep   the last consumed open frame's map and CRC into the feed
+__global__ void k_map_crc(FeedRun r);
+__global__ void k_feed_maps(FeedRun r);
+#define SMH_TILES_BASE_NONE 0xFFFFFFFFu  // a frame's base: none (it can only send a Map or nothing)
+#define SMH_TILES_BASE_KEPT 0xFFFFFFFEu  // ... the feed's kept map; anything else: the index of a frame of the call
+struct FeedTileItem { uint64_t dst; uint32_t frame, n; };   // a MapTiles message of the call: its offset in the buffer, frame (index in the call), tiles
+struct FeedTilesRun {
+	FeedRun r;                           // the call as smhv_batch_feed would make it (flags 0)
+	uint8_t *kept;                       // the kept map: w x h RGBA, tightly packed
+	uint32_t *kstate;                    // {valid, crc, w, h} of the kept map
+	uint32_t *ctl;                       // {MapTiles messages of the call, the frame to keep (SMH_TILES_BASE_NONE: none), its CRC}
+	uint32_t *base;                      // n: SMH_TILES_BASE_* or a frame of the call
+	uint32_t *info;                      // 2 n: per frame the tiles that differ and the sum of their padded bytes (zeroed by the launcher)
+	uint2 *bits;                         // n x words: per 32 tiles {the bits, the padded bytes of the set ones}
+	FeedTileItem *items;                 // n
+	uint32_t words;                      // 32-tile words of a frame's bitmap
+};
+hipError_t launch_feed_tiles(const FeedTilesRun &t, hipStream_t s);
+
 }  // namespace smh

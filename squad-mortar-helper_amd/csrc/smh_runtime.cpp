@@ -33,6 +33,7 @@
 #include "smh_kernels.h"
 #include "smh_glyph_rule.h"
 #include "smh_grid.h"
+#include "smh_maptiles.h"
 
 using namespace smh;
 
@@ -3487,6 +3488,7 @@ extern "C" SMHV_API int smhv_heightmap_overlay(smhv_ctx *c, const smhv_heightmap
 
 #include "smh_render.inc"
 #include "smh_feed.inc"
+#include "smh_feedtiles.inc"
 #include "smh_labels.inc"
 #include "smh_debugtext.inc"
 #include "smh_reach.inc"

@@ -425,6 +425,14 @@ class HipVision:
         else:
             L.check(self._lib.smhv_feed_frame_view(self._ctx, feed._f, ln.ctypes.data if len(ln) else None, len(ln), m, mm, flags, int(map_source)))
 
+    def feed_frame_tiles(self, feed, lines, mpx=None, minimap=None):
+        """feed_frame() with map tiles (smhv_feed_frame_tiles): when the current ui_map differs from the one the feed kept in a few
+        64 x 16 tiles, a MapTiles message (web.decode_map_tiles, web.MapTexture) goes out in the Map's place.  The ui_map only."""
+        ln = np.ascontiguousarray(lines if lines is not None else np.zeros((0, 4)), np.float32).reshape(-1, 4)
+        m = C.byref(C.c_double(float(mpx))) if mpx is not None else None
+        mm = _minimap_arg(minimap)
+        L.check(self._lib.smhv_feed_frame_tiles(self._ctx, feed._f, ln.ctypes.data if len(ln) else None, len(ln), m, mm, 0))
+
     def debug_marker_table(self):
         bits = np.empty((1 << 24) // 32, np.uint32)
         L.check(self._lib.smhv_debug_marker_table(self._ctx, bits.ctypes.data))

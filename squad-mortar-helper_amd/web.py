@@ -4,6 +4,8 @@ HipVision.feed_frame take map_source = a VIEW_* of _lib: that debug view is hash
 (smhv_batch_feed_view / smhv_feed_frame_view; src/ui/map.rs:210).  Transport is the caller's: a
 message from WebFeed.read() or an encoder is what the reference hands its websocket as one binary frame."""
 import ctypes as C
+import struct
+import zlib
 
 import numpy as np
 
@@ -58,6 +60,77 @@ class WebFeed:
         p = [C.c_void_p() for _ in range(3)]
         L.check(self._lib.smhv_feed_ptrs(self._f, *[C.byref(x) for x in p]))
         return tuple(x.value or 0 for x in p)
+
+
+TILE_W, TILE_H = 64, 16                      # the MapTiles grid (include/smh_vision_hip.h, "remote-viewer feed: map tiles")
+
+
+def _pad16(n):
+    return (n + 15) & ~15
+
+
+def decode_map_tiles(message):
+    """A MapTiles message (FrameBatch.feed_tiles / HipVision.feed_frame_tiles) -> (w, h, base_crc, crc, [(index, tile uint8
+    [ch, cw, 4])]): the tiles of the map that differ from the map whose CRC-32 is base_crc, clipped at the map's right and bottom
+    edge; applied to that map they give the map whose CRC-32 is crc.  ValueError for anything that is not a whole, well-formed
+    MapTiles message."""
+    m = bytes(message)
+    if len(m) < 26:
+        raise ValueError("MapTiles: %d bytes" % len(m))
+    kind, w, h, tw, th, n, base_crc, crc = struct.unpack_from("<HIIHHIII", m, 0)
+    if kind != L.WEB_MAP_TILES or (tw, th) != (TILE_W, TILE_H):
+        raise ValueError("MapTiles: id %d, tiles of %d x %d" % (kind, tw, th))
+    tiles_x, tiles_y = -(-w // TILE_W), -(-h // TILE_H)
+    at = 26 + _pad16(4 * n)
+    if len(m) < at:
+        raise ValueError("MapTiles: %d bytes, %d indices" % (len(m), n))
+    idx = struct.unpack_from("<%dI" % n, m, 26)
+    if any(b <= a for a, b in zip(idx, idx[1:])) or (n and idx[-1] >= tiles_x * tiles_y):
+        raise ValueError("MapTiles: the indices are not strictly ascending tiles of a %d x %d map" % (w, h))
+    out = []
+    for t in idx:
+        ty, tx = divmod(t, tiles_x)
+        cw, ch = min(TILE_W, w - TILE_W * tx), min(TILE_H, h - TILE_H * ty)
+        nb = 4 * cw * ch
+        if len(m) < at + _pad16(nb):
+            raise ValueError("MapTiles: the message ends inside tile %d" % t)
+        out.append((t, np.frombuffer(m, np.uint8, nb, at).reshape(ch, cw, 4)))
+        at += _pad16(nb)
+    if at != len(m):
+        raise ValueError("MapTiles: %d bytes behind the last tile" % (len(m) - at))
+    return w, h, base_crc, crc, out
+
+
+class MapTexture:
+    """The client half of the tile feed: the map a viewer holds.  apply(message) takes a Map or a MapTiles message as
+    WebFeed.read() hands them out; a MapTiles whose base_crc is not the texture's CRC-32 is refused (ValueError) and changes
+    nothing.  map: uint8 [h, w, 4] or None."""
+
+    def __init__(self):
+        self.map = None
+
+    def crc(self):
+        """CRC-32 of the texture's bytes, or None before the first Map."""
+        return None if self.map is None else zlib.crc32(self.map.tobytes()) & 0xFFFFFFFF
+
+    def apply(self, message):
+        m = bytes(message)
+        (kind,) = struct.unpack_from("<H", m, 0)
+        if kind == L.WEB_MAP:
+            w, h = struct.unpack_from("<II", m, 2)
+            if len(m) != 10 + 4 * w * h:
+                raise ValueError("Map: %d bytes for %d x %d" % (len(m), w, h))
+            self.map = np.frombuffer(m, np.uint8, 4 * w * h, 10).reshape(h, w, 4).copy()
+            return
+        w, h, base_crc, crc, tiles = decode_map_tiles(m)
+        if self.map is None or self.map.shape != (h, w, 4) or self.crc() != base_crc:
+            raise ValueError("MapTiles against a map with CRC %08x: the texture's is %s" % (base_crc, "none" if self.map is None else "%08x" % self.crc()))
+        tiles_x = -(-w // TILE_W)
+        for t, px in tiles:
+            ty, tx = divmod(t, tiles_x)
+            self.map[TILE_H * ty:TILE_H * ty + px.shape[0], TILE_W * tx:TILE_W * tx + px.shape[1]] = px
+        if self.crc() != crc:
+            raise ValueError("MapTiles: the map after the tiles has CRC %08x, the message says %08x" % (self.crc(), crc))
 
 
 def _encode(call):
