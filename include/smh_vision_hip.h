@@ -1790,6 +1790,190 @@ SMHV_API int smhv_batch_grid_refs_ptr(smhv_batch *b, void **d_grid_refs);
 SMHV_API int smhv_grid_refs(smhv_ctx *ctx, const smhv_line *lines, uint32_t n, const double *mpx, const uint32_t minimap[4], const smhv_heightmap *hm,
                             const smhv_render_options *ropt, const smhv_grid_options *opt, smhv_grid_ref *out);
 
+/* ---- ballistics: firing solutions and a reach map for a caller-supplied weapon ------------------------------------------------------
+ * "firing solutions", "reach map" and "terrain clearance" assume one weapon (the reference's mortar: one muzzle velocity, the high
+ * arc, NATO mils).  This family takes the weapon from the caller: a muzzle velocity, a gravity, the arc it is laid on, the unit its
+ * sight reads, the limits of its mount, a minimum range and a dispersion cone; and it gives, beside the elevation, what a firing
+ * table carries: time of flight, the arc's highest point, the angle of fall.  The library ships NO weapon table (as it ships no glyph
+ * shapes); smhv_weapon_defaults is the reference's mortar and nothing else.  The reference has no such code; the solution's
+ * discriminant is squadex::milliradians::calc's.  Every operation below is ONE IEEE f64 operation, left to right, unfused; the only
+ * function that is not correctly rounded everywhere is the atan of the elevation itself.  Everything else a device gives is bit-equal
+ * to what smhv_ballistic_solve gives on the host.
+ * The weapon in the rule's terms (smhv_weapon_thresholds, computed on the host once per call, never on the device):
+ *   V = velocity, g = gravity, V2 = pow(V, 2.0), V4 = pow(V, 4.0) by the C library's pow (how "firing solutions" documents its
+ *   constants; for smhv_weapon_defaults they ARE those constants, 0x1.79602562a02dfp+13 and 0x1.1626291c459a8p+27, bit for bit).
+ *   U = the unit's size of a degree: 360.0 / 6400.0 (SMHV_ANGLE_MILS6400), 360.0 / 6000.0 (_MILS6000); _DEGREES has none.
+ *   rad(e) of an angle e in the weapon's unit = (e * U) * (pi / 180.0), in degrees e * (pi / 180.0), pi / 180.0 the f64 constant
+ *   0x1.1df46a2529d39p-6.  tanlim(e) = +inf when rad(e) >= 0x1.921fb54442d18p+0 (a quarter turn or more: no limit), -inf when
+ *   rad(e) <= -0x1.921fb54442d18p+0, else the C library's tan(rad(e)).
+ *   t_min = tanlim(elev_min), t_max = tanlim(elev_max); B_j = tanlim(elev_min + ((elev_max - elev_min) * (double)(j + 1)) / 8.0),
+ *   j = 0 .. 6: eight bands of equal width in the weapon's unit; t_disp = tan(dispersion).
+ * A solution from (m, alt) = (range, altitude of the target over the muzzle), both arcs (smhv_ballistic_solve, k_ballistic_lines):
+ *   disc = V4 - g * (g * (m * m) + 2.0 * alt * V2);  s = sqrt(disc);  gm = g * m;
+ *   T_hi = (V2 + s) / gm (arc[SMHV_ARC_HIGH]),  T_lo = (V2 - s) / gm (arc[SMHV_ARC_LOW]); per arc, with its T and tt = T * T:
+ *   elevation = atan(T) * (180.0 / pi), then / U for the mil units (for MILS6400 this is calc's expression, operation for operation);
+ *   tof   = (m * sqrt(1.0 + tt)) / V                     seconds;
+ *   apex  = (V2 * tt) / ((1.0 + tt) * (2.0 * g))         metres above the muzzle; 0.0 when T <= 0.0 (the arc only falls);
+ *   fall  = (gm * (1.0 + tt)) / V2 - T                   the tangent of the angle of fall (positive: descending at the target);
+ *   along = fabs(((m * (1.0 - (gm * T) / V2)) * (1.0 + tt)) / fall) * t_disp   the along-range half width at the target: the range's
+ *           derivative by the elevation, dm/dT = m (1 - g m T / V2) / fall and dT = (1 + tt) d(angle), times the cone's half angle
+ *           taken as its tangent;  cross = m * t_disp, the cross-range half width (one per solution, not per arc).
+ *   status: SMHV_BAL_OUT_OF_RANGE iff !(disc >= 0.0) (disc < 0 or NaN: exactly the reach map's rule); SMHV_BAL_BELOW_MIN_RANGE iff
+ *   m < range_min; and only without OUT_OF_RANGE: SMHV_BAL_ELEV_LOW iff !(T >= t_min), SMHV_BAL_ELEV_HIGH iff !(t_max >= T).  The
+ *   mount's limits are decided on T, never on the elevation.  band = the number of j with T >= B_j (0 .. 7).
+ *   Edges, none of them a special case -- IEEE arithmetic decides: OUT_OF_RANGE makes s NaN and with it T and every number of both
+ *   arcs (band 0).  disc == 0.0: both arcs are equal in every field.  NaN in m or alt, m or alt = +inf: OUT_OF_RANGE; alt = -inf:
+ *   T_hi = +inf, T_lo = -inf.  m == 0.0: gm = 0.0, T_hi = +inf (elevation a quarter turn; tof, apex, fall and along NaN), T_lo
+ *   = (V2 - s) / 0.0 is an infinity or, where s == V2, NaN -- and a NaN T that is not OUT_OF_RANGE has ELEV_LOW and ELEV_HIGH both.
+ *   A target far enough below makes T_lo negative: a negative elevation, apex 0.0.
+ * smhv_weapon_check refuses (SMHV_E_INVALID): a wrong size, an unknown arc or unit, velocity or gravity not finite or <= 0,
+ *   elev_min or elev_max not finite, elev_min > elev_max, range_min or dispersion negative or not finite.
+ * Lines (smhv_batch_ballistics / smhv_ballistic_lines): source, meters and alt_delta of a line are smhv_firing_solutions' (the same
+ *   device function is called); dir[0] fires from p0 at p1 with alt = alt_delta, dir[1] the reverse with -alt_delta; source NONE leaves
+ *   the record zero but for `source`.  A record is 256 bytes.
+ * Map (smhv_batch_ballistic_map / smhv_ballistic_map): target, origin, source, m and alt of window pixel (X, Y) are "reach map"'s, word
+ *   for word.  Per pixel, T = the root of the WEAPON'S arc (smhv_weapon.arc):
+ *   class byte   0 nothing (no origin, source NONE, a coordinate not finite, m NaN); 1 SMHV_BMAP_OUT_OF_RANGE; 2 _BELOW_MIN_RANGE;
+ *                3 _ELEV_LOW; 4 _ELEV_HIGH (the first of these that the status has, in this order); else 5 + band (SMHV_BMAP_BAND0).
+ *     | 0x80     an isochrone (SMHV_BMAP_ISO), only when iso_s > 0 and the class is not 0: b = floor(tof / iso_s); set iff b is not
+ *                NaN and differs from b of pixel (X + 1, Y) or of pixel (X, Y + 1), each evaluated by the same rule even where it lies
+ *                outside the window.  A neighbour whose source differs from this pixel's, whose class would be 0 or whose b is NaN
+ *                does not count ("reach map"'s ring rule on the time of flight).
+ *   tof plane    (SMHV_BMAP_TOF) f32 per pixel: (float)tof, the f64 value rounded once, where the class is 2 or more; NaN where it
+ *                is 0 or 1 (no solution).
+ *   paint        (SMHV_BMAP_PAINT) "reach map"'s integer blend with pal[class - 1], then on an isochrone pixel with iso.
+ *   summary      one smhv_ballistic_map_result per frame: valid, origin as "reach map"; count[c - 1] = window pixels of class c
+ *                (isochrone bit ignored), c = 1 .. 12; iso = pixels with the bit; n_tof = window pixels of class >= 5 whose tof is
+ *                not NaN, tof_min / tof_max = the least and greatest tof among them (0.0 when n_tof == 0); source_mask as "reach map". */
+#define SMHV_ARC_HIGH 0u               /* smhv_weapon.arc; also the index into smhv_ballistic_solution.arc */
+#define SMHV_ARC_LOW 1u
+#define SMHV_ANGLE_MILS6400 0u         /* smhv_weapon.unit */
+#define SMHV_ANGLE_MILS6000 1u
+#define SMHV_ANGLE_DEGREES 2u
+#define SMHV_BAL_OUT_OF_RANGE 1u       /* smhv_ballistic_arc.status */
+#define SMHV_BAL_BELOW_MIN_RANGE 2u
+#define SMHV_BAL_ELEV_LOW 4u
+#define SMHV_BAL_ELEV_HIGH 8u
+#define SMHV_BMAP_PAINT 1u             /* smhv_ballistic_options.flags: tint the render slab (per call: implied by rgba_inout) */
+#define SMHV_BMAP_CLASSES 2u           /*   ... write the class bytes (per call: implied by classes) */
+#define SMHV_BMAP_TOF 4u               /*   ... write the time-of-flight plane (per call: implied by tof) */
+#define SMHV_BMAP_OUT_OF_RANGE 1u      /* the class byte */
+#define SMHV_BMAP_BELOW_MIN_RANGE 2u
+#define SMHV_BMAP_ELEV_LOW 3u
+#define SMHV_BMAP_ELEV_HIGH 4u
+#define SMHV_BMAP_BAND0 5u
+#define SMHV_BMAP_ISO 0x80u
+typedef struct {
+	uint32_t size;                       /*  0: sizeof(smhv_weapon) == 80 */
+	uint32_t arc;                        /*  4: SMHV_ARC_*: the arc the weapon is laid on */
+	uint32_t unit;                       /*  8: SMHV_ANGLE_* */
+	uint32_t reserved0;                  /* 12: 0 */
+	double velocity;                     /* 16: m/s */
+	double gravity;                      /* 24: m/s^2, the weapon's gravity scale multiplied in */
+	double elev_min, elev_max;           /* 32, 40: the mount's limits, in the weapon's unit */
+	double range_min;                    /* 48: metres */
+	double dispersion;                   /* 56: the cone's half angle, radians; 0 = none */
+	uint32_t reserved[4];                /* 64: 0 */
+} smhv_weapon;
+typedef struct {
+	double v, g, v2, v4;                 /*  0 */
+	double t_min, t_max;                 /* 32 */
+	double band[7];                      /* 48: B_j */
+	double t_disp;                       /* 104 */
+	double range_min;                    /* 112 */
+	double unit_deg;                     /* 120: U; 1.0 for SMHV_ANGLE_DEGREES */
+	uint32_t arc, unit;                  /* 128 */
+} smhv_weapon_rule;                      /* 136 bytes */
+typedef struct {
+	double elevation;                    /*  0: in the weapon's unit */
+	double tof;                          /*  8 */
+	double apex;                         /* 16 */
+	double fall;                         /* 24 */
+	double along;                        /* 32 */
+	uint32_t status;                     /* 40: SMHV_BAL_* */
+	uint32_t band;                       /* 44 */
+} smhv_ballistic_arc;                    /* 48 bytes */
+typedef struct {
+	double meters;                       /*  0 */
+	double alt_delta;                    /*  8: the target over the muzzle, as this direction sees it */
+	double cross;                        /* 16 */
+	uint32_t source;                     /* 24: SMHV_FIRING_NONE / _SCALES / _HEIGHTMAP (smhv_ballistic_solve: 0) */
+	uint32_t reserved;                   /* 28 */
+	smhv_ballistic_arc arc[2];           /* 32: [SMHV_ARC_HIGH], [SMHV_ARC_LOW] */
+} smhv_ballistic_solution;               /* 128 bytes */
+typedef struct { smhv_ballistic_solution dir[2]; } smhv_ballistic;   /* 256 bytes: [0] from p0 at p1, [1] from p1 at p0 */
+typedef struct {
+	uint32_t n_lines, reserved[3];       /* == the record's n_lines; lines beyond it are zero */
+	smhv_ballistic line[SMHV_MAX_LINES]; /* 16 */
+} smhv_ballistic_result;
+typedef struct {
+	uint32_t size;                       /*  0: sizeof(smhv_ballistic_options) == 96 */
+	uint32_t flags;                      /*  4: SMHV_BMAP_PAINT | _CLASSES | _TOF (0: the summary alone) */
+	uint32_t origin_mode;                /*  8: SMHV_REACH_ORIGIN_* */
+	uint32_t line;                       /* 12: _LINE_P0 / _LINE_P1: which line of the record, < SMHV_MAX_LINES */
+	float origin[2];                     /* 16: _POINT: the origin, map-ROI coordinates */
+	double iso_s;                        /* 24: seconds between isochrones; 0 = none; finite, >= 0 */
+	uint8_t pal[12][4];                  /* 32: the palette of classes 1 .. 12: R, G, B and the blend weight a */
+	uint8_t iso[4];                      /* 80 */
+	uint32_t reserved[3];                /* 84 */
+} smhv_ballistic_options;
+typedef struct {
+	uint32_t valid;                      /*  0 */
+	uint32_t source_mask;                /*  4 */
+	float origin[2];                     /*  8 */
+	uint32_t count[12];                  /* 16: classes 1 .. 12 */
+	uint32_t iso;                        /* 64 */
+	uint32_t n_tof;                      /* 68 */
+	double tof_min, tof_max;             /* 72, 80 */
+	uint32_t reserved[2];                /* 88 */
+} smhv_ballistic_map_result;             /* 96 bytes */
+typedef struct {
+	void *classes;                       /*  0: SMHV_BMAP_CLASSES: out_w * out_h bytes per frame, device memory */
+	void *tof;                           /*  8: SMHV_BMAP_TOF: out_w * out_h floats per frame, device memory */
+} smhv_ballistic_planes;                 /* 16 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(smhv_weapon) == 80 && sizeof(smhv_weapon_rule) == 136 && sizeof(smhv_ballistic_arc) == 48 && sizeof(smhv_ballistic_solution) == 128,
+              "ballistics layout");
+static_assert(sizeof(smhv_ballistic) == 256 && sizeof(smhv_ballistic_options) == 96 && sizeof(smhv_ballistic_map_result) == 96, "ballistic map layout");
+#endif
+/* Host only, no device needed.  defaults: the reference's mortar -- velocity 109.890938, gravity 9.8, SMHV_ARC_HIGH, MILS6400, elev_min
+ * 0, elev_max 1600 (a quarter turn: no limit), range_min 0, dispersion 0.  check: the list above.  thresholds: check, then the rule's
+ * terms.  solve: thresholds, then the solution of (meters, alt) with source 0. */
+SMHV_API int smhv_weapon_defaults(smhv_weapon *w);
+SMHV_API int smhv_weapon_check(const smhv_weapon *w);
+SMHV_API int smhv_weapon_thresholds(const smhv_weapon *w, smhv_weapon_rule *out);
+SMHV_API int smhv_ballistic_solve(const smhv_weapon *w, double meters, double alt, smhv_ballistic_solution *out);
+/* Host only.  Fills *opt: size, flags = PAINT, origin_mode = POINT at (0, 0), iso_s = 0 and the palette: out of range (200, 30, 30,
+ * 96), below the minimum range (120, 120, 120, 96), mount too low (150, 60, 160, 96), mount too high (90, 60, 200, 96), the bands
+ * smhv_reach_defaults' eight, iso (255, 255, 255, 160). */
+SMHV_API int smhv_ballistic_defaults(smhv_ballistic_options *opt);
+/* The weapon's solutions of the detected lines of frames [first, first + n), asynchronously on `stream`, into the batch's ballistics
+ * slab (allocated by the first call): the records as after smhv_batch_run with SMHV_STAGE_MARKERS.  hm, fopt as smhv_batch_clearance
+ * takes them.  SMHV_E_INVALID: what smhv_weapon_check and smhv_firing_solutions' options check refuse, n == 0, a range beyond the
+ * batch's capacity, a heightmap on another device.  A failed call enqueues nothing. */
+SMHV_API int smhv_batch_ballistics(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_firing_options *fopt,
+                                   const smhv_weapon *weapon, void *stream);
+SMHV_API int smhv_batch_read_ballistics(smhv_batch *b, uint32_t first, uint32_t n, smhv_ballistic_result *out);
+SMHV_API int smhv_batch_ballistics_ptr(smhv_batch *b, void **d_ballistics);
+/* The same for explicit lines, shaped like smhv_firing_solutions. */
+SMHV_API int smhv_ballistic_lines(smhv_ctx *ctx, const smhv_line *lines, uint32_t n, const double *mpx, const uint32_t minimap[4], const smhv_heightmap *hm,
+                                  const smhv_firing_options *fopt, const smhv_weapon *weapon, smhv_ballistic *out);
+/* The ballistic map of frames [first, first + n), asynchronously on `stream`: smhv_batch_reach's contract (the results cleared ahead
+ * of the kernels, PAINT behind the most recent render and SMHV_E_STATE before it or at another window, the heightmap's reference).
+ * planes (NULL: none) names the planes' device memory, each starting at the call's first frame.  SMHV_E_INVALID: what
+ * smhv_weapon_check refuses, a wrong size, unknown flags, an unknown origin_mode, line >= SMHV_MAX_LINES, an iso_s that is negative or
+ * not finite, a plane flag without its pointer, what smhv_batch_render rejects in ropt, n == 0, a range
+ * beyond the batch's capacity, a heightmap on another device.  A failed call enqueues nothing. */
+SMHV_API int smhv_batch_ballistic_map(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_render_options *ropt,
+                                      const smhv_weapon *weapon, const smhv_ballistic_options *opt, const smhv_ballistic_planes *planes, void *stream);
+SMHV_API int smhv_batch_read_ballistic_map(smhv_batch *b, uint32_t first, uint32_t n, smhv_ballistic_map_result *out);
+SMHV_API int smhv_batch_ballistic_map_ptr(smhv_batch *b, void **d_ballistic_map);
+/* The per-call path, stateless like smhv_reach_map: origin_mode must be POINT; rgba_inout, classes (out_w * out_h bytes), tof (out_w *
+ * out_h floats) and result may each be NULL, not all of them.  opt->flags is checked and otherwise not used. */
+SMHV_API int smhv_ballistic_map(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_weapon *weapon,
+                                const smhv_ballistic_options *opt, const double *mpx, const uint32_t minimap[4], uint8_t *rgba_inout, uint8_t *classes,
+                                float *tof, smhv_ballistic_map_result *result);
+
 #ifdef __cplusplus
 }
 #endif

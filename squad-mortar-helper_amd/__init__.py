@@ -16,6 +16,9 @@ from .render import RenderLayers, ctl_marker_prims, ocr_box_prims, prim, scale_b
 from .render import LabelOptions, label_lines  # noqa: F401
 from .render import ReachOptions, reach_thresholds  # noqa: F401
 from .render import ClearanceOptions  # noqa: F401
+from .render import BallisticOptions  # noqa: F401
+from . import ballistics  # noqa: F401
+from .ballistics import Weapon  # noqa: F401
 from .render import ReliefOptions, relief_light  # noqa: F401
 from .render import GridOptions, grid_ref_text  # noqa: F401
 from .render import scale_label_prims  # noqa: F401

@@ -202,6 +202,65 @@ class GridRefsResult(C.Structure):
     _fields_ = [("n_lines", C.c_uint32), ("source", C.c_uint32), ("reserved", C.c_uint32 * 2), ("ref", (GridRef * 2) * MAX_LINES)]
 
 
+ARC_HIGH, ARC_LOW = 0, 1                                               # smhv_weapon.arc; the index into BallisticSolution.arc
+ANGLE_MILS6400, ANGLE_MILS6000, ANGLE_DEGREES = 0, 1, 2                # smhv_weapon.unit
+BAL_OUT_OF_RANGE, BAL_BELOW_MIN_RANGE, BAL_ELEV_LOW, BAL_ELEV_HIGH = 1, 2, 4, 8   # smhv_ballistic_arc.status
+BMAP_PAINT, BMAP_CLASSES, BMAP_TOF = 1, 2, 4                           # smhv_ballistic_options.flags
+BMAP_OUT_OF_RANGE, BMAP_BELOW_MIN_RANGE, BMAP_ELEV_LOW, BMAP_ELEV_HIGH, BMAP_BAND0, BMAP_ISO = 1, 2, 3, 4, 5, 0x80   # the class byte
+
+
+class WeaponStruct(C.Structure):
+    """smhv_weapon: a caller-supplied weapon (80 bytes)."""
+    _fields_ = [("size", C.c_uint32), ("arc", C.c_uint32), ("unit", C.c_uint32), ("reserved0", C.c_uint32), ("velocity", C.c_double),
+                ("gravity", C.c_double), ("elev_min", C.c_double), ("elev_max", C.c_double), ("range_min", C.c_double), ("dispersion", C.c_double),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class WeaponRule(C.Structure):
+    """smhv_weapon_rule: the weapon in the rule's terms (136 bytes)."""
+    _fields_ = [("v", C.c_double), ("g", C.c_double), ("v2", C.c_double), ("v4", C.c_double), ("t_min", C.c_double), ("t_max", C.c_double),
+                ("band", C.c_double * 7), ("t_disp", C.c_double), ("range_min", C.c_double), ("unit_deg", C.c_double), ("arc", C.c_uint32),
+                ("unit", C.c_uint32)]
+
+
+class BallisticArc(C.Structure):
+    """smhv_ballistic_arc: one root of a solution (48 bytes)."""
+    _fields_ = [("elevation", C.c_double), ("tof", C.c_double), ("apex", C.c_double), ("fall", C.c_double), ("along", C.c_double),
+                ("status", C.c_uint32), ("band", C.c_uint32)]
+
+
+class BallisticSolution(C.Structure):
+    """smhv_ballistic_solution: both arcs of one (meters, alt) (128 bytes)."""
+    _fields_ = [("meters", C.c_double), ("alt_delta", C.c_double), ("cross", C.c_double), ("source", C.c_uint32), ("reserved", C.c_uint32),
+                ("arc", BallisticArc * 2)]
+
+
+class Ballistic(C.Structure):
+    """smhv_ballistic: a line's two directions (256 bytes)."""
+    _fields_ = [("dir", BallisticSolution * 2)]
+
+
+class BallisticResult(C.Structure):
+    _fields_ = [("n_lines", C.c_uint32), ("reserved", C.c_uint32 * 3), ("line", Ballistic * MAX_LINES)]
+
+
+class BallisticOptionsStruct(C.Structure):
+    """smhv_ballistic_options: what a ballistic map is computed from and how it is painted (96 bytes)."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("origin_mode", C.c_uint32), ("line", C.c_uint32), ("origin", C.c_float * 2),
+                ("iso_s", C.c_double), ("pal", (C.c_uint8 * 4) * 12), ("iso", C.c_uint8 * 4), ("reserved", C.c_uint32 * 3)]
+
+
+class BallisticMapResult(C.Structure):
+    """smhv_ballistic_map_result: a frame's summary of its ballistic map (96 bytes)."""
+    _fields_ = [("valid", C.c_uint32), ("source_mask", C.c_uint32), ("origin", C.c_float * 2), ("count", C.c_uint32 * 12), ("iso", C.c_uint32),
+                ("n_tof", C.c_uint32), ("tof_min", C.c_double), ("tof_max", C.c_double), ("reserved", C.c_uint32 * 2)]
+
+
+class BallisticPlanes(C.Structure):
+    """smhv_ballistic_planes: the device memory of the planes a batch call writes (16 bytes)."""
+    _fields_ = [("classes", C.c_void_p), ("tof", C.c_void_p)]
+
+
 CLEAR_MAX_SAMPLES = 256
 CLEAR_PROFILE = CLEAR_MAX_SAMPLES + 1                                  # floats of a line's profile row
 CLEAR_PAINT, CLEAR_BYTES = 1, 2                                        # smhv_clearance_options.flags
@@ -538,6 +597,22 @@ SIGNATURES = {
     "smhv_debug_render_form": (C.c_int, [C.c_uint32]),
     "smhv_debug_render_rule": (C.c_int, [C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "smhv_weapon_defaults": (C.c_int, [C.POINTER(WeaponStruct)]),
+    "smhv_weapon_check": (C.c_int, [C.POINTER(WeaponStruct)]),
+    "smhv_weapon_thresholds": (C.c_int, [C.POINTER(WeaponStruct), C.POINTER(WeaponRule)]),
+    "smhv_ballistic_solve": (C.c_int, [C.POINTER(WeaponStruct), C.c_double, C.c_double, C.POINTER(BallisticSolution)]),
+    "smhv_ballistic_defaults": (C.c_int, [C.POINTER(BallisticOptionsStruct)]),
+    "smhv_batch_ballistics": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(FiringOptions), C.POINTER(WeaponStruct), C.c_void_p]),
+    "smhv_batch_read_ballistics": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(BallisticResult)]),
+    "smhv_batch_ballistics_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smhv_ballistic_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(FiringOptions),
+                                       C.POINTER(WeaponStruct), C.POINTER(Ballistic)]),
+    "smhv_batch_ballistic_map": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(WeaponStruct),
+                                           C.POINTER(BallisticOptionsStruct), C.POINTER(BallisticPlanes), C.c_void_p]),
+    "smhv_batch_read_ballistic_map": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(BallisticMapResult)]),
+    "smhv_batch_ballistic_map_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smhv_ballistic_map": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(WeaponStruct), C.POINTER(BallisticOptionsStruct),
+                                     C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BallisticMapResult)]),
 }
 
 

@@ -438,6 +438,48 @@ class FrameBatch:
         """Device address of the clearance-map slab (one smhv_clearance_map_result per frame)."""
         return self._slab_ptr(self._lib.smhv_batch_clearance_map_ptr)
 
+    def ballistics(self, weapon, first=0, n=None, heightmap=None, fit_to_minimap=True, viewport=None, stream=None):
+        """The weapon's solutions of the detected lines of frames [first, first + n) on `stream` (smhv_batch_ballistics): weapon = a
+        ballistics.Weapon; heightmap, fit_to_minimap, viewport as the firing solutions take them.  Asynchronous; read_ballistics()
+        waits for the records."""
+        n = self.max_frames - first if n is None else n
+        w = weapon.struct()
+        fo = L.firing_options(fit_to_minimap, viewport)
+        L.check(self._lib.smhv_batch_ballistics(self._b, first, n, L._hm(heightmap), C.byref(fo), C.byref(w), _ptr(stream)))
+
+    def read_ballistics(self, first=0, n=None):
+        """Synchronising host copy of the ballistics slab -> a ctypes array of n BallisticResult."""
+        return self._read_slab(self._lib.smhv_batch_read_ballistics, L.BallisticResult, first, n)
+
+    def ballistics_ptr(self):
+        """Device address of the ballistics slab (one smhv_ballistic_result per frame)."""
+        return self._slab_ptr(self._lib.smhv_batch_ballistics_ptr)
+
+    def ballistic_map(self, options, weapon, ballistic, first=0, n=None, heightmap=None, classes_ptr=None, tof_ptr=None, stream=None):
+        """The weapon's reach map of frames [first, first + n) on `stream` (smhv_batch_ballistic_map): options = a RenderOptions (the
+        window and the viewport; with paint the most recent render's), weapon = a ballistics.Weapon, ballistic = a BallisticOptions.
+        A plane that ballistic asks for and that has no pointer (device memory, n * out_h * out_w elements) is allocated as a torch
+        tensor [n, out_h, out_w] (uint8, float32), and the call then returns after the device has finished; with every plane's
+        pointer given, or no plane, it is asynchronous.  -> dict(classes=, tof=) of the tensors allocated here."""
+        n = self.max_frames - first if n is None else n
+        w, bo = weapon.struct(), ballistic.struct()
+        out = {}
+        shape = (n, int(options.out_h), int(options.out_w))
+        ptrs = [self._plane(out, name, ptr, getattr(ballistic, name), shape, "float32" if name == "tof" else "uint8")
+                for name, ptr in (("classes", classes_ptr), ("tof", tof_ptr))]
+        planes = L.BallisticPlanes(*[int(p) if p else None for p in ptrs])
+        self._call(out, self._lib.smhv_batch_ballistic_map, self._b, first, n, L._hm(heightmap), C.byref(options), C.byref(w), C.byref(bo), C.byref(planes),
+                   _ptr(stream))
+        return out
+
+    def read_ballistic_map(self, first=0, n=None):
+        """Synchronising host copy of the ballistic-map slab -> a ctypes array of n BallisticMapResult."""
+        return self._read_slab(self._lib.smhv_batch_read_ballistic_map, L.BallisticMapResult, first, n)
+
+    def ballistic_map_ptr(self):
+        """Device address of the ballistic-map slab (one smhv_ballistic_map_result per frame)."""
+        return self._slab_ptr(self._lib.smhv_batch_ballistic_map_ptr)
+
     def scale_labels(self, frames_ptr, n, stream=0):
         """The scale labels of frames [0, n) (smhv_batch_scale_labels), on `stream` behind this batch's run over the same frames
         (frames_ptr: what that run was given; its stages must include STAGE_OCR).  Asynchronous; read_scale_labels() waits for it."""

@@ -234,6 +234,40 @@ def reach_thresholds():
     return [float(v) for v in out]
 
 
+# ---- ballistics (smhv_batch_ballistic_map / smhv_ballistic_map): a caller-supplied weapon's reach map ------------------------------
+class BallisticOptions:
+    """What a ballistic-map call computes: origin as ReachOptions takes it; iso_s = seconds between isochrones (0: none); paint /
+    classes / tof = tint the render slab / write the class bytes / write the f32 time-of-flight plane; palette = None (the
+    library's, smhv_ballistic_defaults) or dict(pal=[12 rgba, classes 1 .. 12], iso=rgba), a = the blend weight."""
+
+    def __init__(self, origin=(0.0, 0.0), iso_s=0.0, paint=True, classes=False, tof=False, palette=None):
+        self.origin = origin
+        self.iso_s = float(iso_s)
+        self.paint = bool(paint)
+        self.classes = bool(classes)
+        self.tof = bool(tof)
+        self.palette = palette
+
+    def struct(self):
+        """-> smhv_ballistic_options."""
+        o = L.BallisticOptionsStruct()
+        L.check(L.load().smhv_ballistic_defaults(C.byref(o)))
+        o.flags = (L.BMAP_PAINT if self.paint else 0) | (L.BMAP_CLASSES if self.classes else 0) | (L.BMAP_TOF if self.tof else 0)
+        if isinstance(self.origin[0], str):
+            o.origin_mode = {"p0": L.REACH_ORIGIN_LINE_P0, "p1": L.REACH_ORIGIN_LINE_P1}[self.origin[0]]
+            o.line = int(self.origin[1])
+        else:
+            o.origin_mode = L.REACH_ORIGIN_POINT
+            o.origin[0], o.origin[1] = float(self.origin[0]), float(self.origin[1])
+        o.iso_s = self.iso_s
+        if self.palette is not None:
+            for k in range(4):
+                o.iso[k] = int(self.palette["iso"][k])
+                for j in range(12):
+                    o.pal[j][k] = int(self.palette["pal"][j][k])
+        return o
+
+
 # ---- terrain clearance (smhv_batch_clearance / smhv_clearance_lines / smhv_batch_clearance_map / smhv_clearance_map) ------------------
 class ClearanceOptions:
     """What a clearance call computes: samples = S, how many steps the line of fire is cut into (1 .. 256); margin_m = metres the arc

@@ -329,6 +329,36 @@ class HipVision:
                                          image.ctypes.data if image is not None else None, cls.ctypes.data if cls is not None else None, C.byref(res)))
         return cls, res
 
+    def ballistic_lines(self, lines, weapon, mpx=None, minimap=None, heightmap=None, fit_to_minimap=True, viewport=None):
+        """The weapon's solutions of explicit lines in map-ROI coordinates (smhv_ballistic_lines; stateless like firing_solutions):
+        lines: float32 [n, 4]; weapon = a ballistics.Weapon; the rest as firing_solutions takes it -> a ctypes array of n Ballistic."""
+        ln = np.ascontiguousarray(np.asarray(lines, np.float32).reshape(-1, 4))
+        n = ln.shape[0]
+        out = (L.Ballistic * n)()
+        w = weapon.struct()
+        opt = L.firing_options(fit_to_minimap, viewport)
+        m = C.byref(C.c_double(float(mpx))) if mpx is not None else None
+        L.check(self._lib.smhv_ballistic_lines(self._ctx, ln.ctypes.data if n else None, n, m, _minimap_arg(minimap), L._hm(heightmap), C.byref(opt),
+                                               C.byref(w), out if n else None))
+        return out
+
+    def ballistic_map(self, options, weapon, ballistic, mpx=None, minimap=None, heightmap=None, image=None, classes=True, tof=True):
+        """The weapon's reach map of one window (smhv_ballistic_map; stateless like reach_map): options = a RenderOptions (the window
+        and the viewport), weapon = a ballistics.Weapon, ballistic = a BallisticOptions with a point origin; mpx, minimap, heightmap:
+        the frame's, or None.  image: uint8 [out_h, out_w, 4], tinted in place; classes / tof: return that plane.
+        -> (uint8 [out_h, out_w] or None, float32 [out_h, out_w] or None, BallisticMapResult)."""
+        w, bo = weapon.struct(), ballistic.struct()
+        h, wd = _window_image_check("ballistic_map", image, options)
+        shape = (max(h, 1), max(wd, 1))
+        cls = np.empty(shape, np.uint8) if classes else None
+        tf = np.empty(shape, np.float32) if tof else None
+        res = L.BallisticMapResult()
+        m = C.byref(C.c_double(float(mpx))) if mpx is not None else None
+        L.check(self._lib.smhv_ballistic_map(self._ctx, L._hm(heightmap), C.byref(options), C.byref(w), C.byref(bo), m, _minimap_arg(minimap),
+                                             image.ctypes.data if image is not None else None, cls.ctypes.data if cls is not None else None,
+                                             tf.ctypes.data if tf is not None else None, C.byref(res)))
+        return cls, tf, res
+
     def clearance_lines(self, lines, clearance, minimap=None, heightmap=None, fit_to_minimap=True, viewport=None, profiles=False):
         """The terrain clearance of explicit lines in map-ROI coordinates (smhv_clearance_lines; stateless like firing_solutions):
         lines: float32 [n, 4]; clearance = a ClearanceOptions (samples, margin_m); minimap, heightmap, fit_to_minimap, viewport as
