@@ -1974,6 +1974,148 @@ SMHV_API int smhv_ballistic_map(smhv_ctx *ctx, const smhv_heightmap *hm, const s
                                 const smhv_ballistic_options *opt, const double *mpx, const uint32_t minimap[4], uint8_t *rgba_inout, uint8_t *classes,
                                 float *tof, smhv_ballistic_map_result *result);
 
+/* ---- ballistic clearance: a caller-supplied weapon's high and low arc against the terrain --------------------------------------------
+ * "ballistics" reads the heightmap at the two end points of a line; "terrain clearance" looks at what lies between them, but for the
+ * reference's mortar on its high arc alone.  This pass holds BOTH arcs of the caller's weapon against the terrain in one march: the
+ * low arc is where terrain masking bites, and a weapon that can fire both wants to know which of them gets through.  The high arc
+ * lies above the low arc everywhere between the ends (a_hi(x) - a_lo(x) = x (T_hi - T_lo)(1 - x / d) >= 0), so the answers of
+ * interest are "the low arc is blocked, the high one clears" and "the high arc is beyond the mount's limit, the low one clears or not".
+ * A verdict exists exactly where "terrain clearance" has one: the heightmap branch, all four rounded end-point coordinates inside the
+ *   heightmap.  The end coordinates (x0, y0), (x1, y1), d, h0, h1, alt, S, the texel of sample k, the terrain z and the sight line
+ *   l = alt * t are "terrain clearance"'s, word for word; d and alt are therefore bit-equal to smhv_ballistic_lines' meters and
+ *   alt_delta on that branch.  What changes is the arc.  Every operation is ONE IEEE f64 operation, left to right, unfused.
+ * Weapon terms, w = the weapon's smhv_weapon_rule ("ballistics": computed on the host once per call, never on the device):
+ *   disc = w.v4 - w.g * (w.g * (d * d) + 2.0 * alt * w.v2);  s = sqrt(disc);  gm = w.g * d;  and for each arc a in {SMHV_ARC_HIGH,
+ *   SMHV_ARC_LOW}:  T_a = (w.v2 + s) / gm (HIGH), (w.v2 - s) / gm (LOW);  qq1_a = 1.0 + T_a * T_a;  bal_a = "ballistics"' status bits
+ *   of (disc, d, T_a) -- SMHV_BAL_OUT_OF_RANGE, _BELOW_MIN_RANGE, _ELEV_LOW, _ELEV_HIGH exactly as defined there.
+ * Interior samples k = 1 .. S - 1:  t = (double)k / (double)S;  x = d * t;  per arc
+ *   a_a = x * T_a - ((w.g * (x * x)) * qq1_a) / (2.0 * w.v2);  m_a = a_a - z;  the sample blocks arc a iff m_a < opt->margin_m.
+ *   The sample blocks the sight line iff l < z.  With smhv_weapon_defaults this is "terrain clearance"'s expression on the high arc,
+ *   operation for operation, on bit-equal constants.
+ * Per arc (smhv_arc_clearance): status (SMHV_CLEAR_OUT_OF_RANGE / _CLEAR / _BLOCKED), first_blocked, n_blocked, min_margin, min_at are
+ *   smhv_clearance_dir's fields by its rules: !(disc >= 0) is OUT_OF_RANGE with no arc (first_blocked = S, the rest 0); d == 0.0 is
+ *   CLEAR with no samples; best starts at +inf and is replaced only when m < best (a NaN never wins, ties go to the lowest k);
+ *   min_margin is 0 when nothing replaced best or S == 1, min_at 0 while nothing replaced it.  bal = bal_a.  The march never looks at
+ *   bal: an arc beyond the mount's limit still gets its CLEAR or BLOCKED.
+ * Per direction (smhv_ballistic_clearance_dir): arc[2]; meters = d; alt_delta = alt; los_blocked = the count (also on an OUT_OF_RANGE
+ *   line, 0 when d == 0.0); valid = 1 iff a verdict exists -- otherwise the record is all zeros; choice = the arc to fire as 1 + a, or
+ *   0: 1 + w.arc if that arc's status is CLEAR and its bal is 0, otherwise 1 + the other arc under the same condition, otherwise 0.
+ *   Direction 1 is the rule on the line (P1, P0): end coordinates swapped, h0 := h1, alt := -alt.
+ * Dense (the ballistic clearance map): origin and target per window pixel are "reach map"'s (origin_mode, line, origin, the "no
+ *   origin" rule); the rule above, direction 0, gives one byte per pixel: bits 0..2 the class of the weapon's own arc (w.arc), bits
+ *   3..5 the class of the other arc, SMHV_BCLR_LOS (0x80) wherever the byte is not 0 and some sample blocks the sight line (d != 0.0),
+ *   bit 6 always 0.  The class of an arc, in order of precedence: 0 SMHV_BCLR_NONE no verdict; 1 _OUT_OF_RANGE !(disc >= 0);
+ *   2 _UNUSABLE the arc's bal != 0; 4 _BLOCKED d != 0.0 and some sample blocks it; 3 _CLEAR otherwise.  A pixel is a SWITCH pixel iff
+ *   its own class is 2 or 4 and the other arc's class is 3: fire the other arc.
+ *   bytes   (SMHV_BCLR_BYTES) out_w * out_h per frame, tightly packed.
+ *   margin  (SMHV_BCLR_MARGIN) f32 per pixel: (float) of the own arc's min_margin as the line record reports it (0 when nothing
+ *           replaced best) where the own class is 3 or 4; NaN elsewhere.
+ *   paint   (SMHV_BCLR_PAINT) "reach map"'s integer blend with pal[own class - 1], then on a switch pixel with switch_arc, then on a
+ *           pixel with the LOS bit with los; a weight of 0 leaves the pixel as it is.
+ *   summary one smhv_ballistic_clearance_map_result per frame, cleared on the stream ahead of the kernel: valid, origin as "reach
+ *           map"; own[c - 1], other[c - 1] = window pixels whose own / other arc has class c = 1 .. 4; los_blocked = pixels with the
+ *           LOS bit; switch_arc = switch pixels. */
+#define SMHV_BCLR_PAINT 1u             /* smhv_ballistic_clearance_options.flags: tint the render slab (per call: implied by rgba_inout) */
+#define SMHV_BCLR_BYTES 2u             /*   ... write the class bytes (per call: implied by bytes) */
+#define SMHV_BCLR_MARGIN 4u            /*   ... write the margin plane (per call: implied by margin) */
+#define SMHV_BCLR_NONE 0u              /* the class of an arc at a pixel */
+#define SMHV_BCLR_OUT_OF_RANGE 1u
+#define SMHV_BCLR_UNUSABLE 2u
+#define SMHV_BCLR_CLEAR 3u
+#define SMHV_BCLR_BLOCKED 4u
+#define SMHV_BCLR_LOS 0x80u            /* the map's byte: | this */
+typedef struct {
+	uint32_t size;                       /*  0: sizeof(smhv_ballistic_clearance_options) == 80 */
+	uint32_t flags;                      /*  4: SMHV_BCLR_PAINT | _BYTES | _MARGIN (the map only; 0: the summary alone) */
+	uint32_t samples;                    /*  8: S, 1 .. SMHV_CLEAR_MAX_SAMPLES */
+	uint32_t origin_mode;                /* 12: the map: SMHV_REACH_ORIGIN_* */
+	uint32_t line;                       /* 16: the map, _LINE_P0 / _LINE_P1: which line of the record, < SMHV_MAX_LINES */
+	uint32_t reserved0;                  /* 20: 0 */
+	float origin[2];                     /* 24: the map, _POINT: the origin, map-ROI coordinates */
+	double margin_m;                     /* 32: metres an arc must keep over the terrain; finite, >= 0 */
+	uint8_t pal[4][4];                   /* 40: the palette of own classes 1 .. 4: R, G, B and the blend weight a */
+	uint8_t switch_arc[4];               /* 56 */
+	uint8_t los[4];                      /* 60 */
+	uint32_t reserved[4];                /* 64: 0 */
+} smhv_ballistic_clearance_options;
+typedef struct {
+	uint32_t status;                     /*  0: SMHV_CLEAR_OUT_OF_RANGE / _CLEAR / _BLOCKED */
+	uint32_t first_blocked;              /*  4: the least k that blocks this arc; S when there is none */
+	uint32_t n_blocked;                  /*  8 */
+	uint32_t bal;                        /* 12: SMHV_BAL_* of this arc */
+	double min_margin;                   /* 16 */
+	uint32_t min_at;                     /* 24 */
+	uint32_t reserved;                   /* 28 */
+} smhv_arc_clearance;                    /* 32 bytes */
+typedef struct {
+	smhv_arc_clearance arc[2];           /*  0: [SMHV_ARC_HIGH], [SMHV_ARC_LOW] */
+	double meters;                       /* 64: d */
+	double alt_delta;                    /* 72: the target over the muzzle, as this direction sees it */
+	uint32_t los_blocked;                /* 80: samples that block the sight line (a count) */
+	uint32_t valid;                      /* 84: 1 iff a verdict exists; 0: the record is all zeros */
+	uint32_t choice;                     /* 88: 1 + the arc to fire, 0: neither */
+	uint32_t reserved;                   /* 92 */
+} smhv_ballistic_clearance_dir;          /* 96 bytes */
+typedef struct { smhv_ballistic_clearance_dir dir[2]; } smhv_ballistic_clearance;   /* 192 bytes: [0] from p0 at p1, [1] from p1 at p0 */
+typedef struct {
+	uint32_t n_lines, reserved[3];       /* == the record's n_lines; lines beyond it are zero */
+	smhv_ballistic_clearance line[SMHV_MAX_LINES];   /* 16 */
+} smhv_ballistic_clearance_result;
+typedef struct {
+	uint32_t valid;                      /*  0 */
+	uint32_t reserved0;                  /*  4 */
+	float origin[2];                     /*  8 */
+	uint32_t own[4];                     /* 16: pixels whose own arc has class 1 .. 4 */
+	uint32_t other[4];                   /* 32: ... whose other arc has */
+	uint32_t los_blocked;                /* 48 */
+	uint32_t switch_arc;                 /* 52 */
+	uint32_t reserved[2];                /* 56 */
+} smhv_ballistic_clearance_map_result;   /* 64 bytes */
+typedef struct {
+	void *bytes;                         /*  0: SMHV_BCLR_BYTES: out_w * out_h bytes per frame, device memory */
+	void *margin;                        /*  8: SMHV_BCLR_MARGIN: out_w * out_h floats per frame, device memory */
+} smhv_ballistic_clearance_planes;       /* 16 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(smhv_ballistic_clearance_options) == 80 && sizeof(smhv_arc_clearance) == 32 && sizeof(smhv_ballistic_clearance_dir) == 96,
+              "ballistic clearance layout");
+static_assert(sizeof(smhv_ballistic_clearance) == 192 && sizeof(smhv_ballistic_clearance_result) == 16 + 192 * SMHV_MAX_LINES &&
+              sizeof(smhv_ballistic_clearance_map_result) == 64 && sizeof(smhv_ballistic_clearance_planes) == 16, "ballistic clearance map layout");
+#endif
+/* Host only.  Fills *opt: size, flags = PAINT, samples = 64, origin_mode = POINT at (0, 0), margin_m = 0 and the palette -- out of
+ * range, unusable and clear (0, 0, 0, 0), blocked (230, 40, 40, 110), switch_arc (240, 190, 40, 110), los (0, 0, 0, 70). */
+SMHV_API int smhv_ballistic_clearance_defaults(smhv_ballistic_clearance_options *opt);
+/* Host only, no device needed: what the entry points below refuse in opt (SMHV_E_INVALID), and nothing else. */
+SMHV_API int smhv_ballistic_clearance_check(const smhv_ballistic_clearance_options *opt);
+/* Both arcs of the weapon against the terrain, for the detected lines of frames [first, first + n), asynchronously on `stream`, into
+ * the batch's ballistic-clearance slab (allocated by the first call): smhv_batch_clearance's contract with the weapon of
+ * smhv_batch_ballistics.  Of opt, samples and margin_m apply (the rest is checked).  No elevation profile is written here;
+ * smhv_batch_clearance gives one.  SMHV_E_INVALID: what smhv_weapon_check refuses, a wrong size, unknown flags, samples 0 or above
+ * SMHV_CLEAR_MAX_SAMPLES, a margin_m that is negative or not finite, an unknown origin_mode, line >= SMHV_MAX_LINES with a line origin,
+ * a reserved word that is not 0, what smhv_firing_solutions rejects in fopt, n == 0, a range beyond the batch's capacity, a heightmap on
+ * another device.  A failed call enqueues nothing. */
+SMHV_API int smhv_batch_ballistic_clearance(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_firing_options *fopt,
+                                            const smhv_weapon *weapon, const smhv_ballistic_clearance_options *opt, void *stream);
+SMHV_API int smhv_batch_read_ballistic_clearance(smhv_batch *b, uint32_t first, uint32_t n, smhv_ballistic_clearance_result *out);
+SMHV_API int smhv_batch_ballistic_clearance_ptr(smhv_batch *b, void **d_ballistic_clearance);
+/* The same for explicit lines, shaped like smhv_clearance_lines: out receives n records. */
+SMHV_API int smhv_ballistic_clearance_lines(smhv_ctx *ctx, const smhv_line *lines, uint32_t n, const uint32_t minimap[4], const smhv_heightmap *hm,
+                                            const smhv_firing_options *fopt, const smhv_weapon *weapon, const smhv_ballistic_clearance_options *opt,
+                                            smhv_ballistic_clearance *out);
+/* The ballistic clearance map of frames [first, first + n), asynchronously on `stream`: smhv_batch_clearance_map's contract (the
+ * results cleared ahead of the kernel, PAINT behind the most recent render and SMHV_E_STATE before it or at another window, the
+ * heightmap's reference) with the errors listed above.  planes (NULL: none) names the planes' device memory, each starting at the
+ * call's first frame; a plane flag without its pointer is refused. */
+SMHV_API int smhv_batch_ballistic_clearance_map(smhv_batch *b, uint32_t first, uint32_t n, const smhv_heightmap *hm, const smhv_render_options *ropt,
+                                                const smhv_weapon *weapon, const smhv_ballistic_clearance_options *opt,
+                                                const smhv_ballistic_clearance_planes *planes, void *stream);
+SMHV_API int smhv_batch_read_ballistic_clearance_map(smhv_batch *b, uint32_t first, uint32_t n, smhv_ballistic_clearance_map_result *out);
+SMHV_API int smhv_batch_ballistic_clearance_map_ptr(smhv_batch *b, void **d_ballistic_clearance_map);
+/* The per-call path, stateless like smhv_clearance_map: origin_mode must be POINT; rgba_inout, bytes (out_w * out_h bytes), margin
+ * (out_w * out_h floats) and result may each be NULL, not all of them.  opt->flags is checked and otherwise not used. */
+SMHV_API int smhv_ballistic_clearance_map(smhv_ctx *ctx, const smhv_heightmap *hm, const smhv_render_options *ropt, const smhv_weapon *weapon,
+                                          const smhv_ballistic_clearance_options *opt, const uint32_t minimap[4], uint8_t *rgba_inout, uint8_t *bytes,
+                                          float *margin, smhv_ballistic_clearance_map_result *result);
+
 #ifdef __cplusplus
 }
 #endif

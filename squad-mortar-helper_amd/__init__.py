@@ -17,6 +17,7 @@ from .render import LabelOptions, label_lines  # noqa: F401
 from .render import ReachOptions, reach_thresholds  # noqa: F401
 from .render import ClearanceOptions  # noqa: F401
 from .render import BallisticOptions  # noqa: F401
+from .render import BallisticClearanceOptions  # noqa: F401
 from . import ballistics  # noqa: F401
 from .ballistics import Weapon  # noqa: F401
 from .render import ReliefOptions, relief_light  # noqa: F401

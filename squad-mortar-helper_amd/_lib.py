@@ -261,6 +261,49 @@ class BallisticPlanes(C.Structure):
     _fields_ = [("classes", C.c_void_p), ("tof", C.c_void_p)]
 
 
+BCLR_PAINT, BCLR_BYTES, BCLR_MARGIN = 1, 2, 4                          # smhv_ballistic_clearance_options.flags
+BCLR_NONE, BCLR_OUT_OF_RANGE, BCLR_UNUSABLE, BCLR_CLEAR, BCLR_BLOCKED, BCLR_LOS = 0, 1, 2, 3, 4, 0x80   # an arc's class; the map's byte
+
+
+class BallisticClearanceOptionsStruct(C.Structure):
+    """smhv_ballistic_clearance_options: how the terrain is sampled against both arcs of a weapon and painted (80 bytes)."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("samples", C.c_uint32), ("origin_mode", C.c_uint32), ("line", C.c_uint32),
+                ("reserved0", C.c_uint32), ("origin", C.c_float * 2), ("margin_m", C.c_double), ("pal", (C.c_uint8 * 4) * 4), ("switch_arc", C.c_uint8 * 4),
+                ("los", C.c_uint8 * 4), ("reserved", C.c_uint32 * 4)]
+
+
+class ArcClearance(C.Structure):
+    """smhv_arc_clearance: one arc of one direction against the terrain (32 bytes)."""
+    _fields_ = [("status", C.c_uint32), ("first_blocked", C.c_uint32), ("n_blocked", C.c_uint32), ("bal", C.c_uint32), ("min_margin", C.c_double),
+                ("min_at", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BallisticClearanceDir(C.Structure):
+    """smhv_ballistic_clearance_dir: both arcs of one direction of a line (96 bytes)."""
+    _fields_ = [("arc", ArcClearance * 2), ("meters", C.c_double), ("alt_delta", C.c_double), ("los_blocked", C.c_uint32), ("valid", C.c_uint32),
+                ("choice", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BallisticClearance(C.Structure):
+    """smhv_ballistic_clearance: a line's two directions (192 bytes)."""
+    _fields_ = [("dir", BallisticClearanceDir * 2)]
+
+
+class BallisticClearanceResult(C.Structure):
+    _fields_ = [("n_lines", C.c_uint32), ("reserved", C.c_uint32 * 3), ("line", BallisticClearance * MAX_LINES)]
+
+
+class BallisticClearanceMapResult(C.Structure):
+    """smhv_ballistic_clearance_map_result: a frame's summary of its ballistic clearance map (64 bytes)."""
+    _fields_ = [("valid", C.c_uint32), ("reserved0", C.c_uint32), ("origin", C.c_float * 2), ("own", C.c_uint32 * 4), ("other", C.c_uint32 * 4),
+                ("los_blocked", C.c_uint32), ("switch_arc", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class BallisticClearancePlanes(C.Structure):
+    """smhv_ballistic_clearance_planes: the device memory of the planes a batch call writes (16 bytes)."""
+    _fields_ = [("bytes", C.c_void_p), ("margin", C.c_void_p)]
+
+
 CLEAR_MAX_SAMPLES = 256
 CLEAR_PROFILE = CLEAR_MAX_SAMPLES + 1                                  # floats of a line's profile row
 CLEAR_PAINT, CLEAR_BYTES = 1, 2                                        # smhv_clearance_options.flags
@@ -613,6 +656,21 @@ SIGNATURES = {
     "smhv_batch_ballistic_map_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "smhv_ballistic_map": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(WeaponStruct), C.POINTER(BallisticOptionsStruct),
                                      C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BallisticMapResult)]),
+    "smhv_ballistic_clearance_defaults": (C.c_int, [C.POINTER(BallisticClearanceOptionsStruct)]),
+    "smhv_ballistic_clearance_check": (C.c_int, [C.POINTER(BallisticClearanceOptionsStruct)]),
+    "smhv_batch_ballistic_clearance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(FiringOptions), C.POINTER(WeaponStruct),
+                                                 C.POINTER(BallisticClearanceOptionsStruct), C.c_void_p]),
+    "smhv_batch_read_ballistic_clearance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(BallisticClearanceResult)]),
+    "smhv_batch_ballistic_clearance_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smhv_ballistic_clearance_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(FiringOptions),
+                                                 C.POINTER(WeaponStruct), C.POINTER(BallisticClearanceOptionsStruct), C.POINTER(BallisticClearance)]),
+    "smhv_batch_ballistic_clearance_map": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(WeaponStruct),
+                                                     C.POINTER(BallisticClearanceOptionsStruct), C.POINTER(BallisticClearancePlanes), C.c_void_p]),
+    "smhv_batch_read_ballistic_clearance_map": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(BallisticClearanceMapResult)]),
+    "smhv_batch_ballistic_clearance_map_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smhv_ballistic_clearance_map": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderOptions), C.POINTER(WeaponStruct),
+                                               C.POINTER(BallisticClearanceOptionsStruct), C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(BallisticClearanceMapResult)]),
 }
 
 

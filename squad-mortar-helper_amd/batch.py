@@ -480,6 +480,49 @@ class FrameBatch:
         """Device address of the ballistic-map slab (one smhv_ballistic_map_result per frame)."""
         return self._slab_ptr(self._lib.smhv_batch_ballistic_map_ptr)
 
+    def ballistic_clearance(self, weapon, clearance, first=0, n=None, heightmap=None, fit_to_minimap=True, viewport=None, stream=None):
+        """Both arcs of the weapon against the terrain, for the detected lines of frames [first, first + n) on `stream`
+        (smhv_batch_ballistic_clearance): weapon = a ballistics.Weapon, clearance = a BallisticClearanceOptions (samples, margin_m);
+        heightmap, fit_to_minimap, viewport as the firing solutions take them.  Asynchronous; read_ballistic_clearance() waits."""
+        n = self.max_frames - first if n is None else n
+        w, co = weapon.struct(), clearance.struct()
+        fo = L.firing_options(fit_to_minimap, viewport)
+        L.check(self._lib.smhv_batch_ballistic_clearance(self._b, first, n, L._hm(heightmap), C.byref(fo), C.byref(w), C.byref(co), _ptr(stream)))
+
+    def read_ballistic_clearance(self, first=0, n=None):
+        """Synchronising host copy of the ballistic-clearance slab -> a ctypes array of n BallisticClearanceResult."""
+        return self._read_slab(self._lib.smhv_batch_read_ballistic_clearance, L.BallisticClearanceResult, first, n)
+
+    def ballistic_clearance_ptr(self):
+        """Device address of the ballistic-clearance slab (one smhv_ballistic_clearance_result per frame)."""
+        return self._slab_ptr(self._lib.smhv_batch_ballistic_clearance_ptr)
+
+    def ballistic_clearance_map(self, options, weapon, clearance, first=0, n=None, heightmap=None, bytes_ptr=None, margin_ptr=None, stream=None):
+        """The ballistic clearance map of frames [first, first + n) on `stream` (smhv_batch_ballistic_clearance_map): options = a
+        RenderOptions (the window and the viewport; with paint the most recent render's), weapon = a ballistics.Weapon, clearance = a
+        BallisticClearanceOptions.  A plane that clearance asks for and that has no pointer (device memory, n * out_h * out_w
+        elements) is allocated as a torch tensor [n, out_h, out_w] (uint8, float32), and the call then returns after the device has
+        finished; with every plane's pointer given, or no plane, it is asynchronous.  -> dict(bytes=, margin=) of the tensors
+        allocated here."""
+        n = self.max_frames - first if n is None else n
+        w, co = weapon.struct(), clearance.struct()
+        out = {}
+        shape = (n, int(options.out_h), int(options.out_w))
+        ptrs = [self._plane(out, name, ptr, getattr(clearance, name), shape, "float32" if name == "margin" else "uint8")
+                for name, ptr in (("bytes", bytes_ptr), ("margin", margin_ptr))]
+        planes = L.BallisticClearancePlanes(*[int(p) if p else None for p in ptrs])
+        self._call(out, self._lib.smhv_batch_ballistic_clearance_map, self._b, first, n, L._hm(heightmap), C.byref(options), C.byref(w), C.byref(co),
+                   C.byref(planes), _ptr(stream))
+        return out
+
+    def read_ballistic_clearance_map(self, first=0, n=None):
+        """Synchronising host copy of the ballistic-clearance-map slab -> a ctypes array of n BallisticClearanceMapResult."""
+        return self._read_slab(self._lib.smhv_batch_read_ballistic_clearance_map, L.BallisticClearanceMapResult, first, n)
+
+    def ballistic_clearance_map_ptr(self):
+        """Device address of the ballistic-clearance-map slab (one smhv_ballistic_clearance_map_result per frame)."""
+        return self._slab_ptr(self._lib.smhv_batch_ballistic_clearance_map_ptr)
+
     def scale_labels(self, frames_ptr, n, stream=0):
         """The scale labels of frames [0, n) (smhv_batch_scale_labels), on `stream` behind this batch's run over the same frames
         (frames_ptr: what that run was given; its stages must include STAGE_OCR).  Asynchronous; read_scale_labels() waits for it."""

@@ -1,6 +1,6 @@
 // smh_ballistics.h -- the rule of "ballistics" (include/smh_vision_hip.h): a caller-supplied weapon in the rule's terms, the two roots
 // of its firing solution from (meters, alt), and per root the elevation, the time of flight, the apex, the tangent of the angle of
-// fall, the dispersion's half widths, the status bits and the elevation band.  One text for the kernels (smh_ballistics.hip), the host
+// fall, the dispersion's half widths, the status bits and the elevation band; below them the per-arc steps of "ballistic clearance".  One text for the kernels (smh_ballistics.hip, smh_balclear.hip), the host
 // entry points (smh_ballistics.inc) and a stand-alone host check (tests/ballistics_rule_check.cpp compiles this header with the host
 // compiler), hence SMH_HD.  Built with -ffp-contract=off: every f64 operation below is the header's, in its order, unfused.  Below the
 // rule, for the HIP build alone: the launch interface of smh_ballistics.hip (the run structs live here and not in smh_kernels.h, which
@@ -99,6 +99,42 @@ SMH_HD smhv_ballistic_solution bal_solve(const smhv_weapon_rule &w, double m, do
 	return o;
 }
 
+// ---- "ballistic clearance" (smh_balclear.hip, tests/ballistic_clearance_rule_check.cpp): both arcs of the weapon held against the
+// terrain, one function per step of the header's rule so that the per-line kernel, the dense kernel and the host program run the same
+// operations.  What the two arcs share (t, the texel, z, x, w.g * (x * x)) is the caller's; what follows is per arc.
+// One arc of a line: its root, 1 + T * T and its status bits (s = sqrt(disc), gm = w.g * d)
+struct BalClearArc { double T, qq1; uint32_t bal; };
+SMH_HD BalClearArc bal_clear_arc(const smhv_weapon_rule &w, double disc, double s, double gm, double d, uint32_t arc) {
+	BalClearArc a;
+	a.T = bal_root(w, s, gm, arc);
+	a.qq1 = 1.0 + a.T * a.T;
+	a.bal = bal_status(w, disc, d, a.T);
+	return a;
+}
+// One sample against one arc: x = d * t, gxx = w.g * (x * x), den = 2.0 * w.v2, z = the terrain over the origin -> the margin m
+SMH_HD double bal_clear_sample(double x, double gxx, double T, double qq1, double den, double z) {
+	const double a = x * T - (gxx * qq1) / den;
+	return a - z;
+}
+// the sample blocks the sight line
+SMH_HD bool bal_clear_los(double alt, double t, double z) { return alt * t < z; }
+// an arc's status in the line record, its class in the map's byte (blocked: some sample blocked it)
+SMH_HD uint32_t bal_clear_status(bool oor, bool none, bool blocked) {
+	return oor ? SMHV_CLEAR_OUT_OF_RANGE : (!none && blocked) ? SMHV_CLEAR_BLOCKED : SMHV_CLEAR_CLEAR;
+}
+SMH_HD uint32_t bal_clear_class(bool oor, bool none, uint32_t bal, bool blocked) {
+	return oor ? SMHV_BCLR_OUT_OF_RANGE : bal ? SMHV_BCLR_UNUSABLE : (!none && blocked) ? SMHV_BCLR_BLOCKED : SMHV_BCLR_CLEAR;
+}
+// the arc to fire as 1 + a, or 0: the weapon's own if it is CLEAR and usable, else the other one under the same condition
+SMH_HD uint32_t bal_clear_choice(uint32_t own, const uint32_t status[2], const uint32_t bal[2]) {
+	const uint32_t other = 1u - own;
+	if (status[own] == SMHV_CLEAR_CLEAR && bal[own] == 0u) return 1u + own;
+	if (status[other] == SMHV_CLEAR_CLEAR && bal[other] == 0u) return 1u + other;
+	return 0u;
+}
+// min_margin as a record reports it: 0 when nothing replaced the starting +inf (no arc, no samples, S == 1, every m a NaN)
+SMH_HD double bal_clear_margin(double best) { return best == (double)INFINITY ? 0.0 : best; }
+
 }  // namespace smh
 
 // ---- the launch interface of smh_ballistics.hip
@@ -143,5 +179,47 @@ hipError_t launch_ballistic_lines(const BalLinesRun &r, uint32_t n, hipStream_t 
 // k_ballistic_map<paint, planes> over n frames (at most 65,535), then k_ballistic_finish over their summaries; the planes asked for are
 // the non-null pointers of r
 hipError_t launch_ballistic_map(const BalMapRun &r, uint32_t n, bool paint, hipStream_t s);
+
+// ---- the launch interface of smh_balclear.hip
+// smhv_batch_ballistic_clearance / smhv_ballistic_clearance_lines (k_bclear_lines): ClearLinesRun's fields and the weapon
+struct BalClearLinesRun {
+	FiringRun fr;                        // the heightmap and the viewport, as the firing solutions take them (`out` is not used)
+	smhv_weapon_rule w;
+	const smhv_frame_result *res;        // batch, per frame: n_lines, the lines, the minimap rectangle
+	const smhv_line *lines;              // per call: the explicit lines
+	smhv_ballistic_clearance_result *out;   // batch: the slab, at the first frame of the call
+	smhv_ballistic_clearance *out_lines; // per call: one record per line
+	double margin_m;
+	uint32_t samples;                    // S
+	uint32_t n_lines;                    // per call: of `lines`
+	uint32_t mm[4];                      // per call: the minimap rectangle (valid iff has_mm)
+	uint32_t per_call, has_mm;
+};
+// smhv_batch_ballistic_clearance_map / smhv_ballistic_clearance_map (k_bclear_map): ClearMapRun's fields, the weapon and the planes
+#define SMH_BCLR_ROWS 2u                 // rows per lane: a tile of SMH_REACH_TW x SMH_REACH_TH is 8 waves
+#define SMH_BCLR_THREADS (64u * (SMH_REACH_TH / SMH_BCLR_ROWS))
+struct BalClearMapRun {
+	FiringRun fr;
+	smhv_weapon_rule w;
+	const FrameAux *aux;                 // batch, per frame: open
+	const smhv_frame_result *res;        // batch, per frame: the minimap rectangle, the lines (the origin)
+	smhv_ballistic_clearance_map_result *out;   // the slab, at the first frame of the call; cleared ahead of the launch
+	uint8_t *img;                        // PAINT: the render slab, at the first frame of the call
+	uint8_t *bytes;                      // the planes (null: not asked for): out_w * out_h elements per frame
+	float *margin;
+	uint64_t img_stride, plane_stride;   // out_w * out_h * 4 bytes, out_w * out_h elements
+	double margin_m;
+	float origin[2];                     // SMHV_REACH_ORIGIN_POINT
+	uint32_t mm[4];                      // per call: the minimap rectangle (valid iff has_mm)
+	uint32_t out_w, out_h;
+	uint32_t samples;                    // S
+	uint32_t origin_mode, line;
+	uint32_t per_call, has_mm;           // 1: mm / has_mm are the call's and aux, res are not read
+	uint32_t pal[6];                     // own classes 1 .. 4, switch_arc, los: R, G, B, a as a little-endian word
+};
+// k_bclear_lines over n frames x SMHV_MAX_LINES lines x 2 directions (per call: n = 1, r.n_lines lines)
+hipError_t launch_bclear_lines(const BalClearLinesRun &r, uint32_t n, hipStream_t s);
+// k_bclear_map<paint, planes> over n frames (at most 65,535); the planes asked for are the non-null pointers of r
+hipError_t launch_bclear_map(const BalClearMapRun &r, uint32_t n, bool paint, hipStream_t s);
 }  // namespace smh
 #endif

@@ -293,6 +293,9 @@ struct smhv_batch {
 	smhv_ballistic_result *d_bal = nullptr;
 	smhv_ballistic_map_result *d_bal_map = nullptr;
 	smhv_heightmap *bal_hm = nullptr, *bal_map_hm = nullptr;
+	smhv_ballistic_clearance_result *d_bclear = nullptr;
+	smhv_ballistic_clearance_map_result *d_bclear_map = nullptr;
+	smhv_heightmap *bclear_hm = nullptr, *bclear_map_hm = nullptr;
 	// smhv_batch_scale_labels: the label slab, the crop slab and the family's own find_scales_preprocess plane with start row 0
 	// (allocated by the first call); what the batch's most recent run covered (its stages and frame count)
 	smhv_scale_label_frame *d_sl = nullptr;
@@ -693,7 +696,7 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	void *ptrs[] = {b->d_ui, b->d_ui_luma, b->d_ui_form, b->d_mask, b->d_bits, b->d_tiled, b->d_occ, b->d_ocr, b->d_scales, b->d_aux, b->d_results, b->d_anchors, b->d_bars, b->d_farm,
 	                b->d_lsd_ctl, b->d_lsd_req, b->d_lsd_cache, b->d_firing, b->d_fire_run, b->d_overlay, b->d_render, b->d_prims, b->d_labels,
 	                b->d_label_cull, b->d_label_extra, b->d_probes, b->d_dbg_items, b->d_dbg_pool, b->d_dbg_stage, b->d_reach, b->d_clear, b->d_clear_map, b->d_relief, b->d_grid, b->d_grid_refs,
-	                b->d_bal, b->d_bal_map, b->d_sl, b->d_sl_crops, b->d_sl_s0, b->d_lt, b->d_lt_anchors};
+	                b->d_bal, b->d_bal_map, b->d_bclear, b->d_bclear_map, b->d_sl, b->d_sl_crops, b->d_sl_s0, b->d_lt, b->d_lt_anchors};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	if (b->h_prims) (void)hipHostFree(b->h_prims);
@@ -722,6 +725,8 @@ extern "C" SMHV_API void smhv_batch_destroy(smhv_batch *b) {
 	hm_release(b->grid_hm);
 	hm_release(b->bal_hm);
 	hm_release(b->bal_map_hm);
+	hm_release(b->bclear_hm);
+	hm_release(b->bclear_map_hm);
 	if (b->ev_render) (void)hipEventDestroy(b->ev_render);
 	if (b->ev) {
 		for (int r = 0; r < smhv_batch::TIMING_RING; ++r)
@@ -3503,5 +3508,6 @@ extern "C" SMHV_API int smhv_heightmap_overlay(smhv_ctx *c, const smhv_heightmap
 #include "smh_relief.inc"
 #include "smh_grid.inc"
 #include "smh_ballistics.inc"
+#include "smh_balclear.inc"
 #include "smh_scalelabels.inc"
 #include "smh_labeltext.inc"

@@ -268,6 +268,44 @@ class BallisticOptions:
         return o
 
 
+# ---- ballistic clearance (smhv_batch_ballistic_clearance / _lines / smhv_batch_ballistic_clearance_map / smhv_ballistic_clearance_map)
+class BallisticClearanceOptions:
+    """What a ballistic-clearance call computes: samples = S (1 .. 256); margin_m = metres an arc must keep over the terrain.  The map
+    only: origin as ReachOptions takes it; paint / bytes / margin = tint the render slab / write the class bytes / write the f32 plane of
+    the own arc's least margin; palette = None (the library's, smhv_ballistic_clearance_defaults) or dict(pal=[4 rgba: out of range,
+    unusable, clear, blocked], switch_arc=rgba, los=rgba), a = the blend weight."""
+
+    def __init__(self, samples=64, margin_m=0.0, origin=(0.0, 0.0), paint=True, bytes=False, margin=False, palette=None):
+        self.samples = int(samples)
+        self.margin_m = float(margin_m)
+        self.origin = origin
+        self.paint = bool(paint)
+        self.bytes = bool(bytes)
+        self.margin = bool(margin)
+        self.palette = palette
+
+    def struct(self):
+        """-> smhv_ballistic_clearance_options."""
+        o = L.BallisticClearanceOptionsStruct()
+        L.check(L.load().smhv_ballistic_clearance_defaults(C.byref(o)))
+        o.flags = (L.BCLR_PAINT if self.paint else 0) | (L.BCLR_BYTES if self.bytes else 0) | (L.BCLR_MARGIN if self.margin else 0)
+        o.samples = self.samples
+        o.margin_m = self.margin_m
+        if isinstance(self.origin[0], str):
+            o.origin_mode = {"p0": L.REACH_ORIGIN_LINE_P0, "p1": L.REACH_ORIGIN_LINE_P1}[self.origin[0]]
+            o.line = int(self.origin[1])
+        else:
+            o.origin_mode = L.REACH_ORIGIN_POINT
+            o.origin[0], o.origin[1] = float(self.origin[0]), float(self.origin[1])
+        if self.palette is not None:
+            for k in range(4):
+                o.switch_arc[k] = int(self.palette["switch_arc"][k])
+                o.los[k] = int(self.palette["los"][k])
+                for j in range(4):
+                    o.pal[j][k] = int(self.palette["pal"][j][k])
+        return o
+
+
 # ---- terrain clearance (smhv_batch_clearance / smhv_clearance_lines / smhv_batch_clearance_map / smhv_clearance_map) ------------------
 class ClearanceOptions:
     """What a clearance call computes: samples = S, how many steps the line of fire is cut into (1 .. 256); margin_m = metres the arc

@@ -359,6 +359,35 @@ class HipVision:
                                              tf.ctypes.data if tf is not None else None, C.byref(res)))
         return cls, tf, res
 
+    def ballistic_clearance_lines(self, lines, weapon, clearance, minimap=None, heightmap=None, fit_to_minimap=True, viewport=None):
+        """Both arcs of the weapon against the terrain along explicit lines in map-ROI coordinates (smhv_ballistic_clearance_lines;
+        stateless like clearance_lines): lines: float32 [n, 4]; weapon = a ballistics.Weapon; clearance = a BallisticClearanceOptions
+        (samples, margin_m); the rest as clearance_lines takes it -> a ctypes array of n BallisticClearance."""
+        ln = np.ascontiguousarray(np.asarray(lines, np.float32).reshape(-1, 4))
+        n = ln.shape[0]
+        out = (L.BallisticClearance * n)()
+        w, co = weapon.struct(), clearance.struct()
+        opt = L.firing_options(fit_to_minimap, viewport)
+        L.check(self._lib.smhv_ballistic_clearance_lines(self._ctx, ln.ctypes.data if n else None, n, _minimap_arg(minimap), L._hm(heightmap), C.byref(opt),
+                                                         C.byref(w), C.byref(co), out if n else None))
+        return out
+
+    def ballistic_clearance_map(self, options, weapon, clearance, minimap=None, heightmap=None, image=None, bytes=True, margin=True):
+        """The ballistic clearance map of one window (smhv_ballistic_clearance_map; stateless like clearance_map): options = a
+        RenderOptions, weapon = a ballistics.Weapon, clearance = a BallisticClearanceOptions with a point origin.  image: uint8 [out_h,
+        out_w, 4], tinted in place; bytes / margin: return that plane.
+        -> (uint8 [out_h, out_w] or None, float32 [out_h, out_w] or None, BallisticClearanceMapResult)."""
+        w, co = weapon.struct(), clearance.struct()
+        h, wd = _window_image_check("ballistic_clearance_map", image, options)
+        shape = (max(h, 1), max(wd, 1))
+        by = np.empty(shape, np.uint8) if bytes else None
+        mg = np.empty(shape, np.float32) if margin else None
+        res = L.BallisticClearanceMapResult()
+        L.check(self._lib.smhv_ballistic_clearance_map(self._ctx, L._hm(heightmap), C.byref(options), C.byref(w), C.byref(co), _minimap_arg(minimap),
+                                                       image.ctypes.data if image is not None else None, by.ctypes.data if by is not None else None,
+                                                       mg.ctypes.data if mg is not None else None, C.byref(res)))
+        return by, mg, res
+
     def clearance_lines(self, lines, clearance, minimap=None, heightmap=None, fit_to_minimap=True, viewport=None, profiles=False):
         """The terrain clearance of explicit lines in map-ROI coordinates (smhv_clearance_lines; stateless like firing_solutions):
         lines: float32 [n, 4]; clearance = a ClearanceOptions (samples, margin_m); minimap, heightmap, fit_to_minimap, viewport as
